@@ -1,8 +1,13 @@
 """Headline benchmark: training images/sec of the WESUP step on GlaS-shaped synthetic patches.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs if ``--dump-outputs`` is given and
+prints the line (``value`` images/s, ``ms_per_step``).  Everything else the line can carry -- the per-box probe, the
+per-step median, HIP-event kernel timing and the roofline objects, the all-reduce profile of multi-GPU runs and the
+CPU baseline -- is measured with ``--full`` only (``--no-kernel-timing`` / ``--no-cpu-baseline`` leave parts out).
 
 A step is one full training iteration (BASELINE.json metric): superpixel
 preprocessing from the label map -> forward -> loss (label propagation + CE) -> backward ->
@@ -45,8 +50,12 @@ def parse_args(argv=None):
     ap.add_argument('--batch', type=int, default=4, help='images per GPU (BASELINE configs[1]: 4)')
     ap.add_argument('--size', type=int, default=480)
     ap.add_argument('--grid', type=int, default=24, help='superpixel grid side: g*g superpixels per image')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-kernel-timing', action='store_true')
+    ap.add_argument('--full', action='store_true', help='also measure what the headline does not need: per-box probe, per-step '
+                    'median, kernel timing + roofline objects, all-reduce profile, CPU baseline (untimed extras after the timed steps)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default='', help='after the timed steps, write what the last timed step '
+                    'computed (loss, metrics, updated parameters, gradients; a fixed sample of the large tensors) as DIR/<name>.npy')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: leave out the CPU baseline')
+    ap.add_argument('--no-kernel-timing', action='store_true', help='with --full: leave out the probe, kernel timing and roofline')
     ap.add_argument('--direct-conv', action='store_true', help='A/B: forward and input gradient of every conv layer with '
                                                                'the direct implicit-GEMM kernel (no Winograd-domain conv)')
     ap.add_argument('--direct-wgrad', action='store_true', help='A/B: every conv weight gradient with the direct '
@@ -149,6 +158,41 @@ def roofline_inputs(B, H, W, g):
     return None
 
 
+DUMP_SAMPLE = 1 << 18            # --dump-outputs: elements kept of a larger tensor (fixed, seeded sample)
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(trainer, out_dir):
+    """--dump-outputs: what a caller of the timed step receives from its last iteration -- the tracker's loss and metrics
+    (float64), the updated parameters and their gradients (float32).  A tensor of more than DUMP_SAMPLE elements is
+    written as the same seeded sample of its flattened elements (ascending indices) in every run."""
+    import numbers
+    import zlib
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+    for key, vals in sorted(trainer.tracker.history.items()):
+        if vals and isinstance(vals[-1], numbers.Real):
+            arrays[key] = np.array([vals[-1]], dtype=np.float64)
+    model = trainer.model
+    for name, p in model.named_parameters():
+        grad = p.grad if p.grad is not None else model._grad_views[name]
+        for prefix, t in (('param', p.detach()), ('grad', grad)):
+            flat = t.reshape(-1)
+            if flat.numel() > DUMP_SAMPLE:
+                rs = np.random.RandomState(zlib.crc32(name.encode()))
+                idx = np.sort(rs.choice(flat.numel(), DUMP_SAMPLE, replace=False))
+                flat = flat[torch.from_numpy(idx).to(flat.device)]
+            arrays[f'{prefix}.{name}'] = flat.float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f'--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES} byte limit')
+    for key, a in arrays.items():
+        np.save(os.path.join(out_dir, key + '.npy'), a)
+    return len(arrays), total
+
+
 def host_cpu():
     try:
         with open('/proc/cpuinfo') as f:
@@ -217,6 +261,8 @@ def worker(args):
     if args.stub_trainer:
         return stub_worker(args, rank, world)
     if args.multiscale or args.end_to_end:            # second lines: throughput only (the roofline objects belong to the headline)
+        args.no_kernel_timing = args.no_cpu_baseline = True
+    if not args.full:                                 # a plain run measures the headline and nothing else
         args.no_kernel_timing = args.no_cpu_baseline = True
     # stdout carries ONE line, the JSON of rank 0: whatever a library prints there while the step runs (RCCL announces its
     # version on stdout when the first communicator is created) goes to stderr instead -- at the descriptor level, native
@@ -385,7 +431,8 @@ def worker(args):
     timer.only = None if args.timed_classes == 'all' else set(args.timed_classes.split(','))
     n_sampled = 0
     reducer = getattr(trainer, 'reducer', None)
-    marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]      # one record per step: its end
+    # --full: one record per step, its end (the per-step median)
+    marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)] if args.full else None
     if timing_on:
         # The event-carrying steps of the timed region take their events from the timer's free list: made (and recorded once) here.
         # Creating them inside the region made the runtime grow its signal pool there -- one step of 79 ms in a 60-step batch-1 run
@@ -407,26 +454,33 @@ def worker(args):
     ev_off = args.event_every // 2 if args.steps > args.event_every // 2 else 0      # a short run (--steps 5) still has one such step
     barrier()
     t0 = time.perf_counter()
-    marks[0].record()
+    if marks:
+        marks[0].record()
     for i in range(args.steps):
         # an event record fences its queue (events on the 25 conv launches of every step cost 3 % of the step, on every
         # kernel class 16 %): inside the timed region only every --event-every'th step carries events
         timer.enabled = timing_on and i % args.event_every == ev_off      # (not the region's first step where there is another)
         n_sampled += int(timer.enabled)
-        if reducer is not None:                       # bucket launch offsets + exposed all-reduce tail of the same steps
+        if reducer is not None and args.full:         # bucket launch offsets + exposed all-reduce tail of the same steps
             reducer.profile = (i % args.event_every == ev_off)
         step(i)
-        marks[i + 1].record()
+        if marks:
+            marks[i + 1].record()
     barrier()
     elapsed = time.perf_counter() - t0
     timer.enabled = False
-    step_ms_raw = [marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)]
-    if os.environ.get('WESUP_BENCH_STEPS'):
-        print('per-step ms:', ' '.join(f'{v:.2f}' for v in step_ms_raw), file=sys.stderr)
-    step_ms = sorted(step_ms_raw)
-    median_ms = step_ms[len(step_ms) // 2] if len(step_ms) % 2 else 0.5 * (step_ms[len(step_ms) // 2 - 1] + step_ms[len(step_ms) // 2])
+    median_ms = None
+    if marks:
+        step_ms_raw = [marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)]
+        if os.environ.get('WESUP_BENCH_STEPS'):
+            print('per-step ms:', ' '.join(f'{v:.2f}' for v in step_ms_raw), file=sys.stderr)
+        step_ms = sorted(step_ms_raw)
+        median_ms = step_ms[len(step_ms) // 2] if len(step_ms) % 2 else 0.5 * (step_ms[len(step_ms) // 2 - 1] + step_ms[len(step_ms) // 2])
+    if args.dump_outputs and rank == 0:               # the last timed step's results, before any untimed extra step moves them
+        n_dumped, dumped_bytes = dump_outputs(trainer, args.dump_outputs)
+        print(f'--dump-outputs: {n_dumped} arrays, {dumped_bytes} bytes in {args.dump_outputs}', file=sys.stderr)
     ddp_stats = None
-    if reducer is not None:
+    if reducer is not None and args.full:
         reducer.profile = False
         ddp_stats = reducer.collect_stats()
     rank_time = None
@@ -489,7 +543,8 @@ def worker(args):
         out = {
             'metric': 'training images/sec, GlaS 480x480 VGG16 ~600 SP/img', 'value': round(value, 3), 'unit': 'images/s',
             'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': round(ms_per_step, 3),
-            'ms_per_step_median': round(median_ms, 3),      # of the per-step GPU times (an event at the end of every step)
+            # --full: of the per-step GPU times (an event at the end of every step)
+            'ms_per_step_median': None if median_ms is None else round(median_ms, 3),
             'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
             'config': {'workload': workload_label(B, H, W, g),
                        'global_batch': world * B, 'image': [H, W], 'superpixels': g * g,

@@ -85,7 +85,7 @@ def test_bench_two_ranks_over_rccl_reports_the_collective():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
     r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '6', '--warmup', '2',
-                        '--no-cpu-baseline', '--no-kernel-timing'], env=env, capture_output=True, text=True, timeout=900)
+                        '--full', '--no-cpu-baseline', '--no-kernel-timing'], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][-1])
     col = out['collective']

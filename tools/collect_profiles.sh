@@ -3,7 +3,7 @@
 #   bash tools/collect_profiles.sh r03                       # BASELINE configs[1]: batch 4, 480x480, 576 superpixels
 #   bash tools/collect_profiles.sh r03_c4 4 800 39           # per-GPU shard of configs[3]
 #   bash tools/collect_profiles.sh r03_c5 8 1024 55          # per-GPU shard of configs[4]
-# 1. bench.py plain -> bench_line.json (run LAST, so that it reads this round's counter inputs);  2. the same command under
+# 1. bench.py --full -> bench_line.json (run LAST, so that it reads this round's counter inputs);  2. the same command under
 #    rocprofv3 --kernel-trace --stats -> kernel stats;
 # 3. PMC counters over bench.py itself, one rocprofv3 run per counter group with no trace domain beside it
 #    (MI355X_MICROARCH.md: FETCH_SIZE and WRITE_SIZE in passes of their own) -> traffic and MFMA-busy per kernel class;
@@ -22,7 +22,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 # rocprofv3 starts the HIP runtime before python does: what bench.py sets at import time comes too late under the profiler
 export GPU_MAX_HW_QUEUES=6
 CPUB=""; [ "$SIZE" != "480" ] && CPUB="--no-cpu-baseline"      # the CPU baseline is config c1's: timed once, on the 480 line
-timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 bench.py $SHAPE --steps 10 --warmup 3 --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/bench_under_rocprof.err || exit 1
+timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 bench.py $SHAPE --full --steps 10 --warmup 3 --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/bench_under_rocprof.err || exit 1
 echo "stats done"
 find $OUT/stats -name "*kernel_stats.csv" -exec cp {} $OUT/kernel_stats.csv \;
 rm -rf $OUT/stats
@@ -31,7 +31,7 @@ pmc() {   # name, counters, program args...
     timeout -k 10 400 rocprofv3 --pmc $ctrs --output-format csv -d $OUT/pmc_$name -- python3 "$@" > $OUT/pmc_$name.log 2>&1 || { echo "pmc $name failed"; tail -5 $OUT/pmc_$name.log; return 1; }
     echo "pmc $name done"
 }
-BENCH="bench.py $SHAPE --steps 2 --warmup 1 --no-cpu-baseline"
+BENCH="bench.py $SHAPE --full --steps 2 --warmup 1 --no-cpu-baseline"
 pmc bench_fetch "FETCH_SIZE" $BENCH &&
 pmc bench_write "WRITE_SIZE" $BENCH &&
 pmc bench_mfma "SQ_VALU_MFMA_BUSY_CYCLES" $BENCH &&
@@ -45,7 +45,7 @@ timeout -k 10 400 python3 tools/wino_table.py --size $SIZE --batch $BATCH --reps
 python3 tools/roofline_inputs.py $OUT $R $BATCH $SIZE $GRID > $OUT/roofline_inputs.log 2>&1 || { echo "roofline_inputs failed"; tail -5 $OUT/roofline_inputs.log; }
 cp profiles/${R}_roofline_inputs.json profiles/${R}_layer_mfma.csv $OUT/ 2>/dev/null
 # the bench line itself, last: the counter inputs of this shape and round exist now (its roofline.traffic reads them)
-timeout -k 10 500 python3 bench.py $SHAPE $CPUB > $OUT/bench_line.json 2> $OUT/bench_line.err || { tail -5 $OUT/bench_line.err; exit 1; }
+timeout -k 10 500 python3 bench.py $SHAPE --full $CPUB > $OUT/bench_line.json 2> $OUT/bench_line.err || { tail -5 $OUT/bench_line.err; exit 1; }
 echo "bench done"
 # traffic past L2 per kernel over a whole step (the same two counter passes, all kernels): profiles/<tag>_step_traffic.txt
 python3 tools/step_traffic.py $OUT/pmc_bench_fetch $OUT/pmc_bench_write auto > $OUT/step_traffic.txt 2>/dev/null

@@ -65,7 +65,7 @@ def main():
     B, H, g = (int(v) for v in sys.argv[3:6]) if len(sys.argv) >= 6 else (4, 480, 24)
     W, N = H, g * g
     res = {'round': rnd, 'shape': {'batch': B, 'H': H, 'W': W, 'superpixels': N},
-           'how': f'rocprofv3 --pmc passes over `python3 bench.py --batch {B} --size {H} --grid {g} --steps 2 --warmup 1 --no-cpu-baseline` (one counter '
+           'how': f'rocprofv3 --pmc passes over `python3 bench.py --batch {B} --size {H} --grid {g} --full --steps 2 --warmup 1 --no-cpu-baseline` (one counter '
                   'group per pass, no trace domain beside it); per-launch means over every launch of the kernel class in '
                   'the run; bytes = (2*FETCH_SIZE + WRITE_SIZE) * 1024 (gfx950 FETCH_SIZE correction)'}
     fetch, nf = per_class(read_pass(os.path.join(out_dir, 'pmc_bench_fetch')), 'FETCH_SIZE')

@@ -6,7 +6,7 @@ R=${1:-r04}
 O=gpurun_out/lines; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 export GPU_MAX_HW_QUEUES=6
-b() { local out=$1; shift; timeout -k 10 300 python3 bench.py --no-cpu-baseline "$@" > $O/$out.json 2> $O/$out.err || { tail -3 $O/$out.err; exit 1; }; }
+b() { local out=$1; shift; timeout -k 10 300 python3 bench.py --full --no-cpu-baseline "$@" > $O/$out.json 2> $O/$out.err || { tail -3 $O/$out.err; exit 1; }; }
 b ${R}_e2e_bench_line --end-to-end --steps 40 --warmup 10
 b ${R}_multiscale_bench_line --multiscale 12 --no-kernel-timing --steps 120 --warmup 60
 b ${R}_multiscale_walk_bench_line --multiscale 12 --no-kernel-timing --steps 120 --warmup 60 --no-step-plan
