@@ -126,12 +126,14 @@ def forced_step(weights, imgs, segs, masks, y_gpu, dtype=torch.float64, tie_tol=
     if mlp_gpu is not None:
         orc.mlp_head = mlp
     total = 0.0
+    forced_step.last_sp_in = []                                    # each image's superpixel input of the fc layers (N, 2112)
     try:
         for b in range(B):                                         # one image at a time: the graph of one image is
             cur['b'] = b                                           # several GB at 480x480 in fp64
             o = orc.forward_image(w, torch.from_numpy(imgs[b]).to(dtype), torch.from_numpy(segs[b].astype(np.int64)),
                                   None if masks is None else torch.from_numpy(masks[b].astype(np.int64)))
             pp = o['pp']
+            forced_step.last_sp_in.append(o['sp_in'].detach())
             if pseudo_gpu is not None and pp['n_l'] < pp['K'] and loss_kw.get('enable_propagation', True):
                 thr = loss_kw.get('propagate_threshold', 0.8)
                 n, n_l = pp['K'], pp['n_l']
@@ -185,6 +187,7 @@ def check_gradients(model, weights, imgs, segs, masks, names=None, tol=1e-4, tie
                                     loss_kw.get('propagate_threshold', 0.8))
         pseudo = y_all.cpu()
     _, g64, named = forced_step(weights, imgs, segs, masks, ys, torch.float64, tie_tol, mlp_gpu=hs, pseudo_gpu=pseudo, **loss_kw)
+    sp_in64 = forced_step.last_sp_in
     bad = [n for n in named if not n['near_tie']]
     assert not bad, f'decisions that differ from fp64 without being near-ties: {bad[:5]}'
     # a handful of near-tie decisions per million units is what fp32 rounding produces; thousands would be a kernel
@@ -221,4 +224,5 @@ def check_gradients(model, weights, imgs, segs, masks, names=None, tol=1e-4, tie
                 _tol.within(case, 'torch CPU fp32 gradients vs fp64 (yardstick, no bar)', e_cpu, 1.0, 'the same measure for torch\'s own fp32 path')
     check_gradients.last_named = named
     check_gradients.last_g64 = g64          # (callers that hold the reference's own fp32 gradients measure ITS distance from these)
+    check_gradients.last_sp_in = sp_in64    # the fp64 superpixel inputs of the fc layers under the GPU's decisions, per image
     return worst, named.total

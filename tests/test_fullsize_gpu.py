@@ -21,6 +21,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from conftest import load_full_size_case          # noqa: E402
 import _gradcheck
+import _parity                              # noqa: E402
 import _tol                                 # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -103,6 +104,10 @@ def test_step_matches_the_reference_at_full_size(golden_dir, name):
     fm = model.feature_maps
     assert tuple(fm.shape) == (2112, H, W)
     assert _tol.within(name, 'feature map channel means vs reference', rel_err(fm.mean(dim=(1, 2)), fx['fm_chan_mean']), TOL, ref)
+    # ... and slice by slice: the 13 side outputs differ in magnitude, one max over 2112 channels would hide a small slice
+    ok, errs = _parity.check_sp_slices(name, 'feature map channel means per slice vs reference', fm.mean(dim=(1, 2)),
+                                       fx['fm_chan_mean'], TOL, 'the reference\'s per-channel means of the 2112-channel feature map')
+    assert ok, errs
     assert _tol.within(name, 'feature map samples vs reference', rel_err(fm[::97, ::23, ::29], fx['fm_sample']), TOL, ref)
     del fm
 
@@ -124,10 +129,16 @@ def test_step_matches_the_reference_at_full_size(golden_dir, name):
     # every parameter gradient against fp64 under the same ReLU / pooling decisions: 1e-4 of each tensor's max (fixed bar) ...
     worst, n_named = _gradcheck.check_gradients(model, weights, fx['img'][None], fx['seg'][None], fx['mask'][None], case=name)
     g64 = _gradcheck.check_gradients.last_g64
+    # the superpixel input of the fc layers, slice by slice, against the fp64 evaluation (the reference keeps no copy of it)
+    ok, errs = _parity.check_sp_slices(name, 'sp_in per slice vs oracle', model.engine._last.sp_in[0, :K],
+                                       _gradcheck.check_gradients.last_sp_in[0], TOL, 'GPU superpixel input of the fc layers against fp64')
+    assert ok, errs
     # ... and against the reference itself: the norm of every tensor, and 64 elements per tensor at north_star's 1e-4 of the
     # tensor's max -- PER TENSOR, with one named reason for anything above it: the reference's own fp32 CPU gradient is that far
     # from the fp64 evaluation at the very same elements (its sums carry summation-order noise -- conv1_1's dW adds 230 400
-    # mixed-sign products per element -- and it takes near-tie decisions its own way).  bar_k = 1e-4 + (the reference's own distance).
+    # mixed-sign products per element -- and it takes near-tie decisions its own way).  bar_k = min(1e-4 + (the reference's own
+    # distance), 1e-3), and that distance itself at most 1e-3 (worst observed 7.25e-4, profiles/r06_tolerances.json): a bug the
+    # oracle and the GPU shared would otherwise be absorbed into the reference's own distance.
     exceptions = []
     for k in [k[6:] for k in fx if k.startswith('gnorm.')]:
         g = model._grad_views[k]
@@ -140,13 +151,13 @@ def test_step_matches_the_reference_at_full_size(golden_dir, name):
         gmax = float(fx['gmax.' + k])
         ref_own = float(np.abs(fx['gsamp.' + k].astype(np.float64) - s64).max() / gmax)
         err = float(np.abs(samp - fx['gsamp.' + k]).max() / gmax)
-        _tol.within(name, 'reference fp32 gradient samples vs fp64 (the reference\'s own distance; no bar)', ref_own, 1.0,
-                    'the same 64 elements: |g_ref - g64| / max |g_ref|, fp64 under the GPU\'s decisions')
+        assert _tol.within(name, 'reference fp32 gradient samples vs fp64 (the reference\'s own distance)', ref_own, 1e-3,
+                           'the same 64 elements: |g_ref - g64| / max |g_ref|, fp64 under the GPU\'s decisions'), (k, ref_own)
         if err > 1e-4:
             exceptions.append((k, err, ref_own))
-        assert _tol.within(name, 'gradient samples vs reference (fp32 CPU), per-tensor bar', err, 1e-4 + ref_own,
-                           '64 elements per tensor, error / max |g_ref|; bar = 1e-4 + the reference\'s own distance from fp64 at '
-                           'the same elements (the one named reason for exceeding 1e-4)'), (k, err, ref_own)
+        assert _tol.within(name, 'gradient samples vs reference (fp32 CPU), per-tensor bar', err, min(1e-4 + ref_own, 1e-3),
+                           '64 elements per tensor, error / max |g_ref|; bar = min(1e-4 + the reference\'s own distance from fp64 at '
+                           'the same elements (the one named reason for exceeding 1e-4), 1e-3)'), (k, err, ref_own)
     _tol.within(name, 'gradient tensors above 1e-4 vs reference (count; each named with the reference\'s own fp64 distance)',
                 len(exceptions), len(exceptions), '; '.join(f'{k}: {e:.1e} (reference vs fp64 {r:.1e})' for k, e, r in exceptions) or 'none')
     print(f'{name}: worst gradient error vs fp64 {worst:.2e}, {n_named} near-tie decisions differ; tensors above 1e-4 of the '
@@ -198,6 +209,9 @@ def test_config_c2_exactly_matches_the_oracle():
         top2 = W_ul.topk(2, dim=1).values
         near = ((max_sim - 0.8).abs() < 1e-5) | ((top2[:, 0] - top2[:, 1]).abs() < 1e-5)   # threshold / runner-up within rounding
         assert _tol.within('c2_exact', 'sp_features vs oracle', rel_err(feats[b, :n], outs[b]['sp_features']), TOL)
+        ok, errs = _parity.check_sp_slices(f'c2_exact image {b}', 'sp_in per slice vs oracle', bufs.sp_in[b, :n],
+                                           outs[b]['sp_in'].detach(), TOL, 'GPU superpixel input of the fc layers against the oracle\'s fp32')
+        assert ok, (b, errs)
         # (how many rows the comparison below leaves out: recorded, and bounded -- a kernel whose arg-max drifted would mask many)
         assert _tol.within(f'c2_exact image {b}', 'propagation rows masked as near-ties before src / y_u are compared (count)',
                            int(near.sum()), MASKED_ROWS_BUDGET, f'of {n - n_l} unlabelled rows; near = max_sim within 1e-5 of the threshold '
@@ -280,6 +294,9 @@ def test_one_image_of_config_c5_matches_the_oracle():
     assert torch.equal(meta.perm[0, :n].cpu().long(), pp['perm']) and torch.equal(meta.sp_labels[0, :n_l].cpu(), pp['sp_labels'])
     feats = bufs.feats.view(1, meta.Kmax, -1)
     assert rel_err(feats[0, :n], outs[0]['sp_features']) < TOL
+    ok, errs = _parity.check_sp_slices('c5_one_image', 'sp_in per slice vs oracle', bufs.sp_in[0, :n], outs[0]['sp_in'].detach(), TOL,
+                                       'GPU superpixel input of the fc layers against the oracle\'s fp32')
+    assert ok, errs
     y_all, src, sim = ops.propagate(feats.contiguous(), meta, 0.8)
     y_u, W_ul, max_sim, src_ref = orc.label_propagate(outs[0]['sp_features'], pp['sp_labels'], 0.8, return_aux=True)
     top2 = W_ul.topk(2, dim=1).values
