@@ -341,8 +341,8 @@ int wesup_sp_pool_fwd(const float* fm, const int32_t* pix_sorted, const int32_t*
                       const int32_t* seg_start, const int32_t* unit_row, float* sp_feat,
                       int B, int HW, int ldf, int C, int Kmax, int Umax, void* ws, size_t ws_bytes, void* stream);
 /* fused upsample + scatter-mean: sp_feat[b][r][coff+c] = (1/area_r) sum_{p in row r} bilinear_ac(s[b], p)[c], s = side
- * output [B][h][w][C] (C in {32,64,128,256}); equals wesup_upsample_fwd followed by wesup_sp_pool_fwd on that slice
- * without materialising the (HW x 2112) feature map (models/wesup.py:254-261 + :283-285) */
+ * output [B][h][w][C] (C in {32,64,128,256} or a multiple of 256, which goes in slabs of 256 channels); equals
+ * wesup_upsample_fwd followed by wesup_sp_pool_fwd on that slice without materialising the (HW x 2112) feature map (models/wesup.py:254-261 + :283-285) */
 int wesup_sp_pool_upsample_fwd(const float* s, const int32_t* pix_sorted, const int32_t* row_start,
                                const int32_t* seg_start, const int32_t* unit_row, float* sp_feat,
                                int B, int h, int w, int H, int W, int C, int ldo, int coff, int Kmax, int Umax,

@@ -787,7 +787,7 @@ def test_maxpool(ops, B, H, W, C):
     base = rnd(B, H, W, C, seed=3)
     out = base.clone().to(d)
     ops.maxpool2_bwd(nhwc(y).to(d), nhwc(dyp).to(d), out, accumulate=True)
-    assert rel_err(nchw(out.cpu() - base), yr.grad) < 1e-6
+    assert torch.equal(out.cpu(), base + nhwc(yr.grad))           # every value is a copy or one fp32 add (tests/test_pooling_branches_gpu.py)
 
 
 @pytest.mark.parametrize('B,h,w,H,W,C', [(2, 4, 4, 8, 8, 32), (1, 2, 2, 32, 32, 256), (1, 15, 15, 240, 240, 64),
