@@ -423,6 +423,45 @@ size_t wesup_seg_metrics_workspace_bytes(int B);
 int wesup_seg_metrics(const float* pred, const uint8_t* mask, float* out4, int B, int HW, int C,
                       void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------ mask post-processing and challenge scoring (csrc/regions.hip)
+ * Integer image processing of predicted masks on the device: what scipy.ndimage / numpy do on the host in evaluate.py, infer.py
+ * and utils/metrics.py, bit for bit.  Masks are uint8 [B][H][W] (a pixel is set when it is non-zero), label maps int32.
+ *
+ * wesup_cc_label: connected components (connectivity 4 or 8, anything else is WESUP_ERR_INVALID) of the pixels where
+ * (mask != 0) == (value != 0); labels = 0 for the other pixels and 1..n_labels[b] in raster order of a component's first pixel
+ * (scipy.ndimage.label). */
+size_t wesup_cc_label_workspace_bytes(int B, int H, int W);
+int wesup_cc_label(const uint8_t* mask, int32_t* labels, int32_t* n_labels, int B, int H, int W, int connectivity, int value,
+                   void* ws, size_t ws_bytes, void* stream);
+/* evaluate.remove_small_regions (scripts/evaluate_glas.py:29-43): 8-connected foreground components smaller than min_size
+ * pixels are erased, then background components of the RESULT smaller than min_size are filled; out is {0, 1}, out != mask */
+size_t wesup_remove_small_regions_workspace_bytes(int B, int H, int W);
+int wesup_remove_small_regions(const uint8_t* mask, uint8_t* out, int B, int H, int W, int min_size, void* ws, size_t ws_bytes,
+                               void* stream);
+/* binary erosion (op 0), dilation (op 1), opening (op 2) with footprint uint8 [fh][fw] (device memory, fh * fw <= 1024) and
+ * scipy.ndimage's conventions: origin at size / 2, dilation with the mirrored footprint, border mode 'reflect' -- equal to
+ * grey_erosion / grey_dilation / grey_opening on {0, 1} input.  out != mask; ws only for the opening. */
+size_t wesup_binary_morph_workspace_bytes(int B, int H, int W, int op);
+int wesup_binary_morph(const uint8_t* mask, uint8_t* out, const uint8_t* footprint, int B, int H, int W, int fh, int fw, int op,
+                       void* ws, size_t ws_bytes, void* stream);
+/* table [B][nS + 1][nG + 1] = pixels per (label in S, label in G), zeroed here; status[b] |= 1 for a label outside the table;
+ * (nS + 1) * (nG + 1) <= 2^26 */
+int wesup_contingency(const int32_t* S, const int32_t* G, int32_t* table, int32_t* status, int B, int HW, int nS, int nG,
+                      void* stream);
+/* pixels sorted by label 0..L (L < 16384), ascending index inside a label: the pixels of label l are
+ * pix[b][start[b][l] .. start[b][l + 1]), start / bstart [B][L + 2], pix / bpix [B][HW].  bstart / bpix: the same lists of the
+ * labels >= 1 restricted to boundary pixels (a 4-neighbour outside the object or outside the image).  status[b] |= 1 for a
+ * label > L (negative labels are skipped). */
+size_t wesup_label_sort_workspace_bytes(int B, int H, int W, int L);
+int wesup_label_sort(const int32_t* labels, int32_t* start, int32_t* pix, int32_t* bstart, int32_t* bpix, int32_t* status, int B,
+                     int H, int W, int L, void* ws, size_t ws_bytes, void* stream);
+/* d2[i] = max over the pixels p of object pairs[i][0] of map X of min over the pixels q of object pairs[i][1] of map Y of
+ * |p - q|^2 (one image pair; H, W <= 32767): lists of X and label map + boundary lists of Y from wesup_label_sort.  0 when the
+ * first object lies inside the second, -1 for an object id outside [1, LX] x [1, LY].  The square root is the host's. */
+int wesup_directed_hausdorff_sq(const int32_t* pairs, const int32_t* start_x, const int32_t* pix_x, const int32_t* labels_y,
+                                const int32_t* bstart_y, const int32_t* bpix_y, int32_t* d2, int P, int H, int W, int LX, int LY,
+                                void* stream);
+
 /* ------------------------------------------------------------------ entries by the names of SURVEY.md 8(b)
  * One call per ATen op of the reference for a binding that replaces them one by one; each is a thin entry over the
  * kernels above (csrc/named.hip).  Matrices are row-major with the channel / feature index contiguous (NHWC pixels). */

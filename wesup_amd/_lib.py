@@ -110,6 +110,17 @@ _SIGS = {
     'wesup_sgd_step': (c_int, 'pppzffffip'),
     'wesup_seg_metrics_workspace_bytes': (c_size_t, 'i'),
     'wesup_seg_metrics': (c_int, 'pppiiipzp'),
+    # mask post-processing and challenge scoring (csrc/regions.hip)
+    'wesup_cc_label_workspace_bytes': (c_size_t, 'iii'),
+    'wesup_cc_label': (c_int, 'ppp' + 'iiiii' + 'pzp'),
+    'wesup_remove_small_regions_workspace_bytes': (c_size_t, 'iii'),
+    'wesup_remove_small_regions': (c_int, 'pp' + 'iiii' + 'pzp'),
+    'wesup_binary_morph_workspace_bytes': (c_size_t, 'iiii'),
+    'wesup_binary_morph': (c_int, 'ppp' + 'iiiiii' + 'pzp'),
+    'wesup_contingency': (c_int, 'pppp' + 'iiii' + 'p'),
+    'wesup_label_sort_workspace_bytes': (c_size_t, 'iiii'),
+    'wesup_label_sort': (c_int, 'pppppp' + 'iiii' + 'pzp'),
+    'wesup_directed_hausdorff_sq': (c_int, 'ppppppp' + 'iiiii' + 'p'),
     # entries by the names of SURVEY.md 8(b) (csrc/named.hip)
     'wesup_sp_stats': (c_int, 'ppiiiipppp'),
     'wesup_conv1x1_workspace_bytes': (c_size_t, 'iii'),

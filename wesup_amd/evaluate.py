@@ -5,7 +5,9 @@ SURVEY.md 8(f) row 4).
   python -m wesup_amd.evaluate PRED_ROOT --gt-root ~/data/GLAS_all        # post-process + score testA / testB
   python -m wesup_amd.evaluate --test -c CKPT --scales 0.6,0.55,0.5,0.45,0.4 --data-root ~/data/GLAS_all
 
-Evaluation-time code on the CPU, as in the reference (numpy / scipy; the training step does not touch it)."""
+Evaluation-time code on the CPU by default, as in the reference (numpy / scipy; the training step does not touch it).
+With ``device=`` / ``--gpu-scoring`` the post-processing and the scoring run on the GPU (csrc/regions.hip,
+utils/metrics_gpu.py): integer kernels and the same float64 formulas on the host, so the numbers are the same."""
 import argparse
 import csv
 from pathlib import Path
@@ -17,12 +19,18 @@ from .utils import metrics as M
 MIN_REGION = 2000        # pixels (scripts/evaluate_glas.py:33,39)
 
 
-def remove_small_regions(pred, min_size=MIN_REGION):
+def remove_small_regions(pred, min_size=MIN_REGION, device=None):
     """Post-processing of a binary prediction (scripts/evaluate_glas.py:29-43): connected foreground regions smaller
     than ``min_size`` pixels are erased, then connected background regions (holes) smaller than ``min_size`` are
     filled -- the second pass sees the result of the first.  8-connected components (skimage.measure.label's default
     for 2-D input).  The reference walks the regions one boolean mask at a time; here one ``bincount`` of the label map
-    gives every region's area and one table lookup rewrites the mask."""
+    gives every region's area and one table lookup rewrites the mask.  With ``device`` both passes run there
+    (ops.remove_small_regions); the result comes back as the same float64 array."""
+    if device is not None:
+        import torch
+        from . import ops
+        m = torch.tensor(np.asarray(pred) != 0).to(device).to(torch.uint8)
+        return ops.remove_small_regions(m, min_size).cpu().numpy().astype(np.float64)
     out = (np.asarray(pred) != 0).astype(np.float64)
     for value in (1.0, 0.0):                       # erase small foreground regions, then fill small holes
         regions = M.label(out == value)
@@ -39,15 +47,26 @@ def _read_mask(path):
     return a[..., 0] if a.ndim == 3 else a
 
 
-def score(predictions, gts, binarize_gt=False):
+def score(predictions, gts, binarize_gt=False, device=None):
     """Per-image rows and means of accuracy, Dice and the three object-level challenge metrics
     (scripts/evaluate_glas.py:46-69).  The reference hands the ground-truth OBJECT maps (ids 0..n) to ``accuracy`` and
     ``dice`` as they are -- for GlaS that compares a {0, 1} prediction with instance ids; kept by default so that the
-    numbers are the reference's, ``binarize_gt=True`` scores against ``gt > 0`` instead."""
+    numbers are the reference's, ``binarize_gt=True`` scores against ``gt > 0`` instead.  With ``device`` the three
+    object-level metrics of an image come from one pass on the GPU (metrics_gpu.challenge_scores)."""
     rows = []
     for pred, gt in zip(predictions, gts):
         gt = np.asarray(gt)
         flat = (gt > 0).astype(pred.dtype) if binarize_gt else gt
+        if device is not None:
+            import torch
+            from .utils import metrics_gpu
+            with torch.cuda.device(device):
+                obj = metrics_gpu.challenge_scores(torch.tensor(np.asarray(pred)).to(device),
+                                                   torch.tensor(np.asarray(gt)).to(device))
+            rows.append({'accuracy': float(M.accuracy(pred, flat)), 'dice': float(M.dice(pred, flat)),
+                         'detection_f1': obj['detection_f1'], 'object_dice': obj['object_dice'],
+                         'object_hausdorff': obj['object_hausdorff']})
+            continue
         rows.append({'accuracy': float(M.accuracy(pred, flat)),
                      'dice': float(M.dice(pred, flat)),
                      'detection_f1': float(M.detection_f1(pred, gt)),
@@ -57,7 +76,7 @@ def score(predictions, gts, binarize_gt=False):
     return rows, means
 
 
-def evaluate_split(pred_dir, gt_dir, new_pred_dir=None, csv_path=None, min_size=MIN_REGION, log=print):
+def evaluate_split(pred_dir, gt_dir, new_pred_dir=None, csv_path=None, min_size=MIN_REGION, log=print, device=None):
     """One test split: read predictions (0/255 images) and ground-truth object maps in sorted order, post-process,
     optionally save the new predictions and the per-image csv (columns of scripts/evaluate_glas.py:62-66)."""
     from PIL import Image
@@ -66,13 +85,13 @@ def evaluate_split(pred_dir, gt_dir, new_pred_dir=None, csv_path=None, min_size=
     gt_paths = sorted(p for e in exts for p in Path(gt_dir).glob(e))
     if len(pred_paths) != len(gt_paths):
         raise ValueError(f'{len(pred_paths)} predictions in {pred_dir} but {len(gt_paths)} masks in {gt_dir}')
-    predictions = [remove_small_regions(_read_mask(p) / 255, min_size) for p in pred_paths]
+    predictions = [remove_small_regions(_read_mask(p) / 255, min_size, device) for p in pred_paths]
     gts = [_read_mask(p) for p in gt_paths]
     if new_pred_dir is not None:
         Path(new_pred_dir).mkdir(parents=True, exist_ok=True)
         for pred, path in zip(predictions, pred_paths):
             Image.fromarray((pred * 255).astype('uint8')).save(Path(new_pred_dir) / path.name)
-    rows, means = score(predictions, gts)
+    rows, means = score(predictions, gts, device=device)
     for name, key in (('Accuracy', 'accuracy'), ('Dice', 'dice'), ('Detection F1', 'detection_f1'),
                       ('Object Dice', 'object_dice'), ('Object Hausdorff', 'object_hausdorff')):
         log(f'{name}: {means.get(key, float("nan"))}')
@@ -85,7 +104,7 @@ def evaluate_split(pred_dir, gt_dir, new_pred_dir=None, csv_path=None, min_size=
     return rows, means
 
 
-def evaluate_glas(pred_root, gt_root='~/data/GLAS_all', min_size=MIN_REGION, log=print):
+def evaluate_glas(pred_root, gt_root='~/data/GLAS_all', min_size=MIN_REGION, log=print, device=None):
     """scripts/evaluate_glas.py: testA and testB under ``pred_root`` against ``gt_root/<split>/masks``; post-processed
     predictions go to ``<pred_root>-new/<split>``, per-image metrics to ``pred_root/<split>.csv``."""
     pred_root, gt_root = Path(pred_root).expanduser(), Path(gt_root).expanduser()
@@ -96,7 +115,7 @@ def evaluate_glas(pred_root, gt_root='~/data/GLAS_all', min_size=MIN_REGION, log
             continue
         log(title)
         result[split] = evaluate_split(pred_root / split, gt_root / split / 'masks', new_root / split,
-                                       pred_root / f'{split}.csv', min_size, log)[1]
+                                       pred_root / f'{split}.csv', min_size, log, device)[1]
     return result
 
 
@@ -131,12 +150,13 @@ def main(argv=None):
     ap.add_argument('--scales', default='0.6,0.55,0.5,0.45,0.4')          # test_glas.py:48
     ap.add_argument('--data-root', default='~/data/GLAS_all')
     ap.add_argument('-d', '--device', default='cuda')
+    ap.add_argument('--gpu-scoring', action='store_true', help='post-process and score on --device instead of the CPU')
     a = ap.parse_args(argv)
     if a.test:
         size = [int(s) for s in a.input_size.split(',')] if a.input_size else None
         test(a.checkpoint, a.model, size, tuple(float(s) for s in a.scales.split(',')), a.device, a.data_root)
     else:
-        evaluate_glas(a.pred_root, a.gt_root, a.min_size)
+        evaluate_glas(a.pred_root, a.gt_root, a.min_size, device=a.device if a.gpu_scoring else None)
 
 
 if __name__ == '__main__':

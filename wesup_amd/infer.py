@@ -4,7 +4,9 @@ Same flow as the reference: resize (fixed ``input_size`` or every factor in ``sc
 SLIC here) -> model forward -> ``postprocess`` (round) -> nearest upsample to the original size; multi-scale
 predictions are averaged and rounded, then opened with the reference's 9x9 cross.  Everything stays on the GPU until
 the final mask; the opening runs on the CPU (scipy.ndimage instead of skimage.morphology, which is absent: parity
-of that step unpinned).  ``evaluate_predictions`` scores masks with the challenge metrics (utils/metrics.py)."""
+of that step unpinned) unless ``device_post`` / ``--device-post`` asks for the GPU opening (ops.binary_opening: scipy's result
+bit for bit).  ``evaluate_predictions`` scores masks with the challenge metrics (utils/metrics.py; ``device=``:
+utils/metrics_gpu.py)."""
 import argparse
 from math import ceil
 from pathlib import Path
@@ -39,8 +41,10 @@ def _cross(size=9):
     return selem
 
 
-def predict(trainer, dataset, input_size=None, scales=(0.5,), device='cuda'):
-    """Predict every image of ``dataset`` (raw items of utils.data.SegmentationDataset).  Returns a list of (H,W) masks."""
+def predict(trainer, dataset, input_size=None, scales=(0.5,), device='cuda', device_post=False):
+    """Predict every image of ``dataset`` (raw items of utils.data.SegmentationDataset).  Returns a list of (H,W) masks.
+    ``device_post``: the opening of a multi-scale prediction runs on the device too (ops.binary_opening: scipy's conventions
+    bit for bit) and the mask is copied to the host once, after it."""
     from scipy import ndimage
     predictions = []
     for i in range(len(dataset)):
@@ -65,6 +69,12 @@ def predict(trainer, dataset, input_size=None, scales=(0.5,), device='cuda'):
                 target_size = [ceil(s * scale) for s in orig_size]
                 multi.append(predict_single_image(trainer, *resized(target_size), orig_size))
             prediction = torch.cat(multi).mean(dim=0).round()
+        if device_post and input_size is None and len(scales) > 1:
+            from . import ops
+            prediction = prediction.squeeze()
+            opened = ops.binary_opening((prediction != 0).to(torch.uint8).contiguous(), _cross(9))
+            predictions.append(opened.to(prediction.dtype).cpu().numpy())
+            continue
         prediction = prediction.squeeze().cpu().numpy()
         if input_size is None and len(scales) > 1:
             prediction = ndimage.grey_opening(prediction, footprint=_cross(9))
@@ -80,12 +90,21 @@ def save_predictions(predictions, dataset, output_dir='predictions'):
         Image.fromarray(pred.astype('uint8') * 255).save(output_dir / f'{img_path.stem}.png')
 
 
-def evaluate_predictions(predictions, dataset):
-    """Challenge metrics of the predictions against the dataset's masks (scripts/evaluate_glas.py:29-69)."""
+def evaluate_predictions(predictions, dataset, device=None):
+    """Challenge metrics of the predictions against the dataset's masks (scripts/evaluate_glas.py:29-69); with ``device`` the
+    object-level metrics are computed there (utils/metrics_gpu.py: the same values)."""
     rows = []
     for i, pred in enumerate(predictions):
         gt = dataset[i][1].numpy()
         gt = (gt == 1).astype(np.uint8)
+        if device is not None:
+            from .utils import metrics_gpu
+            with torch.cuda.device(device):
+                obj = metrics_gpu.challenge_scores(torch.tensor(np.asarray(pred)).to(device),
+                                                   torch.from_numpy(gt).to(device))
+            rows.append({'accuracy': M.accuracy(pred, gt), 'dice': M.dice(pred, gt), 'detection_f1': obj['detection_f1'],
+                         'object_dice': obj['object_dice'], 'object_hausdorff': obj['object_hausdorff']})
+            continue
         rows.append({'accuracy': M.accuracy(pred, gt), 'dice': M.dice(pred, gt), 'detection_f1': M.detection_f1(pred, gt),
                      'object_dice': M.object_dice(pred, gt),
                      'object_hausdorff': M.object_hausdorff(pred, gt) if pred.any() and gt.any() else float('nan')})
@@ -93,10 +112,10 @@ def evaluate_predictions(predictions, dataset):
     return {k: float(np.nanmean([r[k] for r in rows])) for k in keys}, rows
 
 
-def infer(trainer, data_dir, output_dir=None, input_size=None, scales=(0.5,), device='cuda'):
+def infer(trainer, data_dir, output_dir=None, input_size=None, scales=(0.5,), device='cuda', device_post=False):
     trainer.model.eval()
     dataset = SegmentationDataset(data_dir, train=False)
-    predictions = predict(trainer, dataset, input_size=input_size, scales=scales, device=device)
+    predictions = predict(trainer, dataset, input_size=input_size, scales=scales, device=device, device_post=device_post)
     if output_dir is not None:
         save_predictions(predictions, dataset, output_dir)
     return predictions
@@ -111,6 +130,7 @@ def main(argv=None):
     ap.add_argument('--input-size', type=int, nargs=2)
     ap.add_argument('--scales', type=float, nargs='+', default=[0.5])
     ap.add_argument('--device', default='cuda')
+    ap.add_argument('--device-post', action='store_true', help='open multi-scale predictions on the device (default: scipy on the CPU)')
     a = ap.parse_args(argv)
     output_dir = a.output_dir
     if output_dir is None and a.checkpoint is not None:
@@ -118,7 +138,8 @@ def main(argv=None):
     trainer = initialize_trainer(a.model_type, device=a.device)
     if a.checkpoint is not None:
         trainer.load_checkpoint(a.checkpoint)
-    infer(trainer, a.data_dir, output_dir, input_size=a.input_size, scales=tuple(a.scales), device=a.device)
+    infer(trainer, a.data_dir, output_dir, input_size=a.input_size, scales=tuple(a.scales), device=a.device,
+          device_post=a.device_post)
 
 
 if __name__ == '__main__':

@@ -228,6 +228,16 @@ class BaseTrainer(ABC):
             ev = self.evaluate(pred_, target_)
         else:
             ev = {}
+        val_funcs = self.kwargs.get('val_metrics')
+        if phase != 'train' and has_gt and val_funcs:
+            # extra metrics of the validation phase only (the challenge metrics of utils/metrics_gpu.py under
+            # train.py --challenge-metrics): on the post-processed prediction, image by image
+            pred_, target_ = self.postprocess(pred.detach(), target)
+            extra = defaultdict(list)
+            for P, G in zip(pred_, target_):
+                for func in val_funcs:
+                    extra[func.__name__].append(func(P, G))
+            ev = {**ev, **{k: np.mean(v) for k, v in extra.items()}}
         self.tracker.step({**metrics, **ev})
 
     def _read_back(self, loss, metrics, seg):
@@ -329,7 +339,8 @@ class BaseTrainer(ABC):
             self.logger.info(self.tracker.log())
 
     def train(self, data_root, **kwargs):
-        """Start training process (models/base.py:252-333)."""
+        """Start training process (models/base.py:252-333).  ``val_metrics=[f, ...]``: metric functions f(P, G) evaluated in
+        the validation phase only, besides ``metrics`` (history.csv gains a ``val_<name>`` column each)."""
         self.kwargs = {**self.kwargs, **kwargs}
         self.optimizer, self.scheduler = self.get_default_optimizer()
         if self.reducer is not None and hasattr(self.optimizer, 'grad_scale'):

@@ -1302,3 +1302,136 @@ def seg_metrics(pred, mask, out=None):
     ws = workspace(nb, pred.device, 'seg')
     _lib.call('wesup_seg_metrics', _p(pred), _p(mask), _p(out), B, H * W, C, _p(ws), nb, _stream())
     return out
+
+
+# ---------------------------------------------------------------- mask post-processing and challenge scoring (csrc/regions.hip)
+MORPH_ERODE, MORPH_DILATE, MORPH_OPEN = 0, 1, 2
+CONTINGENCY_MAX_CELLS = 1 << 26      # above this a table is not allocated: the caller scores that image on the host
+LABEL_SORT_MAX_LABELS = 16384        # labels 0 .. L with L below this (the placement kernel's cursor table in LDS)
+
+
+def _mask3(mask, name='mask'):
+    """(H,W) or (B,H,W) uint8 -> (B,H,W), and whether a batch axis was added."""
+    _chk(mask, torch.uint8, name)
+    if mask.dim() not in (2, 3):
+        raise _lib.WesupHipError(f'{name}: expected (H,W) or (B,H,W), got {tuple(mask.shape)}')
+    return (mask.unsqueeze(0), True) if mask.dim() == 2 else (mask, False)
+
+
+def cc_label(mask, connectivity=8, value=1):
+    """Connected components of the pixels where ``(mask != 0) == value``: mask (H,W) / (B,H,W) uint8 -> (labels int32 of the
+    same shape, 0 elsewhere and 1..n in raster order of the first pixel like scipy.ndimage.label; n_labels (B,) int32)."""
+    m, squeeze = _mask3(mask)
+    B, H, W = m.shape
+    if connectivity not in (4, 8):
+        raise _lib.WesupHipError(f'cc_label: connectivity {connectivity} (4 or 8)')
+    labels = torch.empty(B, H, W, dtype=torch.int32, device=m.device)
+    n_labels = torch.empty(B, dtype=torch.int32, device=m.device)
+    nb = _lib.load().wesup_cc_label_workspace_bytes(B, H, W)
+    ws = workspace(nb, m.device, 'regions')
+    _lib.call('wesup_cc_label', _p(m), _p(labels), _p(n_labels), B, H, W, int(connectivity), int(bool(value)), _p(ws), nb,
+              _stream())
+    return (labels[0] if squeeze else labels), n_labels
+
+
+def remove_small_regions(mask, min_size=2000):
+    """Both passes of evaluate.remove_small_regions on the device: mask (H,W) / (B,H,W) uint8 -> {0,1} uint8 of the same shape."""
+    m, squeeze = _mask3(mask)
+    B, H, W = m.shape
+    out = torch.empty_like(m)
+    nb = _lib.load().wesup_remove_small_regions_workspace_bytes(B, H, W)
+    ws = workspace(nb, m.device, 'regions')
+    _lib.call('wesup_remove_small_regions', _p(m), _p(out), B, H, W, int(min_size), _p(ws), nb, _stream())
+    return out[0] if squeeze else out
+
+
+def binary_morph(mask, footprint, op=MORPH_OPEN):
+    """Erosion / dilation / opening of a {0,1} uint8 map (H,W) / (B,H,W) with scipy.ndimage's conventions (footprint origin at
+    size // 2, dilation with the mirrored footprint, border mode 'reflect'); footprint: a 2-D array or tensor, non-zero = set."""
+    m, squeeze = _mask3(mask)
+    B, H, W = m.shape
+    fp = torch.as_tensor(footprint)
+    if fp.dim() != 2 or fp.numel() == 0 or fp.numel() > 1024 or max(fp.shape) > 255:
+        raise _lib.WesupHipError(f'binary_morph: footprint {tuple(fp.shape)} (2-D, 1 .. 1024 cells)')
+    if op not in (MORPH_ERODE, MORPH_DILATE, MORPH_OPEN):
+        raise _lib.WesupHipError(f'binary_morph: op {op}')
+    fp = (fp != 0).to(torch.uint8).to(m.device).contiguous()
+    out = torch.empty_like(m)
+    nb = _lib.load().wesup_binary_morph_workspace_bytes(B, H, W, int(op))
+    ws = workspace(nb, m.device, 'regions')
+    _lib.call('wesup_binary_morph', _p(m), _p(out), _p(fp), B, H, W, fp.shape[0], fp.shape[1], int(op), _p(ws), nb, _stream())
+    return out[0] if squeeze else out
+
+
+def binary_opening(mask, footprint):
+    return binary_morph(mask, footprint, MORPH_OPEN)
+
+
+def contingency(S, G, nS, nG):
+    """Label maps S, G (H,W) / (B,H,W) int32 with labels in [0, nS] / [0, nG] -> (B, nS+1, nG+1) int32 pixel counts (the batch
+    axis only for batched input).  Raises when a label lies outside the table or the table would exceed
+    ``CONTINGENCY_MAX_CELLS`` (nothing is allocated then)."""
+    _chk(S, torch.int32, 'S'); _chk(G, torch.int32, 'G')
+    if S.shape != G.shape or S.dim() not in (2, 3):
+        raise _lib.WesupHipError(f'contingency: shapes {tuple(S.shape)} and {tuple(G.shape)}')
+    nS, nG = int(nS), int(nG)
+    if nS < 0 or nG < 0 or (nS + 1) * (nG + 1) > CONTINGENCY_MAX_CELLS:
+        raise _lib.WesupHipError(f'contingency: a table of {nS + 1} x {nG + 1} cells is not built on the device')
+    B = 1 if S.dim() == 2 else S.shape[0]
+    HW = S.shape[-1] * S.shape[-2]
+    table = torch.empty(B, nS + 1, nG + 1, dtype=torch.int32, device=S.device)
+    status = torch.empty(B, dtype=torch.int32, device=S.device)
+    _lib.call('wesup_contingency', _p(S), _p(G), _p(table), _p(status), B, HW, nS, nG, _stream())
+    return (table[0] if S.dim() == 2 else table), status
+
+
+class LabelLists:
+    """Per-label pixel lists of a label map (label_sort): ``pix[start[l]:start[l+1]]`` are the pixels of label l in ascending
+    order, ``bpix`` / ``bstart`` the boundary pixels of the labels >= 1."""
+    __slots__ = ('labels', 'L', 'start', 'pix', 'bstart', 'bpix', 'status')
+
+
+def label_sort(labels, L):
+    """labels (H,W) / (B,H,W) int32 in [0, L] -> LabelLists (tensors carry a batch axis only for batched input)."""
+    _chk(labels, torch.int32, 'labels')
+    if labels.dim() not in (2, 3):
+        raise _lib.WesupHipError(f'label_sort: expected (H,W) or (B,H,W), got {tuple(labels.shape)}')
+    L = int(L)
+    if L < 0 or L >= LABEL_SORT_MAX_LABELS:
+        raise _lib.WesupHipError(f'label_sort: {L} labels (below {LABEL_SORT_MAX_LABELS})')
+    single = labels.dim() == 2
+    B = 1 if single else labels.shape[0]
+    H, W = labels.shape[-2:]
+    dev = labels.device
+    out = LabelLists()
+    out.labels, out.L = labels, L
+    out.start = torch.empty(B, L + 2, dtype=torch.int32, device=dev)
+    out.bstart = torch.empty(B, L + 2, dtype=torch.int32, device=dev)
+    out.pix = torch.empty(B, H * W, dtype=torch.int32, device=dev)
+    out.bpix = torch.empty(B, H * W, dtype=torch.int32, device=dev)
+    out.status = torch.empty(B, dtype=torch.int32, device=dev)
+    nb = _lib.load().wesup_label_sort_workspace_bytes(B, H, W, L)
+    ws = workspace(nb, dev, 'regions')
+    _lib.call('wesup_label_sort', _p(labels), _p(out.start), _p(out.pix), _p(out.bstart), _p(out.bpix), _p(out.status), B, H, W,
+              L, _p(ws), nb, _stream())
+    if single:
+        for k in ('start', 'pix', 'bstart', 'bpix'):
+            setattr(out, k, getattr(out, k)[0])
+    return out
+
+
+def directed_hausdorff_sq(pairs, X, Y):
+    """pairs (P,2) int32 of (object of X, object of Y); X, Y: LabelLists of two (H,W) label maps -> (P,) int32 squared directed
+    Hausdorff distances max_{p in a} min_{q in b} |p - q|^2."""
+    _chk(pairs, torch.int32, 'pairs')
+    if pairs.dim() != 2 or pairs.shape[1] != 2:
+        raise _lib.WesupHipError(f'directed_hausdorff_sq: pairs {tuple(pairs.shape)}')
+    if X.labels.dim() != 2 or X.labels.shape != Y.labels.shape:
+        raise _lib.WesupHipError('directed_hausdorff_sq: two (H,W) label maps of one shape')
+    H, W = X.labels.shape
+    P = pairs.shape[0]
+    d2 = torch.empty(P, dtype=torch.int32, device=pairs.device)
+    if P:
+        _lib.call('wesup_directed_hausdorff_sq', _p(pairs), _p(X.start), _p(X.pix), _p(Y.labels), _p(Y.bstart), _p(Y.bpix),
+                  _p(d2), P, H, W, X.L, Y.L, _stream())
+    return d2

@@ -121,3 +121,27 @@ def make_batch(seed, B, H, W, g, frac=0.2, tie_every=0):
     pts = np.stack([point_mask(seed * 1000 + b, labs[b], frac, 2, tie_every) for b in range(B)])
     pix = np.stack([pixel_mask(seed * 1000 + b, H, W) for b in range(B)])
     return imgs, labs, pts, pix
+
+
+def gland_map(seed, H=522, W=775, n=14, rmin=25, rmax=70):
+    """A binary map of ``n`` random ellipses with semi-axes of ``rmin`` .. ``rmax`` pixels (overlapping ones merge): the
+    stand-in for a GlaS gland mask that the scoring tests and tools/score_micro.py use."""
+    rs = np.random.RandomState(seed)
+    yy, xx = np.mgrid[0:H, 0:W]
+    m = np.zeros((H, W), dtype=np.uint8)
+    for _ in range(n):
+        cy, cx = rs.randint(0, H), rs.randint(0, W)
+        ry, rx = rs.randint(rmin, rmax + 1), rs.randint(rmin, rmax + 1)
+        m[((yy - cy) / ry) ** 2 + ((xx - cx) / rx) ** 2 <= 1.0] = 1
+    return m
+
+
+def gland_pair(seed, H=522, W=775, n=14, shift=7, square=60):
+    """(prediction, ground truth): a gland map and its copy rolled by ``shift`` pixels along both axes, with one
+    ``square`` x ``square`` block pasted into the prediction (an object that may overlap nothing)."""
+    G = gland_map(seed, H, W, n)
+    S = np.roll(G, shift, axis=(0, 1)).copy()
+    rs = np.random.RandomState(seed + 7919)
+    y, x = rs.randint(0, H - square), rs.randint(0, W - square)
+    S[y:y + square, x:x + square] = 1
+    return S, G

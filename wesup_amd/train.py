@@ -1,6 +1,6 @@
 """Training module (mirror of the reference's train.py:14-32; `fire` is replaced by argparse).
 
-  python -m wesup_amd.train synthetic:480:480:24:16 --epochs 1 --batch_size 4 [--smoke]
+  python -m wesup_amd.train synthetic:480:480:24:16 --epochs 1 --batch_size 4 [--smoke] [--challenge-metrics]
 """
 import argparse
 import logging
@@ -30,11 +30,16 @@ def fit(dataset_path, model='wesup', **kwargs):
         if not dist.is_initialized():
             torch.cuda.set_device(local_rank)
             dist.init_process_group(kwargs.pop('dist_backend', 'nccl'))
+    extra = {}
+    if kwargs.pop('challenge_metrics', False):
+        # the three object-level GlaS metrics on the validation images, scored on the GPU (utils/metrics_gpu.py)
+        from .utils import metrics_gpu
+        extra['val_metrics'] = [metrics_gpu.detection_f1, metrics_gpu.object_dice, metrics_gpu.object_hausdorff]
     trainer = initialize_trainer(model, logger=logger, **kwargs)
     if world > 1:
         trainer.enable_data_parallel()
     try:
-        trainer.train(dataset_path, metrics=[accuracy, dice], **kwargs)
+        trainer.train(dataset_path, metrics=[accuracy, dice], **extra, **kwargs)
     finally:
         if kwargs.get('smoke') and trainer.rank == 0 and trainer.record_dir is not None:
             rmtree(trainer.record_dir, ignore_errors=True)

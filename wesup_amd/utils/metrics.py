@@ -4,6 +4,8 @@
 trainer's hot path does not call them per image: it reads the sums produced by
 the ``wesup_seg_metrics`` kernel and applies the same formulas
 (``accuracy_from_sums``/``dice_from_sums``) -- one host sync per step instead of four."""
+import math
+
 import numpy as np
 import torch
 
@@ -75,7 +77,12 @@ def detection_f1(S, G, overlap_threshold=0.5, epsilon=1e-7):
     """F1 of object detection: a segmented object is a true positive when it covers more than ``overlap_threshold``
     of the ground-truth object it overlaps most (utils/metrics.py:49-109)."""
     S, G = label(_to_numpy(S)), label(_to_numpy(G))
-    C, nS, nG = _contingency(S, G)
+    return detection_f1_from_table(_contingency(S, G)[0], overlap_threshold, epsilon)
+
+
+def detection_f1_from_table(C, overlap_threshold=0.5, epsilon=1e-7):
+    """``detection_f1`` from the contingency table of the two labelled maps (rows: segmented objects, row / column 0: background)."""
+    nS, nG = C.shape[0] - 1, C.shape[1] - 1
     if nS == 0 and nG == 0:
         return 1
     if nS == 0 or nG == 0:
@@ -109,7 +116,12 @@ def _weighted_pair_dice(C, epsilon=1e-7):
 def object_dice(S, G):
     """Object-level Dice (utils/metrics.py:139-196)."""
     S, G = label(_to_numpy(S)), label(_to_numpy(G))
-    C, nS, nG = _contingency(S, G)
+    return object_dice_from_table(_contingency(S, G)[0])
+
+
+def object_dice_from_table(C):
+    """``object_dice`` from the contingency table of the two labelled maps."""
+    nS, nG = C.shape[0] - 1, C.shape[1] - 1
     if nS == 0 and nG == 0:
         return 1
     if nS == 0 or nG == 0:
@@ -129,21 +141,59 @@ def hausdorff(S, G):
     return max(directed_hausdorff(Sc, Gc)[0], directed_hausdorff(Gc, Sc)[0])
 
 
-def _weighted_pair_hausdorff(A, B, C):
-    """sum over the objects a of A of (area_a / total) * Hausdorff(a, partner in B), or to the nearest object of B
-    when a overlaps none (utils/metrics.py:247-261)."""
+def hausdorff_from_sq(d2_ab, d2_ba):
+    """Symmetric Hausdorff distance of two non-empty pixel sets from the two SQUARED directed distances (integers): the square
+    roots are taken in float64, as scipy.spatial.distance.directed_hausdorff takes them."""
+    return max(math.sqrt(d2_ab), math.sqrt(d2_ba))
+
+
+def _weighted_pair_hausdorff_from(C, dist):
+    """sum over the rows a >= 1 of C of (area_a / total) * dist(a, partner of a), or the smallest dist(a, b) over all columns
+    b >= 1 when a overlaps none (utils/metrics.py:247-261).  ``dist(a, b)``: Hausdorff distance of row object a and column
+    object b."""
     partner = _partner(C)
     area = C.sum(1)
     total = area[1:].sum()
     nB = C.shape[1] - 1
     acc = 0.0
     for a in range(1, C.shape[0]):
-        Ai = A == a
         if partner[a] > 0:
-            acc += area[a] / total * hausdorff(Ai, B == partner[a])
+            acc += area[a] / total * dist(a, partner[a])
         elif nB > 0:
-            acc += area[a] / total * min(hausdorff(Ai, B == b) for b in range(1, nB + 1))
+            acc += area[a] / total * min(dist(a, b) for b in range(1, nB + 1))
     return acc
+
+
+def _weighted_pair_hausdorff(A, B, C):
+    """``_weighted_pair_hausdorff_from`` on the label maps themselves: one boolean mask per object, scipy's distance."""
+    masks = {}
+
+    def dist(a, b):
+        if a not in masks:
+            masks[a] = A == a
+        return hausdorff(masks[a], B == b)
+    return _weighted_pair_hausdorff_from(C, dist)
+
+
+def hausdorff_pairs(C):
+    """The (row object, column object) pairs whose Hausdorff distance ``object_hausdorff_from_table`` asks for, both directions
+    of the table together, sorted: every object with its partner, an object that overlaps nothing with every object of the
+    other map."""
+    pairs = set()
+    for T, swap in ((C, False), (C.T, True)):
+        partner = _partner(T)
+        for a in range(1, T.shape[0]):
+            others = [int(partner[a])] if partner[a] > 0 else range(1, T.shape[1])
+            pairs.update((b, a) if swap else (a, b) for b in others)
+    return sorted(pairs)
+
+
+def object_hausdorff_from_table(C, d2_sg, d2_gs):
+    """``object_hausdorff`` from the contingency table and the squared directed distances of ``hausdorff_pairs(C)``:
+    ``d2_sg[(s, g)]`` from segmented object s to ground-truth object g, ``d2_gs[(s, g)]`` the other way."""
+    def dist_sg(s, g):
+        return hausdorff_from_sq(d2_sg[(int(s), int(g))], d2_gs[(int(s), int(g))])
+    return (_weighted_pair_hausdorff_from(C, dist_sg) + _weighted_pair_hausdorff_from(C.T, lambda g, s: dist_sg(s, g))) / 2
 
 
 def object_hausdorff(S, G):
