@@ -196,6 +196,37 @@ def _lib_mod():
     return _lib
 
 
+def _composite(ops, entry, B, H, W, k_in, k_out, m, *args):
+    """A C composite of the Winograd-domain conv (input transform, products, output transform issued from C: the form a C
+    caller uses) called directly: args are the entry's arguments up to its workspace, tensors as themselves.  The ops
+    wrappers issue the same passes one by one from Python and must leave the same bits."""
+    lib = _lib_mod()
+    nb = lib.load().wesup_conv3x3_winograd_workspace_bytes(B, H, W, k_in, k_out, m)
+    assert nb > 0
+    ws = ops.workspace(nb, dev(), 'composite')
+    lib.call(entry, *[ops._p(a) if a is None or isinstance(a, torch.Tensor) else a for a in args], ops._p(ws), nb, ops._stream())
+
+
+class _Tags:
+    """A timer like engine.KernelTimer that records the class tags in the order the passes are bracketed."""
+    def __init__(self):
+        self.tags = []
+
+    def begin(self, tag):
+        self.tags.append(tag)
+        return tag
+
+    def end(self, tok, work):
+        assert tok == self.tags[-1] and work > 0      # the brackets do not nest; every pass states its work
+
+
+def _wino_tags(ops, k_in, k_out, tiles, v_pre=False):
+    """The timer classes of a dgrad-like pass per route: one kernel for products + output transform, or three passes."""
+    one_kernel = ops.winograd_fused_supported(k_in, k_out, 4, tiles) == 2
+    tags = ['winograd_transform', 'winograd_gemm'] + ([] if one_kernel else ['winograd_transform'])
+    return tags[1:] if v_pre else tags
+
+
 def wino_bar(m, e_direct):
     """Error bar of a Winograd-domain conv pass against fp64, as a fraction of the tensor's maximum."""
     return max(TOL / 10, 4 * e_direct) if m == 2 else 2e-5
@@ -231,11 +262,20 @@ def test_conv3x3_fwd_winograd(ops, B, H, W, Cin, Cout, relu_in, m):
     e_w, e_0 = rel_err(nchw(y), ref), rel_err(nchw(y0), ref)
     assert e_w < wino_bar(m, e_0), (e_w, e_0)
     assert torch.equal(yr, torch.relu(y))
+    # the C composite (the same passes issued from C) leaves the same bits in every output
+    yc, yrc, vc = torch.empty_like(y), torch.empty_like(y), torch.empty_like(v_keep)
+    _composite(ops, 'wesup_conv3x3_fwd_winograd', B, H, W, Cin, Cout, m, xg, uf, b.to(d), yc, yrc, None, 0, vc, B, H, W, Cin, Cout,
+               int(relu_in), m)
+    assert torch.equal(yc, y) and torch.equal(yrc, yr) and torch.equal(vc, v_keep)
     if H >= 2 and W >= 2:      # the pooled third output = the max-pool kernel on y, bit for bit (odd borders: floor mode)
         for pool_relu in (False, True):
             yp = torch.full((B, H // 2, W // 2, Cout), 7.0, device=d)
             y3 = torch.empty_like(y)
             ops.conv3x3_fwd_winograd(xg, uf, b.to(d), relu_in, out=y3, out_pool=yp, pool_relu=pool_relu, m=m)
+            ypc, y3c = torch.full_like(yp, 7.0), torch.empty_like(y)
+            _composite(ops, 'wesup_conv3x3_fwd_winograd', B, H, W, Cin, Cout, m, xg, uf, b.to(d), y3c, None, ypc, int(pool_relu), None,
+                       B, H, W, Cin, Cout, int(relu_in), m)
+            assert torch.equal(y3c, y3) and torch.equal(ypc, yp)
             if _lib_mod().load().wesup_winograd_fused_supported(Cin, Cout, m):
                 # without a second (ReLU'd) output, short products take the one-kernel route: the same sums in another order
                 assert float((y3 - y).abs().max()) < 4e-6 * float(y.abs().max()) * 25
@@ -338,6 +378,9 @@ def test_conv3x3_dgrad_winograd(ops, B, H, W, Cin, Cout, m):
     out = base.clone().to(d)
     mask = nhwc(x.detach()).to(d)
     ops.conv3x3_dgrad_winograd(nhwc(dy).to(d), ud, mask_src=mask, out=out, accumulate=True, m=m)
+    outc = base.clone().to(d)                              # the C composite: the same bits
+    _composite(ops, 'wesup_conv3x3_dgrad_winograd', B, H, W, Cout, Cin, m, nhwc(dy).to(d), ud, mask, outc, B, H, W, Cin, Cout, 1, m)
+    assert torch.equal(outc, out)
     out0 = base.clone().to(d)
     ops.conv3x3_dgrad(nhwc(dy).to(d), wd, Cin, mask_src=mask, out=out0, accumulate=True)
     e_w, e_0 = rel_err(nchw(out.cpu() - base), ref), rel_err(nchw(out0.cpu() - base), ref)
@@ -347,6 +390,9 @@ def test_conv3x3_dgrad_winograd(ops, B, H, W, Cin, Cout, m):
     F.conv2d(x2.double(), w.double(), None, padding=1).backward(dy.double())
     out2 = ops.conv3x3_dgrad_winograd(nhwc(dy).to(d), ud, m=m)
     assert rel_err(nchw(out2), x2.grad) < wino_bar(m, TOL / 40)
+    out2c = torch.empty_like(out2)
+    _composite(ops, 'wesup_conv3x3_dgrad_winograd', B, H, W, Cout, Cin, m, nhwc(dy).to(d), ud, None, out2c, B, H, W, Cin, Cout, 0, m)
+    assert torch.equal(out2c, out2)
 
 
 @pytest.mark.parametrize('B,H,W,K,N', [(2, 24, 16, 64, 64), (1, 37, 41, 64, 128), (3, 9, 8, 128, 64), (1, 2, 2, 64, 64),
@@ -432,13 +478,15 @@ def test_conv3x3_dgrad_winograd_through_the_maxpool_backward(ops, B, Hu, Wu, Cin
     out = F.conv2d(F.max_pool2d(F.relu(yp), 2), w.double(), None, padding=1)
     out.backward(nchw(dy.cpu()).double())
     assert rel_err(nchw(fused.cpu() - base), yp.grad) < 2e-5
-    # the timed form (three bracketed passes) is the same computation
-    class _T:
-        def begin(self, tag): return tag
-        def end(self, tok, work): pass
+    # the C composite (the passes issued from C) is the same computation as the passes of the wrapper ...
     again = base.clone().to(d)
-    ops.conv3x3_dgrad_winograd_unpool(dy, ud, ypre_g, again, timer=_T())
+    _composite(ops, 'wesup_conv3x3_dgrad_winograd_unpool', B, H, W, Cout, Cin, 4, dy, ud, ypre_g, again, B, H, W, Hu, Wu, Cin, Cout, 4)
     assert torch.equal(again, fused)
+    # ... which a timer sees bracketed as classes of their own, per route
+    timed, rec = base.clone().to(d), _Tags()
+    ops.conv3x3_dgrad_winograd_unpool(dy, ud, ypre_g, timed, timer=rec)
+    assert torch.equal(timed, fused)
+    assert rec.tags == _wino_tags(ops, Cout, Cin, ops.winograd_tiles(B, H, W, 4))
 
 
 @pytest.mark.parametrize('B,Hd,Wd,g,Cin,Cout,pooled', [(2, 32, 32, 4, 64, 64, False), (1, 44, 36, 5, 64, 128, True), (2, 24, 40, 4, 64, 64, True),
@@ -473,13 +521,21 @@ def test_conv3x3_dgrad_winograd_with_the_side_gradient_gathered_in_the_epilogue(
     same_route = ops.winograd_fused_supported(Cout, Cin, 4, ops.winograd_tiles(B, H, W, 4)) == 2
     assert float((got - want).abs().max()) <= (2e-7 if same_route else 4e-6) * scale
     assert float((want - base).abs().max()) > 0.05 * scale         # the conv part is not negligible beside the gathered part
-    class _T:
-        def begin(self, tag): return tag
-        def end(self, tok, work): pass
+    # the C composite (the passes issued from C) is the same computation as the passes of the wrapper ...
     again = torch.empty_like(got)
-    ops.conv3x3_dgrad_winograd_gather(dy, ud, side, m.new_row, m.area_new, out=again, mask_src=None if pooled else ypre,
-                                      unpool_src=ypre if pooled else None, timer=_T())
+    _composite(ops, 'wesup_conv3x3_dgrad_winograd_gather', B, H, W, Cout, Cin, 4, dy, ud, None if pooled else ypre,
+               ypre if pooled else None, again, side, m.new_row, m.area_new, Kmax, B, H, W, Hd if pooled else 0, Wd if pooled else 0,
+               Cin, Cout)
     assert torch.equal(again, got)
+    # ... which a timer sees bracketed as classes of their own: always the one-kernel route; no transform when dy's is handed in
+    timed, rec = torch.empty_like(got), _Tags()
+    ops.conv3x3_dgrad_winograd_gather(dy, ud, side, m.new_row, m.area_new, out=timed, mask_src=None if pooled else ypre,
+                                      unpool_src=ypre if pooled else None, timer=rec)
+    assert torch.equal(timed, got) and rec.tags == ['winograd_transform', 'winograd_gemm']
+    timed, rec = torch.empty_like(got), _Tags()
+    ops.conv3x3_dgrad_winograd_gather(dy, ud, side, m.new_row, m.area_new, out=timed, mask_src=None if pooled else ypre,
+                                      unpool_src=ypre if pooled else None, timer=rec, v_pre=ops.winograd_input_transform(dy, m=4))
+    assert torch.equal(timed, got) and rec.tags == ['winograd_gemm']
     # the side rows divided by their areas beforehand (scale_rows_by_area; area_new = None): the same coefficient applied once
     # per row instead of once per pixel -- one rounding more per element (the product is no longer fused into the sum)
     scaled = ops.scale_rows_by_area(side.clone(), m.area_new)
@@ -527,6 +583,9 @@ def test_winograd_dual_transform_and_weight_gradient_from_it(ops, B, H, W, Cin, 
     ops.conv3x3_dgrad_winograd_unpool(dy, ud, ypre, a)
     ops.conv3x3_dgrad_winograd_unpool(dy, ud, ypre, b_, v_pre=V)
     assert torch.equal(a, b_)
+    timed, rec = base.clone(), _Tags()          # a timer sees no input transform then
+    ops.conv3x3_dgrad_winograd_unpool(dy, ud, ypre, timed, v_pre=V, timer=rec)
+    assert torch.equal(a, timed) and rec.tags == _wino_tags(ops, Cout, Cin, T, v_pre=True)
 
 
 def _pool_codes(y):

@@ -478,106 +478,104 @@ def winograd_filter_grad(slabs, dw=None, db=None, m=2):
     return dw, db
 
 
-def _winograd_conv(inp, u, bias, mask_src, out, out_relu, v_keep, relu_in, accumulate, ws_tag, timer, out_pool=None,
-                   pool_relu=False, m=2, relu_bits_out=None, pool_code_out=None, mask_bits=None, v_ready=False,
-                   after_transform=None):
-    """The three passes of a Winograd-domain conv (input transform, P batched NT GEMMs, output transform + epilogue) -- or, for
-    the short products (K <= 256 channels), the input transform and ONE kernel for products + output transform.
-    timer (optional, engine.KernelTimer-like): the GEMM and the transforms are bracketed as classes of their own.
-    after_transform: called once, when the input transform has been queued (the engine queues the previous layer's side
-    branch there)."""
+class _NullTimer:
+    def begin(self, tag): return None
+    def end(self, tok, work): pass
+
+
+_NULL_TIMER = _NullTimer()
+
+
+def _winograd_conv(inp, u, m, ws_tag, timer, V=None, v_ready=False, relu_in=False, relu_bits_out=None, after_transform=None,
+                   bias=None, mask_src=None, mask_bits=None, out=None, out_relu=None, out_pool=None, pool_relu=False,
+                   pool_code_out=None, accumulate=False, unpool=None, gather=None):
+    """Every Winograd-domain conv with an epilogue: inp (B,H,W,Cin) x u (P,Cout,Cin) -> the epilogue's destination.  The one
+    place that decides the route, splits the workspace, brackets the timer classes and reads DIAG.
+    Stage 1, the operand: V (P,tiles,Cin) is handed in transformed (v_ready) or produced by the input transform, into V when
+    given (the forward's v_keep), else into the head of the workspace; relu_bits_out: the sign bits of inp ride along.
+    after_transform is then called once (the engine queues the previous layer's side branch there).
+    Stage 2, the product: ONE kernel for the products and the output transform (short products on a grid that fills the chip),
+    or the P batched NT GEMMs into the tail of the workspace and the output transform.
+    unpool = (src, code, dst): the max-pool backward as the epilogue, into dst (B,Hu,Wu,Cout), decided by src or by the codes;
+    gather = (side, new_row, area_new): the destination's old content replaced by the gathered side gradient.  The compact
+    forms (mask_bits, pool_code_out, codes) and the gather exist on the one-kernel route only.
+    timer (engine.KernelTimer-like, optional): the transforms and the product are bracketed as classes of their own."""
     B, H, W, Cin = inp.shape
     Cout = u.shape[1]
     lib = _lib.load()
     nb = lib.wesup_conv3x3_winograd_workspace_bytes(B, H, W, Cin, Cout, m)
     if not nb:
         raise _lib.WesupHipError(f'winograd conv: unsupported shape {(B, H, W, Cin, Cout, m)}')
+    if timer is None:
+        timer = _NULL_TIMER
     T, P = winograd_tiles(B, H, W, m), winograd_positions(m)
-    ws = workspace(nb, inp.device, ws_tag)
-    v_bytes = (P * T * Cin * 4 + 255) // 256 * 256
-    V = v_keep if v_keep is not None else ws[:v_bytes]
-    Mt = ws[v_bytes:]
-    n_io = 1 + (out_relu is not None) + (mask_src is not None) + bool(accumulate)
-
-    hook = [after_transform]      # called once, when the (first) input transform has been queued
-
-    def t_in(b0, nb_, st):
-        if not v_ready and 'tin' not in DIAG:
-            _t_in(b0, nb_, st)
-        if hook[0] is not None:
-            hook[0]()
-            hook[0] = None
-
-    def _t_in(b0, nb_, st):
-        tok = timer.begin('winograd_transform') if timer else None
-        t0 = winograd_tiles(b0, H, W, m)
-        if relu_bits_out is not None:      # the sign bits of the input ride along (the ReLU mask of the layer below, for its backward)
-            _lib.call('wesup_winograd_input_transform_bits', _p(inp[b0:b0 + nb_]), ctypes.c_void_p(V.data_ptr() + 4 * t0 * Cin),
-                      T * Cin, _p(relu_bits_out[b0:b0 + nb_]), nb_, H, W, Cin, int(relu_in), st)
-        else:
-            _lib.call('wesup_winograd_input_transform', _p(inp[b0:b0 + nb_]), ctypes.c_void_p(V.data_ptr() + 4 * t0 * Cin), T * Cin,
-                      nb_, H, W, Cin, int(relu_in), m, st)
-        if timer:       # bytes: read x, write the P / m^2-fold expansion (4x for m = 2, 2.25x for m = 4)
-            timer.end(tok, 4.0 * (nb_ * H * W + P * winograd_tiles(nb_, H, W, m)) * Cin)
-
-    def gemm(b0, nb_, st):
-        tok = timer.begin('winograd_gemm') if timer else None
-        t0, tn = winograd_tiles(b0, H, W, m), winograd_tiles(nb_, H, W, m)
-        _lib.call('wesup_gemm_nt_batched', ctypes.c_void_p(V.data_ptr() + 4 * t0 * Cin), Cin, T * Cin, _p(u), Cin, Cout * Cin,
-                  ctypes.c_void_p(Mt.data_ptr() + 4 * t0 * Cout), Cout, T * Cout, P, tn, Cout, Cin, st)
-        if timer:
-            timer.end(tok, 2.0 * P * tn * Cin * Cout)
-
-    def t_out(b0, nb_, st):
-        if 'tout' in DIAG:
-            return
-        tok = timer.begin('winograd_transform') if timer else None
-        t0 = winograd_tiles(b0, H, W, m)
-        sl = slice(b0, b0 + nb_)
-        _lib.call('wesup_winograd_output_transform', ctypes.c_void_p(Mt.data_ptr() + 4 * t0 * Cout), T * Cout, _p(bias),
-                  _p(None if mask_src is None else mask_src[sl]), _p(out[sl]), _p(None if out_relu is None else out_relu[sl]),
-                  _p(None if out_pool is None else out_pool[sl]), int(pool_relu), nb_, H, W, Cout, int(accumulate), m, st)
-        if timer:
-            timer.end(tok, 4.0 * (P * winograd_tiles(nb_, H, W, m) + (n_io + (0.25 if out_pool is not None else 0)) * nb_ * H * W) * Cout)
-
-    # (the compact forms -- sign bits in, pooling codes out -- exist on the one-kernel route only: a caller that hands them over
-    #  has chosen it; otherwise the size of the grid decides, wesup_winograd_fused_route)
-    compact = mask_bits is not None or pool_code_out is not None
-    fused = 0 if out_relu is not None else (lib.wesup_winograd_fused_supported(Cin, Cout, m) if compact
+    us, ucode, udst = unpool or (None, None, None)
+    Hu, Wu = udst.shape[1:3] if unpool else (0, 0)
+    side, new_row, area_new = gather or (None, None, None)
+    # the route: a caller that hands over a compact form or the gather has chosen the one-kernel route; otherwise the size of
+    # the grid decides (wesup_winograd_fused_route).  Level 1 of that route has the forward's epilogues only.
+    compact = mask_bits is not None or pool_code_out is not None or ucode is not None
+    chosen = compact or gather is not None
+    fused = 0 if out_relu is not None else (lib.wesup_winograd_fused_supported(Cin, Cout, m) if chosen
                                             else lib.wesup_winograd_fused_route(Cin, Cout, m, T))
-    masked = mask_src is not None or mask_bits is not None
-    if relu_bits_out is not None:
-        assert m == 4 and relu_bits_out.dtype == torch.uint8 and relu_bits_out.shape == (B, H, W, Cin // 4) and relu_bits_out.is_contiguous()
-    if mask_bits is not None or pool_code_out is not None:       # compact mask in / pooling decisions out: one-kernel route only
-        if not (fused == 2 or (fused == 1 and not masked and not accumulate)):
-            raise _lib.WesupHipError(f'winograd conv {Cin} -> {Cout}: mask_bits / pool_code_out need the one-kernel product route')
-        assert mask_bits is None or (mask_bits.dtype == torch.uint8 and mask_bits.shape == (B, H, W, Cout // 4) and mask_bits.is_contiguous())
-        assert pool_code_out is None or (out_pool is not None and pool_code_out.dtype == torch.int16
-                                         and pool_code_out.shape == (B, H // 2, W // 2, Cout // 4) and pool_code_out.is_contiguous())
-    if fused == 2 or (fused == 1 and not masked and not accumulate):
-        # short products (64 ... 256 channels): the batched products and the output transform in one kernel
-        st = _stream()
-        for b0, nb_ in ((0, B),):
-            t_in(b0, nb_, st)
-            tok = timer.begin('winograd_gemm') if timer else None
-            t0, tn = winograd_tiles(b0, H, W, m), winograd_tiles(nb_, H, W, m)
-            sl = slice(b0, b0 + nb_)
-            if mask_bits is not None or pool_code_out is not None:
-                _lib.call('wesup_winograd_gemm_output_transform_ex', ctypes.c_void_p(V.data_ptr() + 4 * t0 * Cin), T * Cin, _p(u),
-                          _p(bias), _p(None if mask_src is None else mask_src[sl]), _p(None if mask_bits is None else mask_bits[sl]),
-                          _p(out[sl]), _p(None if out_pool is None else out_pool[sl]), int(pool_relu),
-                          _p(None if pool_code_out is None else pool_code_out[sl]), None, None, None, 0, 0, None, None, None, 0,
-                          nb_, H, W, Cin, Cout, int(accumulate), st)
-            else:
-                _lib.call('wesup_winograd_gemm_output_transform', ctypes.c_void_p(V.data_ptr() + 4 * t0 * Cin), T * Cin, _p(u), _p(bias),
-                          _p(None if mask_src is None else mask_src[sl]), _p(out[sl]), _p(None if out_pool is None else out_pool[sl]),
-                          int(pool_relu), None, None, 0, 0, nb_, H, W, Cin, Cout, int(accumulate), st)
-            if timer:
-                timer.end(tok, 2.0 * P * tn * Cin * Cout)
-        return out
+    backward = mask_src is not None or mask_bits is not None or accumulate or unpool is not None or gather is not None
+    one_kernel = fused == 2 or (fused == 1 and not backward)
+    if chosen and not one_kernel:
+        raise _lib.WesupHipError(f'winograd conv {Cin} -> {Cout}: compact masks / pooling codes / the gathered side gradient '
+                                 'need the one-kernel product route')
+    # the workspace: [V: P T Cin][Mt: P T Cout]; a finished operand on the one-kernel route needs neither part
+    if not (v_ready and one_kernel):
+        ws = workspace(nb, inp.device, ws_tag)
+        if V is None:
+            V = ws
     st = _stream()
-    t_in(0, B, st); gemm(0, B, st); t_out(0, B, st)
-    return out
+
+    # stage 1: the operand
+    if not v_ready and 'tin' not in DIAG:
+        tok = timer.begin('winograd_transform')
+        if relu_bits_out is not None:      # the sign bits of the input ride along (the ReLU mask of the layer below, for its backward)
+            _lib.call('wesup_winograd_input_transform_bits', _p(inp), _p(V), 0, _p(relu_bits_out), B, H, W, Cin, int(relu_in), st)
+        else:
+            _lib.call('wesup_winograd_input_transform', _p(inp), _p(V), 0, B, H, W, Cin, int(relu_in), m, st)
+        # bytes: read x, write the P / m^2-fold expansion (4x for m = 2, 2.25x for m = 4)
+        timer.end(tok, 4.0 * (B * H * W + P * T) * Cin)
+    if after_transform is not None:
+        after_transform()
+
+    # stage 2: the product
+    tok = timer.begin('winograd_gemm')
+    if one_kernel:
+        # (three entries to one launcher, csrc/wino_fused.hip: _ex takes every option, the other two are its older subsets)
+        if compact or (unpool is not None and v_ready and gather is None):
+            pooled = unpool is not None
+            _lib.call('wesup_winograd_gemm_output_transform_ex', _p(V), 0, _p(u), _p(bias), _p(mask_src), _p(mask_bits),
+                      _p(None if pooled else out), _p(out_pool), int(pool_relu), _p(pool_code_out), _p(us), _p(ucode), _p(udst),
+                      Hu, Wu, _p(side), _p(new_row), _p(area_new), side.shape[1] if gather else 0, B, H, W, Cin, Cout,
+                      int(accumulate), st)
+        elif gather is not None:
+            _lib.call('wesup_winograd_gemm_output_transform_gather', _p(V), 0, _p(u), _p(mask_src), _p(udst if unpool else out),
+                      _p(us), Hu, Wu, _p(side), _p(new_row), _p(area_new), side.shape[1], B, H, W, Cin, Cout, st)
+        else:
+            _lib.call('wesup_winograd_gemm_output_transform', _p(V), 0, _p(u), _p(bias), _p(mask_src), _p(out), _p(out_pool),
+                      int(pool_relu), _p(us), _p(udst), Hu, Wu, B, H, W, Cin, Cout, int(accumulate), st)
+        timer.end(tok, 2.0 * P * T * Cin * Cout)
+        return
+    Mt = ws[(P * T * Cin * 4 + 255) // 256 * 256:]
+    _lib.call('wesup_gemm_nt_batched', _p(V), Cin, T * Cin, _p(u), Cin, Cout * Cin, _p(Mt), Cout, T * Cout, P, T, Cout, Cin, st)
+    timer.end(tok, 2.0 * P * T * Cin * Cout)
+    if 'tout' in DIAG:
+        return
+    tok = timer.begin('winograd_transform')
+    if unpool is not None:
+        _lib.call('wesup_winograd_output_transform_unpool', _p(Mt), 0, _p(bias), _p(mask_src), _p(us), _p(udst), B, H, W, Hu, Wu,
+                  Cout, m, st)
+        # bytes: the transformed gradient in, the windows of the pre-pool activations, one position of four read and re-written
+        timer.end(tok, 4.0 * (P * T + (4 + 2) * B * H * W) * Cout)
+    else:
+        _lib.call('wesup_winograd_output_transform', _p(Mt), 0, _p(bias), _p(mask_src), _p(out), _p(out_relu), _p(out_pool),
+                  int(pool_relu), B, H, W, Cout, int(accumulate), m, st)
+        n_io = 1 + (out_relu is not None) + (mask_src is not None) + bool(accumulate) + (0.25 if out_pool is not None else 0)
+        timer.end(tok, 4.0 * (P * T + n_io * B * H * W) * Cout)
 
 
 def conv3x3_fwd_winograd(x, u_fwd, bias, relu_in, out=None, out_relu=None, v_keep=None, ws_tag='default', timer=None,
@@ -602,8 +600,15 @@ def conv3x3_fwd_winograd(x, u_fwd, bias, relu_in, out=None, out_relu=None, v_kee
         _chk(out_pool, name='out_pool'); assert out_pool.shape == (B, H // 2, W // 2, Cout) and out_pool.is_contiguous()
     # relu_bits_out (B,H,W,Cin/4) uint8: the sign bits of x; pool_code_out (B,H/2,W/2,Cout/4) int16: the pooling's decisions
     # (include/wesup_hip.h: wesup_winograd_input_transform_bits, wesup_winograd_gemm_output_transform_ex)
-    return _winograd_conv(x, u_fwd, bias, None, out, out_relu, v_keep, relu_in, False, ws_tag, timer, out_pool, pool_relu, m,
-                          relu_bits_out=relu_bits_out, pool_code_out=pool_code_out, after_transform=after_transform)
+    if relu_bits_out is not None:
+        assert m == 4 and relu_bits_out.dtype == torch.uint8 and relu_bits_out.shape == (B, H, W, Cin // 4) and relu_bits_out.is_contiguous()
+    if pool_code_out is not None:
+        assert (out_pool is not None and pool_code_out.dtype == torch.int16
+                and pool_code_out.shape == (B, H // 2, W // 2, Cout // 4) and pool_code_out.is_contiguous())
+    _winograd_conv(x, u_fwd, m, ws_tag, timer, V=v_keep, relu_in=relu_in, relu_bits_out=relu_bits_out,
+                   after_transform=after_transform, bias=bias, out=out, out_relu=out_relu, out_pool=out_pool, pool_relu=pool_relu,
+                   pool_code_out=pool_code_out)
+    return out
 
 
 def conv3x3_dgrad_winograd(dy, u_dgrad, mask_src=None, out=None, accumulate=False, ws_tag='default', timer=None, m=2,
@@ -614,6 +619,8 @@ def conv3x3_dgrad_winograd(dy, u_dgrad, mask_src=None, out=None, accumulate=Fals
     assert u_dgrad.shape == (winograd_positions(m), Cin, Cout)
     if mask_src is not None:
         _chk(mask_src, name='mask_src'); assert mask_src.shape == (B, H, W, Cin)
+    if mask_bits is not None:
+        assert mask_bits.dtype == torch.uint8 and mask_bits.shape == (B, H, W, Cin // 4) and mask_bits.is_contiguous()
     if out is None:
         assert not accumulate
         out = torch.empty(B, H, W, Cin, dtype=torch.float32, device=dy.device)
@@ -621,91 +628,32 @@ def conv3x3_dgrad_winograd(dy, u_dgrad, mask_src=None, out=None, accumulate=Fals
     # v_pre (P,tiles,Cout): dy's input transform, done already (winograd_dual_transform): only the products and the way back
     if v_pre is not None:
         _chk(v_pre, name='v_pre'); assert v_pre.shape == (winograd_positions(m), winograd_tiles(B, H, W, m), Cout)
-    return _winograd_conv(dy, u_dgrad, None, mask_src, out, None, v_pre, False, accumulate, ws_tag, timer, m=m, mask_bits=mask_bits,
-                          v_ready=v_pre is not None)
+    _winograd_conv(dy, u_dgrad, m, ws_tag, timer, V=v_pre, v_ready=v_pre is not None, mask_src=mask_src, mask_bits=mask_bits,
+                   out=out, accumulate=accumulate)
+    return out
 
 
 def conv3x3_dgrad_winograd_unpool(dy, u_dgrad, unpool_src, unpool_dst, ws_tag='default', timer=None, m=4, unpool_code=None,
                                   v_pre=None):
     """Input gradient of a layer that follows a 2x2 max-pool, added straight into the gradient of the PRE-pool activations:
     dy (B,H,W,Cout) at pooled resolution, unpool_src / unpool_dst (B,Hu,Wu,Cin) with H == Hu // 2, W == Wu // 2.  Equals
-    conv3x3_dgrad_winograd(out=dxp) followed by maxpool2_bwd(unpool_src, dxp, unpool_dst, accumulate=True)."""
+    conv3x3_dgrad_winograd(out=dxp) followed by maxpool2_bwd(unpool_src, dxp, unpool_dst, accumulate=True).
+    unpool_code (B,H,W,Cin/4) int16: the pooling's decisions as codes (conv3x3_fwd_winograd(pool_code_out=...)) instead of a read
+    of unpool_src; v_pre (P,tiles,Cout): dy's input transform, done already (winograd_dual_transform)."""
     _chk(dy, name='dy'); _chk(u_dgrad, name='u_dgrad'); _chk(unpool_dst, name='unpool_dst')
     B, H, W, Cout = dy.shape
     Cin = u_dgrad.shape[1]
     assert m == 4 and u_dgrad.shape == (winograd_positions(m), Cin, Cout)
     _, Hu, Wu, _ = unpool_dst.shape
     assert unpool_dst.shape == (B, Hu, Wu, Cin) and (Hu // 2, Wu // 2) == (H, W)
-    lib = _lib.load()
-    route = lib.wesup_winograd_fused_route(Cout, Cin, m, winograd_tiles(B, H, W, m))
-    if unpool_code is not None or (v_pre is not None and route == 2):
-        # the pooling's decisions as codes (conv3x3_fwd_winograd(pool_code_out=...)): no read of unpool_src; and / or the input
-        # transform of dy done already (winograd_dual_transform).  One-kernel product route only.
-        if unpool_code is not None:
-            assert unpool_code.dtype == torch.int16 and unpool_code.shape == (B, H, W, Cin // 4) and unpool_code.is_contiguous()
-        else:
-            _chk(unpool_src, name='unpool_src'); assert unpool_src.shape == unpool_dst.shape
-        if lib.wesup_winograd_fused_supported(Cout, Cin, m) != 2:
-            raise _lib.WesupHipError(f'winograd dgrad {Cout} -> {Cin}: unpool_code needs the one-kernel product route')
-        T, P = winograd_tiles(B, H, W, m), winograd_positions(m)
-        st = _stream()
-        if v_pre is None:
-            nb = lib.wesup_conv3x3_winograd_workspace_bytes(B, H, W, Cout, Cin, m)
-            ws = workspace(nb, dy.device, ws_tag)
-            tok = timer.begin('winograd_transform') if timer else None
-            _lib.call('wesup_winograd_input_transform', _p(dy), _p(ws), 0, B, H, W, Cout, 0, m, st)
-            if timer:
-                timer.end(tok, 4.0 * (B * H * W + P * T) * Cout)
-        else:
-            _chk(v_pre, name='v_pre'); assert v_pre.shape == (P, T, Cout)
-            ws = v_pre
-        tok = timer.begin('winograd_gemm') if timer else None
-        _lib.call('wesup_winograd_gemm_output_transform_ex', _p(ws), 0, _p(u_dgrad), None, None, None, None, None, 0, None,
-                  _p(None if unpool_code is not None else unpool_src),
-                  _p(unpool_code), _p(unpool_dst), Hu, Wu, None, None, None, 0, B, H, W, Cout, Cin, 0, st)
-        if timer:
-            timer.end(tok, 2.0 * P * T * Cin * Cout)
-        return unpool_dst
-    _chk(unpool_src, name='unpool_src')
-    assert unpool_src.shape == unpool_dst.shape
-    nb = lib.wesup_conv3x3_winograd_workspace_bytes(B, H, W, Cout, Cin, m)
-    if not nb:
-        raise _lib.WesupHipError(f'winograd dgrad: unsupported shape {(B, H, W, Cout, Cin, m)}')
-    ws = workspace(nb, dy.device, ws_tag)
-    if timer is None and v_pre is None:
-        _lib.call('wesup_conv3x3_dgrad_winograd_unpool', _p(dy), _p(u_dgrad), _p(unpool_src), _p(unpool_dst), B, H, W, Hu, Wu,
-                  Cin, Cout, m, _p(ws), nb, _stream())
-        return unpool_dst
-    # the three passes bracketed as classes of their own, as in _winograd_conv
-    class _NoTimer:
-        def begin(self, tag): return None
-        def end(self, tok, work): pass
-    timer = timer or _NoTimer()
-    T, P = winograd_tiles(B, H, W, m), winograd_positions(m)
-    v_bytes = (P * T * Cout * 4 + 255) // 256 * 256
-    V, Mt = ws[:v_bytes], ws[v_bytes:]
-    st = _stream()
-    if v_pre is not None:      # dy's input transform, done already (winograd_dual_transform)
-        _chk(v_pre, name='v_pre'); assert v_pre.shape == (P, T, Cout)
-        V = v_pre
+    if unpool_code is not None:
+        assert unpool_code.dtype == torch.int16 and unpool_code.shape == (B, H, W, Cin // 4) and unpool_code.is_contiguous()
+        unpool_src = None
     else:
-        tok = timer.begin('winograd_transform')
-        _lib.call('wesup_winograd_input_transform', _p(dy), _p(V), 0, B, H, W, Cout, 0, m, st)
-        timer.end(tok, 4.0 * (B * H * W + P * T) * Cout)
-    if route == 2:
-        tok = timer.begin('winograd_gemm')
-        _lib.call('wesup_winograd_gemm_output_transform', _p(V), 0, _p(u_dgrad), None, None, None, None, 0, _p(unpool_src),
-                  _p(unpool_dst), Hu, Wu, B, H, W, Cout, Cin, 0, st)
-        timer.end(tok, 2.0 * P * T * Cin * Cout)
-        return unpool_dst
-    tok = timer.begin('winograd_gemm')
-    _lib.call('wesup_gemm_nt_batched', _p(V), Cout, T * Cout, _p(u_dgrad), Cout, Cin * Cout, _p(Mt), Cin, T * Cin, P, T, Cin, Cout, st)
-    timer.end(tok, 2.0 * P * T * Cin * Cout)
-    tok = timer.begin('winograd_transform')
-    _lib.call('wesup_winograd_output_transform_unpool', _p(Mt), 0, None, None, _p(unpool_src), _p(unpool_dst), B, H, W, Hu, Wu,
-              Cin, m, st)
-    # bytes: the transformed gradient in, the windows of the pre-pool activations, one position of four read and re-written
-    timer.end(tok, 4.0 * (P * T + (4 + 2) * B * H * W) * Cin)
+        _chk(unpool_src, name='unpool_src'); assert unpool_src.shape == unpool_dst.shape
+    if v_pre is not None:
+        _chk(v_pre, name='v_pre'); assert v_pre.shape == (winograd_positions(m), winograd_tiles(B, H, W, m), Cout)
+    _winograd_conv(dy, u_dgrad, m, ws_tag, timer, V=v_pre, v_ready=v_pre is not None, unpool=(unpool_src, unpool_code, unpool_dst))
     return unpool_dst
 
 
@@ -730,7 +678,7 @@ def conv3x3_dgrad_winograd_gather(dy, u_dgrad, side, new_row, area_new, out, mas
     Cin = u_dgrad.shape[1]
     Kmax = side.shape[1]
     assert u_dgrad.shape == (36, Cin, Cout) and side.shape == (B, Kmax, Cin) and (area_new is None or area_new.shape == (B, Kmax))
-    Hu = Wu = 0
+    unpool = None
     if unpool_src is not None or unpool_code is not None:
         _, Hu, Wu, _ = out.shape
         assert out.shape == (B, Hu, Wu, Cin) and (Hu // 2, Wu // 2) == (H, W) and Hu % 2 == 0 and Wu % 2 == 0
@@ -740,6 +688,7 @@ def conv3x3_dgrad_winograd_gather(dy, u_dgrad, side, new_row, area_new, out, mas
             unpool_src = None
         else:
             _chk(unpool_src, name='unpool_src'); assert unpool_src.shape == out.shape
+        unpool = (unpool_src, unpool_code, out)
     else:
         assert out.shape == (B, H, W, Cin) and new_row.shape == (B, H * W)
         if mask_bits is not None:
@@ -747,38 +696,10 @@ def conv3x3_dgrad_winograd_gather(dy, u_dgrad, side, new_row, area_new, out, mas
             mask_src = None
         elif mask_src is not None:
             _chk(mask_src, name='mask_src'); assert mask_src.shape == out.shape
-    lib = _lib.load()
-    if lib.wesup_winograd_fused_supported(Cout, Cin, 4) != 2:
-        raise _lib.WesupHipError(f'conv3x3_dgrad_winograd_gather: product {Cout} -> {Cin} is not on the one-kernel route')
-    nb = lib.wesup_conv3x3_winograd_workspace_bytes(B, H, W, Cout, Cin, 4)
-    ws = workspace(nb, dy.device, ws_tag)
-    compact = mask_bits is not None or unpool_code is not None
     if v_pre is not None:      # dy's input transform, done already (winograd_dual_transform)
         _chk(v_pre, name='v_pre'); assert v_pre.shape == (36, winograd_tiles(B, H, W, 4), Cout)
-    if timer is None and not compact and v_pre is None:
-        _lib.call('wesup_conv3x3_dgrad_winograd_gather', _p(dy), _p(u_dgrad), _p(mask_src), _p(unpool_src), _p(out), _p(side),
-                  _p(new_row), _p(area_new), Kmax, B, H, W, Hu, Wu, Cin, Cout, _p(ws), nb, _stream())
-        return out
-    T, P = winograd_tiles(B, H, W, 4), 36
-    st = _stream()
-    if v_pre is None:
-        tok = timer.begin('winograd_transform') if timer else None
-        _lib.call('wesup_winograd_input_transform', _p(dy), _p(ws), 0, B, H, W, Cout, 0, 4, st)
-        if timer:
-            timer.end(tok, 4.0 * (B * H * W + P * T) * Cout)
-    else:
-        ws = v_pre
-    tok = timer.begin('winograd_gemm') if timer else None
-    if compact:
-        pooled = Hu > 0
-        _lib.call('wesup_winograd_gemm_output_transform_ex', _p(ws), 0, _p(u_dgrad), None, _p(mask_src), _p(mask_bits),
-                  _p(None if pooled else out), None, 0, None, _p(unpool_src), _p(unpool_code), _p(out if pooled else None), Hu, Wu,
-                  _p(side), _p(new_row), _p(area_new), Kmax, B, H, W, Cout, Cin, 0, st)
-    else:
-        _lib.call('wesup_winograd_gemm_output_transform_gather', _p(ws), 0, _p(u_dgrad), _p(mask_src), _p(out), _p(unpool_src), Hu, Wu,
-                  _p(side), _p(new_row), _p(area_new), Kmax, B, H, W, Cout, Cin, st)
-    if timer:
-        timer.end(tok, 2.0 * P * T * Cin * Cout)
+    _winograd_conv(dy, u_dgrad, 4, ws_tag, timer, V=v_pre, v_ready=v_pre is not None, mask_src=mask_src, mask_bits=mask_bits,
+                   out=out, unpool=unpool, gather=(side, new_row, area_new))
     return out
 
 
