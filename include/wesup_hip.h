@@ -462,6 +462,23 @@ int wesup_directed_hausdorff_sq(const int32_t* pairs, const int32_t* start_x, co
                                 const int32_t* bstart_y, const int32_t* bpix_y, int32_t* d2, int P, int H, int W, int LX, int LY,
                                 void* stream);
 
+/* ------------------------------------------------------------------ window inference on large images (csrc/tiles.hip)
+ * The device ends of infer_tile.py: cutting an image into the network's input windows and merging the per-window predictions.
+ * The window lattice is tops[n_h] x lefts[n_w] (int32, device memory, sorted, first 0, last size - p: infer_tile.window_grid);
+ * window k, row-major, has its corner at (tops[k / n_w], lefts[k % n_w]).  Both entries return WESUP_ERR_INVALID for a null
+ * pointer, p < 1, p > H, p > W, n_h < 1 or n_w < 1 (and count < 1, first < 0 / C < 1); no workspace, no host sync.
+ *
+ * wesup_window_gather: img uint8 [H][W][3] -> out fp32 [count][3][p][p], the windows first .. first + count - 1 scaled to
+ * [0, 1] exactly as ATen's uint8 -> float -> div_(255.) does on the device (a multiplication by the fp32 reciprocal); an index
+ * >= n_h * n_w repeats the last window (the padding of a ragged final batch). */
+int wesup_window_gather(const uint8_t* img, const int32_t* tops, const int32_t* lefts, float* out, int H, int W, int n_h, int n_w,
+                        int p, int first, int count, void* stream);
+/* pred fp32 [n_h * n_w][p][p][C] -> out fp64 [H][W][C]: the mean over the windows that cover a pixel -- the values (rintf of
+ * them with round_first: half to even) added as doubles in ascending window order and divided by the count once, which is
+ * infer_tile.combine_patches_to_image bit for bit */
+int wesup_window_merge(const float* pred, const int32_t* tops, const int32_t* lefts, double* out, int H, int W, int C, int n_h,
+                       int n_w, int p, int round_first, void* stream);
+
 /* ------------------------------------------------------------------ entries by the names of SURVEY.md 8(b)
  * One call per ATen op of the reference for a binding that replaces them one by one; each is a thin entry over the
  * kernels above (csrc/named.hip).  Matrices are row-major with the channel / feature index contiguous (NHWC pixels). */

@@ -121,6 +121,9 @@ _SIGS = {
     'wesup_label_sort_workspace_bytes': (c_size_t, 'iiii'),
     'wesup_label_sort': (c_int, 'pppppp' + 'iiii' + 'pzp'),
     'wesup_directed_hausdorff_sq': (c_int, 'ppppppp' + 'iiiii' + 'p'),
+    # window inference on large images (csrc/tiles.hip)
+    'wesup_window_gather': (c_int, 'pppp' + 'iiiiiii' + 'p'),
+    'wesup_window_merge': (c_int, 'pppp' + 'iiiiiii' + 'p'),
     # entries by the names of SURVEY.md 8(b) (csrc/named.hip)
     'wesup_sp_stats': (c_int, 'ppiiiipppp'),
     'wesup_conv1x1_workspace_bytes': (c_size_t, 'iii'),

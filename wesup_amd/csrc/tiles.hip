@@ -1,0 +1,134 @@
+// Window inference on images larger than the network input, the two ends of it that used to run on the host:
+// cutting an (H, W, 3) uint8 image into the fp32 windows the network reads, and merging the per-window predictions into one
+// map by the mean over the covering windows.  Both kernels are pure memory movement: no LDS, no atomics, no workspace.
+//
+// The window lattice (infer_tile.window_grid) is two sorted int32 arrays on the device, tops[n_h] and lefts[n_w]; window k
+// (row-major) has its corner at (tops[k / n_w], lefts[k % n_w]).  The arrays are made by the caller: neither kernel trusts
+// them with an address.  The gather clamps a corner into the image, the merge only ever reads pred at offsets it has itself
+// tested to lie in [0, p), so a wrong lattice gives wrong numbers (NaN where no window covers a pixel), never a fault.
+#include "common.hpp"
+
+#define TL_BLOCK 256
+#define TL_MAX_BLOCKS 4096     // grid-stride above this (cdna_hip_programming.md, guideline 11)
+
+namespace {
+
+// What ATen makes of uint8 -> float -> div_(255.) on the device: the division by a host scalar is a multiplication by the
+// fp32 reciprocal (1.f / 255.f rounded once, on the host), which differs from x / 255.f in the last bit for some bytes.
+// tests/test_tiles_gpu.py holds all 256 values to infer_tile._to_tensor bit for bit.
+__device__ __forceinline__ float byte_to_unit(uint8_t v) { return (float)v * (1.0f / 255.0f); }
+
+// out[n][c][y][x] = unit(img[top + y][left + x][c]) for the windows first .. first + count - 1, the last window repeated
+// past the end of the lattice.  One thread makes VEC pixels along x of all three planes: 3 * VEC bytes in (neighbouring
+// lanes read neighbouring bytes), one VEC-wide store per plane.  VEC = 4 needs p % 4 == 0 (16-byte aligned stores).
+template <int VEC>
+__global__ __launch_bounds__(TL_BLOCK) void tl_gather_kernel(const uint8_t* __restrict__ img, const int32_t* __restrict__ tops,
+                                                             const int32_t* __restrict__ lefts, float* __restrict__ out, int H,
+                                                             int W, int n_h, int n_w, int p, int first, int count) {
+    const int pv = p / VEC;
+    const long per_win = (long)p * pv;
+    const long total = (long)count * per_win;
+    const long plane = (long)p * p;
+    const int last = n_h * n_w - 1;
+    for (long idx = (long)blockIdx.x * TL_BLOCK + threadIdx.x; idx < total; idx += (long)gridDim.x * TL_BLOCK) {
+        const int n = (int)(idx / per_win);
+        const int r = (int)(idx - (long)n * per_win);
+        const int y = r / pv, x = (r - y * pv) * VEC;
+        int k = first + n;
+        k = k > last ? last : k;
+        const int wi = k / n_w, wj = k - wi * n_w;
+        int top = tops[wi], left = lefts[wj];
+        top = top < 0 ? 0 : (top > H - p ? H - p : top);
+        left = left < 0 ? 0 : (left > W - p ? W - p : left);
+        const uint8_t* src = img + ((long)(top + y) * W + left + x) * 3;
+        float v[3][VEC];
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) v[c][i] = byte_to_unit(src[i * 3 + c]);
+        }
+        float* dst = out + (long)n * 3 * plane + (long)y * p + x;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            if (VEC == 4) st4(dst + c * plane, make_float4(v[c][0], v[c][1], v[c][2], v[c][3]));
+            else dst[c * plane] = v[c][0];
+        }
+    }
+}
+
+// out[y][x][c] = mean over the windows that cover (y, x) of pred[k][y - top][x - left][c], in fp64.  One thread per output
+// element (c fastest: loads and stores of neighbouring lanes are neighbours).  The lattice is sorted, so the covering windows
+// are a range of rows times a range of columns: n_h + n_w comparisons find it.  The values are added as doubles in ascending
+// row-major window order onto 0.0 and divided by the count once -- the order and the operations of
+// infer_tile.combine_patches_to_image, hence its result bit for bit (adds and one IEEE division: nothing to contract).
+__global__ __launch_bounds__(TL_BLOCK) void tl_merge_kernel(const float* __restrict__ pred, const int32_t* __restrict__ tops,
+                                                            const int32_t* __restrict__ lefts, double* __restrict__ out, int H,
+                                                            int W, int C, int n_h, int n_w, int p, int round_first) {
+    const long total = (long)H * W * C;
+    const long WC = (long)W * C;
+    for (long idx = (long)blockIdx.x * TL_BLOCK + threadIdx.x; idx < total; idx += (long)gridDim.x * TL_BLOCK) {
+        const int y = (int)(idx / WC);
+        const int r = (int)(idx - (long)y * WC);
+        const int x = r / C, c = r - x * C;
+        int i0 = n_h, i1 = 0, j0 = n_w, j1 = 0;      // [i0, i1) x [j0, j1): the covering windows
+        for (int i = 0; i < n_h; ++i) {
+            const int d = y - tops[i];
+            if (d >= 0 && d < p) { i0 = i < i0 ? i : i0; i1 = i + 1; }
+        }
+        for (int j = 0; j < n_w; ++j) {
+            const int d = x - lefts[j];
+            if (d >= 0 && d < p) { j0 = j < j0 ? j : j0; j1 = j + 1; }
+        }
+        double acc = 0.0;
+        int cnt = 0;
+        for (int i = i0; i < i1; ++i) {
+            const int dy = y - tops[i];
+            if (dy < 0 || dy >= p) continue;         // (an unsorted lattice: never an address outside the window)
+            for (int j = j0; j < j1; ++j) {
+                const int dx = x - lefts[j];
+                if (dx < 0 || dx >= p) continue;
+                float v = pred[(((long)(i * n_w + j) * p + dy) * p + dx) * C + c];
+                if (round_first) v = rintf(v);       // half to even: torch.round / np.round
+                acc += (double)v;
+                ++cnt;
+            }
+        }
+        out[idx] = acc / (double)cnt;
+    }
+}
+
+inline unsigned tl_blocks(long total) {
+    const long b = (total + TL_BLOCK - 1) / TL_BLOCK;
+    return (unsigned)(b > TL_MAX_BLOCKS ? TL_MAX_BLOCKS : b);
+}
+
+}  // namespace
+
+extern "C" int wesup_window_gather(const uint8_t* img, const int32_t* tops, const int32_t* lefts, float* out, int H, int W,
+                                   int n_h, int n_w, int p, int first, int count, void* stream) {
+    if (!img || !tops || !lefts || !out || p < 1 || p > H || p > W || n_h < 1 || n_w < 1 || first < 0 || count < 1 ||
+        (long)n_h * n_w > 0x7fffffffl)
+        return WESUP_ERR_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    if (p % 4 == 0) {
+        WESUP_LAUNCH(tl_gather_kernel<4>, dim3(tl_blocks((long)count * p * (p / 4))), dim3(TL_BLOCK), 0, st, img, tops, lefts, out,
+                     H, W, n_h, n_w, p, first, count);
+    } else {
+        WESUP_LAUNCH(tl_gather_kernel<1>, dim3(tl_blocks((long)count * p * p)), dim3(TL_BLOCK), 0, st, img, tops, lefts, out, H, W,
+                     n_h, n_w, p, first, count);
+    }
+    WESUP_CHECK_LAUNCH();
+    return WESUP_OK;
+}
+
+extern "C" int wesup_window_merge(const float* pred, const int32_t* tops, const int32_t* lefts, double* out, int H, int W, int C,
+                                  int n_h, int n_w, int p, int round_first, void* stream) {
+    if (!pred || !tops || !lefts || !out || p < 1 || p > H || p > W || C < 1 || n_h < 1 || n_w < 1 ||
+        (long)n_h * n_w > 0x7fffffffl)
+        return WESUP_ERR_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    WESUP_LAUNCH(tl_merge_kernel, dim3(tl_blocks((long)H * W * C)), dim3(TL_BLOCK), 0, st, pred, tops, lefts, out, H, W, C, n_h,
+                 n_w, p, round_first ? 1 : 0);
+    WESUP_CHECK_LAUNCH();
+    return WESUP_OK;
+}

@@ -1356,3 +1356,90 @@ def directed_hausdorff_sq(pairs, X, Y):
         _lib.call('wesup_directed_hausdorff_sq', _p(pairs), _p(X.start), _p(X.pix), _p(Y.labels), _p(Y.bstart), _p(Y.bpix),
                   _p(d2), P, H, W, X.L, Y.L, _stream())
     return d2
+
+
+# ---------------------------------------------------------------- window inference on large images (csrc/tiles.hip)
+_lattice_cache = {}    # (device, axis positions) -> int32 device tensor: an image size meets the same few lattices again and again
+
+
+def _lattice_axis(pos, size, p, name, device):
+    """One axis of a window lattice (infer_tile.window_grid), checked on the HOST -- the kernels read it from device memory and
+    cannot be asked -- and uploaded once per (device, contents): sorted, first window at 0, last one flush at ``size - p``, no
+    pixel between two windows left uncovered."""
+    pos = [int(v) for v in pos]
+    if not pos:
+        raise _lib.WesupHipError(f'window lattice: {name} is empty')
+    if any(b < a for a, b in zip(pos, pos[1:])):
+        raise _lib.WesupHipError(f'window lattice: {name} {pos} is not sorted')
+    if pos[0] != 0 or pos[-1] != size - p:
+        raise _lib.WesupHipError(f'window lattice: {name} {pos} does not run from 0 to size - p = {size - p}')
+    if any(b - a > p for a, b in zip(pos, pos[1:])):
+        raise _lib.WesupHipError(f'window lattice: {name} {pos} leaves pixels between windows of {p} uncovered')
+    key = (str(device), tuple(pos))
+    t = _lattice_cache.get(key)
+    if t is None:
+        if len(_lattice_cache) >= 256:
+            _lattice_cache.clear()
+        t = _lattice_cache[key] = torch.tensor(pos, dtype=torch.int32, device=device)
+    return t
+
+
+def _lattice(tops, lefts, H, W, p, device):
+    p = int(p)
+    if p < 1 or p > H or p > W:
+        raise _lib.WesupHipError(f'window lattice: patch size {p} for an image of {H} x {W}')
+    return _lattice_axis(tops, H, p, 'tops', device), _lattice_axis(lefts, W, p, 'lefts', device)
+
+
+def window_gather(img_u8_hwc, tops, lefts, p, first, count, out=None):
+    """Network input windows of an image on the device: img (H,W,3) uint8, the lattice ``tops`` x ``lefts`` of
+    infer_tile.window_grid (host integer sequences; checked here, their device copies are cached) -> (count,3,p,p) fp32 in
+    [0, 1], the row-major windows ``first .. first + count - 1``, bit-equal to infer_tile._to_tensor.  Indices past the last
+    window repeat it (the padding of a ragged final batch)."""
+    if not isinstance(img_u8_hwc, torch.Tensor) or img_u8_hwc.dim() != 3 or img_u8_hwc.shape[-1] != 3:
+        raise _lib.WesupHipError('window_gather: expected an (H,W,3) uint8 image')
+    H, W, _ = img_u8_hwc.shape
+    first, count, p = int(first), int(count), int(p)
+    if first < 0 or count < 1:
+        raise _lib.WesupHipError(f'window_gather: windows [{first}, {first} + {count})')
+    tops_d, lefts_d = _lattice(tops, lefts, H, W, p, img_u8_hwc.device)
+    _chk(img_u8_hwc, torch.uint8, 'img')
+    if out is None:
+        out = torch.empty(count, 3, p, p, dtype=torch.float32, device=img_u8_hwc.device)
+    _chk(out, name='out')
+    if out.shape != (count, 3, p, p) or out.device != img_u8_hwc.device or out.data_ptr() % 16:
+        raise _lib.WesupHipError(f'window_gather: out {tuple(out.shape)} on {out.device}, expected {(count, 3, p, p)}')
+    tok = _tbegin('window_gather')
+    _lib.call('wesup_window_gather', _p(img_u8_hwc), _p(tops_d), _p(lefts_d), _p(out), H, W, tops_d.numel(), lefts_d.numel(), p,
+              first, count, _stream())
+    _tend(tok, 15.0 * count * p * p)                  # 3 bytes in, 3 floats out per window pixel
+    return out
+
+
+def window_merge(pred, tops, lefts, H, W, round_first=False, out=None):
+    """Mean over the covering windows: pred (N,p,p,C) or (N,p,p) fp32 for ALL N = len(tops) * len(lefts) windows of one image
+    (row-major) -> (H,W,C) / (H,W) fp64, equal to infer_tile.combine_patches_to_image bit for bit; ``round_first`` rounds
+    every value half to even before it is added (torch.round / np.round of the per-window path)."""
+    if not isinstance(pred, torch.Tensor) or pred.dim() not in (3, 4):
+        raise _lib.WesupHipError('window_merge: expected (N,p,p) or (N,p,p,C) predictions')
+    flat = pred.dim() == 3
+    N, p, p2 = pred.shape[:3]
+    C = 1 if flat else pred.shape[3]
+    H, W = int(H), int(W)
+    if p != p2 or C < 1:
+        raise _lib.WesupHipError(f'window_merge: pred {tuple(pred.shape)}')
+    tops_d, lefts_d = _lattice(tops, lefts, H, W, p, pred.device)
+    if N != tops_d.numel() * lefts_d.numel():
+        raise _lib.WesupHipError(f'window_merge: {N} windows for a lattice of {tops_d.numel()} x {lefts_d.numel()}')
+    _chk(pred, name='pred')
+    shape = (H, W) if flat else (H, W, C)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float64, device=pred.device)
+    _chk(out, torch.float64, 'out')
+    if out.shape != shape or out.device != pred.device:
+        raise _lib.WesupHipError(f'window_merge: out {tuple(out.shape)} on {out.device}, expected {shape}')
+    tok = _tbegin('window_merge')
+    _lib.call('wesup_window_merge', _p(pred), _p(tops_d), _p(lefts_d), _p(out), H, W, C, tops_d.numel(), lefts_d.numel(), p,
+              int(bool(round_first)), _stream())
+    _tend(tok, 4.0 * N * p * p * C + 8.0 * H * W * C)
+    return out
