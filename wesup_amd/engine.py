@@ -28,15 +28,8 @@ import os
 
 import torch
 
-from . import ops
-
-CONV_IDX = [0, 2, 5, 7, 10, 12, 14, 17, 19, 21, 24, 26, 28]
-CONV_CH = [(3, 64), (64, 64), (64, 128), (128, 128), (128, 256), (256, 256), (256, 256),
-           (256, 512), (512, 512), (512, 512), (512, 512), (512, 512), (512, 512)]
-POOL_AFTER = [False, True, False, True, False, False, True, False, False, True, False, False, False]
-SIDE_OFF = [0, 32, 64, 128, 192, 320, 448, 576, 832, 1088, 1344, 1600, 1856]
-FM_CHANNELS = 2112
-# (the 13th conv is followed by a MaxPool in VGG16 whose output the reference discards, models/wesup.py:279)
+from . import layer_plan, ops
+from .layer_plan import CONV_IDX, CONV_CH, POOL_AFTER, SIDE_OFF, FM_CHANNELS
 
 
 class KernelTimer:
@@ -106,7 +99,8 @@ def default_route(ci, co, h, w, B):
     the activation bytes) at 480x480, 800x800 and 1024x1024, down to the 8x8-tile maps of conv5_x; F(2x2) (4/9 of the
     multiply-adds, 4x the bytes) is slower than F(4x4) everywhere and slower than the direct kernel at 64 input channels.
     Inside the step the two 64-channel layers (conv1_2, conv2_1: HBM-bound in the domain) gain 0.5 % at 480x480 and 2 % at
-    800x800 / 1024x1024 (bench.py --winograd-min-ci 128 for the A/B); the image layer (3 channels) has no Winograd form."""
+    800x800 / 1024x1024 (WesupEngine.WINOGRAD_CONV_MIN_CI = 128 for the A/B, or a route_fn of one's own); the image layer
+    (3 channels) has no Winograd form."""
     if ci < WesupEngine.WINOGRAD_CONV_MIN_CI:
         return 0
     return WesupEngine.WINOGRAD_TILE
@@ -119,15 +113,10 @@ class WesupEngine:
     WINOGRAD_MIN_CI, WINOGRAD_MIN_CO = 128, 256
     # layers whose forward and input gradient go through the Winograd domain when conv_winograd is on: every layer
     # with >= 64 input channels (conv1_2 ... conv5_3); the image layer stays on the implicit-GEMM kernel.
-    # bench.py --winograd-min-ci / --winograd-tile for the A/B.
+    # default_route reads these two class attributes; an engine's route_fn replaces the rule altogether.
     WINOGRAD_CONV_MIN_CI = 64
     WINOGRAD_TILE = 4                    # m of F(m x m, 3x3) for those layers: 4 (default) or 2 (round 2's routing)
-    # Positions of the backward walk, measured in rounds 3 - 5 (every alternative within +-0.05 ms, HISTORY.md) and fixed: the deep
-    # layers' side-conv weight gradients are queued when the chain reaches conv2_1; the shallow layers' side-branch gradients at the
-    # head of the weight-gradient stream; the weight gradient of the layer above the lowest trainable one stays in front of its
-    # input gradient, every other one goes behind
-    _DEEP_SIDE_WGRAD_AT = 2
-    _WGRAD_EARLY_LAYERS = 1
+    # (the fixed positions of the backward walk -- which weight gradients are queued late -- are layer_plan's)
 
     def __init__(self, params, grads, D=32):
         """params/grads: dict name -> tensor (views of the flat parameter / gradient buffers)."""
@@ -168,7 +157,8 @@ class WesupEngine:
         self.plain = False
         self._diag_skip = set()          # TIMING-ONLY diagnostics (bench.py --diag-skip): classes of launches left out, results wrong
         self.route_fn = default_route    # (ci, co, h, w, B) -> 0 | 2 | 4, consulted per layer and shape
-        self._route = None               # the 13 tile sizes of the current / most recent shape
+        self._routes = {}                # route() per (rule, shape), as tuples
+        self._last_shape = None          # (B, H, W) of the most recent forward
         self._side_stream = None
         self._wgrad_stream = None
         self.timer = KernelTimer()
@@ -275,7 +265,7 @@ class WesupEngine:
         step (their lazily allocated parts exist), else the constant above."""
         best = 0.0
         for (B, H, W, _), b in self._bufs.items():
-            if getattr(b, 'train', False) and getattr(b, 'x_in', None) is not None:
+            if getattr(b, 'train', False) and b.plans:
                 best = max(best, self._set_bytes(b) / float(B * H * W))
         return best * 1.1 if best > 0 else float(self.BYTES_PER_PIXEL)
 
@@ -322,56 +312,38 @@ class WesupEngine:
             self.buf_generation += 1
             b.gen = self.buf_generation
             b.x0 = torch.empty(B, H, W, 4, **f32)
-            b.y, b.yp, b.s, b.dims, b.yr, b.yr_wanted = [], [], [], [], [], []
+            b.y, b.yp, b.s, b.dims, b.yr = [], [], [], [], []
             b.V = [None] * 13            # Winograd-transformed layer inputs (training forward), allocated on first use
             h, w = H, W
             for l, (ci, co) in enumerate(CONV_CH):
                 b.dims.append((h, w))
                 b.y.append(torch.empty(B, h, w, co, **f32))
                 b.s.append(None)         # side outputs: views of the group buffers below, or allocated on first use (_side_out)
-                # the ReLU'd copy the next conv (forward and wgrad) reads: the pooled tensor where the layer is pooled
-                # (stored ReLU'd), a second output of the conv kernel elsewhere; the last layer has no reader
-                b.yr.append(None)        # allocated on first use (forward): a Winograd-domain consumer never needs it
-                b.yr_wanted.append(bool(not POOL_AFTER[l] and l < 12))
+                b.yr.append(None)        # the ReLU'd copy, allocated on first use (forward): a Winograd-domain consumer never needs it
                 if POOL_AFTER[l]:
                     h, w = h // 2, w // 2
                     b.yp.append(torch.empty(B, h, w, co, **f32))
                 else:
                     b.yp.append(None)
-            # Coarse resolutions (deep layers): upsample + scatter-mean and its backward run as GEMMs with the
-            # interpolation-pooling matrix Wm of the resolution; the side outputs of the layers that share a
-            # resolution sit side by side in one buffer so that one GEMM per image serves all of them.
-            b.groups, b.group_of = [], [None] * 13
-            if self.fuse_pool_fwd and self.fuse_pool_bwd and self.matrix_pool and Kmax % 4 == 0:
-                l = 0
-                while l < 13:
-                    e = l
-                    while e + 1 < 13 and b.dims[e + 1] == b.dims[l]:
-                        e += 1
-                    gh, gw = b.dims[l]
-                    # ... up to 4096 cells and a matrix of at most 16 MB per image: beyond that (1024^2 with 3025 superpixels: conv5_x's
-                    # 64 x 64 map under 3072 rows = 50 MB per image, 19 GF per image and direction) the gather form with the side
-                    # conv commuted is faster (8 x 1024^2: 62.3 -> 61.2 ms, round 6); below it the matrix form is (batch 1: 7 - 9 %)
-                    if (gh, gw) != (H, W) and gh * gw <= 4096 and (gh * gw) % 4 == 0 and Kmax * gh * gw <= (4 << 20):
-                        g = _Bufs()
-                        g.layers, g.h, g.w = list(range(l, e + 1)), gh, gw
-                        g.off = SIDE_OFF[l]
-                        g.C = sum(CONV_CH[i][1] // 2 for i in g.layers)
-                        g.s = g.ds = None    # side outputs / their gradients side by side: allocated on first use
-                        g.Wm = torch.empty(B, Kmax, gh * gw, **f32)
-                        g.WmT = torch.empty(B, gh * gw, Kmax, **f32)
-                        for i in g.layers:
-                            b.group_of[i] = len(b.groups)
-                        b.groups.append(g)
-                    l = e + 1
+            # the matrix-form groups of this set (layer_plan.groups_for): a set keeps the grouping it was made with
+            groups, group_of = layer_plan.groups_for(B, H, W, Kmax, self._switches())
+            b.group_of = list(group_of)
+            b.groups = []
+            for grp in groups:
+                g = _Bufs()
+                g.layers, g.h, g.w, g.off, g.C = list(grp.layers), grp.h, grp.w, grp.off, grp.C
+                g.s = g.ds = None    # side outputs / their gradients side by side: allocated on first use
+                g.Wm = torch.empty(B, Kmax, g.h * g.w, **f32)
+                g.WmT = torch.empty(B, g.h * g.w, Kmax, **f32)
+                b.groups.append(g)
             # the (B,HW,2112) feature map only exists on the unfused path (or when somebody asks for it)
             b.fm = None if self.fuse_pool_fwd else torch.empty(B, H, W, FM_CHANNELS, **f32)
             b.fm_valid = False
             b.ybar, b.dybar = [None] * 13, [None] * 13       # commuted side branch: mean_r(upsample(y_l)) and its gradient
             b.dM, b.bpart, b.dV = [None] * 13, [None] * 13, None   # dual_transform: per layer dM + bias rows, one shared V'
-            b.mbits, b.pcode = [None] * 13, [None] * 13      # compact_masks: sign bits / pooling codes of y_l (None: not kept)
-            b.mbits_ok, b.pcode_ok = [False] * 13, [False] * 13
+            b.mbits, b.pcode = [None] * 13, [None] * 13      # compact_masks: sign bits / pooling codes of y_l, allocated on first use
             b.s_valid = [False] * 13
+            b.plans = {}                 # train -> (key, StepPlan): see _plan
             b.shape = (B, H, W)
             R = B * Kmax
             b.sp_in = torch.empty(B, Kmax, FM_CHANNELS, **f32)
@@ -425,11 +397,6 @@ class WesupEngine:
             b.ds[l] = torch.empty(b.shape[0], h, w, CONV_CH[l][1] // 2, dtype=torch.float32, device=self.device)
         return b.ds[l]
 
-    def _commuted(self, b, l):
-        """Layer l's side conv behind the pooling instead of in front of it (see commute_side)."""
-        return (self.commute_side and self.fuse_pool_fwd and self.fuse_pool_bwd
-                and b.group_of[l] is None)
-
     def bufs_gen(self, B, H, W, Kmax):
         """The identity of the cached buffer set of a shape (None: not cached), marking it most recently used: what a
         recorded step plan of that shape depends on -- other shapes' sets coming and going do not move its addresses."""
@@ -448,14 +415,44 @@ class WesupEngine:
     def route(self, B, H, W):
         """Per layer: m of the Winograd domain its forward / input gradient (and, with the kept V, weight gradient) run in,
         or 0 for the implicit-GEMM kernel."""
-        r, h, w = [], H, W
-        for l, (ci, co) in enumerate(CONV_CH):
-            r.append(int(self.route_fn(ci, co, h, w, B)) if (self.conv_winograd and ci >= 32) else 0)
-            if POOL_AFTER[l]:
-                h, w = h // 2, w // 2
+        return list(layer_plan.route(self.route_fn, self.conv_winograd, B, H, W))
+
+    # ------------------------------------------------------------------ the plan
+    BENCH_SHAPE = (4, 480, 480)      # what a weight prefetch in front of the very first forward packs for
+
+    def _switches(self):
+        return layer_plan.Switches(self.fuse_pool_bwd, self.fuse_pool_fwd, self.two_streams, self.wgrad_winograd, self.conv_winograd,
+                                   self.plain, self.matrix_pool, self.fuse_side_fwd, self.WINOGRAD_MIN_CI, self.WINOGRAD_MIN_CO,
+                                   self.WINOGRAD_TILE)
+
+    def _route_of(self, B, H, W):
+        """route(B, H, W) as a tuple, remembered per (routing rule, shape): thirteen calls of the rule per walk otherwise."""
+        key = (self.route_fn, self.conv_winograd, self.WINOGRAD_CONV_MIN_CI, self.WINOGRAD_TILE, ops.winograd_fused_min_blocks(), B, H, W)
+        r = self._routes.get(key)
+        if r is None:
+            if len(self._routes) > 1024:
+                self._routes.clear()
+            r = self._routes[key] = tuple(self.route(B, H, W))
         return r
 
-    def _pack_weights(self, train):
+    def plan_key(self, B, H, W, train=True, route=None):
+        """Everything layer_plan.build reads besides the grouping a buffer set was made with: a changed key is a new plan (and a
+        new recording of the step runner)."""
+        return (self._switches(), self._route_of(B, H, W) if route is None else route, ops.winograd_fused_min_blocks(),
+                frozenset(self.frozen), frozenset(self._diag_skip), bool(train))
+
+    def _plan(self, b, train, route=None):
+        """The plan of buffer set b for a training / evaluation walk, rebuilt when its key changes (tests flip switches on a live
+        engine).  route: the forward's, for the backward that follows it."""
+        key = self.plan_key(*b.shape, train=train, route=route)
+        hit = b.plans.get(train)
+        if hit is None or hit[0] != key:
+            hit = b.plans[train] = (key, layer_plan.build(b.shape, b.group_of, key[1], key[0], key[4], key[3], train,
+                                                          ops.winograd_fused_supported, ops.winograd_bias_rows))
+        return hit[1]
+
+    def _pack_weights(self, train, wino=None):
+        """wino: the route of the forward this is for (None: a prefetch -- the most recent forward's shape)."""
         pk = self._packed
         if pk is None:
             pk = _Bufs()
@@ -476,7 +473,9 @@ class WesupEngine:
                       torch.empty(1024, 1024, dtype=torch.float32, device=self.device),
                       torch.empty(1024, self.D, dtype=torch.float32, device=self.device)]
             self._packed = pk
-        wino = list(self._route) if self._route is not None else self.route(4, 480, 480)
+        if wino is None:
+            wino = self._route_of(*(self._last_shape or self.BENCH_SHAPE))
+        wino = list(wino)
         if self._prefetched == train and pk.wino == wino:     # prefetch_weights() already queued exactly this for the current step
             self._prefetched = None
             return pk
@@ -551,10 +550,6 @@ class WesupEngine:
                 pk.bwd_ready = True
         return pk
 
-    def _wino(self, l):
-        """m of the Winograd domain layer l runs in at the current shape (0: implicit GEMM)."""
-        return self._route[l]
-
     def prefetch_weights(self, train=True):
         """Queue the weight repacking of the coming forward now (side stream, behind everything queued so far, i.e.
         behind the optimiser step).  The parameters must not change between this call and the forward."""
@@ -569,6 +564,61 @@ class WesupEngine:
         return self._OnSide(self)
 
     # ------------------------------------------------------------------ forward
+    @staticmethod
+    def _input_of(b, l, L):
+        """The tensor layer l's conv (forward and weight gradient) reads, by the plan's name for it."""
+        return b.x0 if L.src == 'x0' else getattr(b, L.src)[l - 1]
+
+    def _side_2d(self, b, l, fm2d):
+        """Layer l's side output as a (pixels, C/2) matrix: its own buffer, or (unfused, full resolution) its slice of fm."""
+        s_l = self._side_out(b, l)
+        co = CONV_CH[l][1]
+        return fm2d[:, SIDE_OFF[l]:SIDE_OFF[l] + co // 2] if s_l is None else s_l.view(-1, co // 2)
+
+    def _side_fwd(self, b, meta, l, L, fm2d):
+        """Side branch of layer l: 1x1 conv on the pre-ReLU tap, then either the fused upsample+scatter-mean straight into the
+        superpixel feature slice, or upsample into fm's channel slice (commuted: the pooling first, the 1x1 conv on its rows)."""
+        B, H, W = b.shape
+        Kmax = b.sp_in.shape[1]
+        co, h, w, off = L.co, L.h, L.w, SIDE_OFF[l]
+        p, T = self.p, self.timer
+        ws = p[f'side_conv{off}.weight'].view(co // 2, co)
+        grp = b.groups[L.group] if L.group is not None else None
+        s_l = None if L.commuted else self._side_out(b, l)       # (None too where, unfused, the side conv writes its slice of fm)
+        with self._OnSide(self):
+            if ('side_fwd_shallow' in self._diag_skip and grp is None) or ('side_fwd_deep' in self._diag_skip and grp is not None):
+                pass                     # timing-only diagnostic: sp_in keeps an earlier step's slice
+            elif L.commuted:
+                if b.ybar[l] is None:
+                    b.ybar[l] = torch.empty(B, Kmax, co, dtype=torch.float32, device=self.device)
+                tok = T.begin('sp_pool_up_fwd')          # (commuted layers are the gather layers: no interpolation matrix)
+                ops.sp_pool_upsample_fwd(b.y[l], meta, b.ybar[l], 0)
+                T.end(tok, 4.0 * B * (h * w * co + H * W + Kmax * co))
+                tok = T.begin('side_fwd')
+                ops.gemm_nt(b.ybar[l].view(B * Kmax, co), ws, p[f'side_conv{off}.bias'],
+                            out=b.sp_in.view(B * Kmax, FM_CHANNELS)[:, off:off + co // 2])
+                T.end(tok, 2.0 * B * Kmax * co * (co // 2))
+            elif not L.side_in_conv:
+                tok = T.begin('side_fwd')
+                ops.gemm_nt(b.y[l].view(B * h * w, co), ws, p[f'side_conv{off}.bias'], out=self._side_2d(b, l, fm2d))
+                T.end(tok, 2.0 * B * h * w * co * (co // 2))
+            if L.commuted or ('side_fwd_deep' in self._diag_skip and grp is not None):
+                pass
+            elif grp is not None:
+                if l == grp.layers[-1]:        # all side outputs of this resolution are in: sp_in slice = Wm . s
+                    tok = T.begin('sp_pool_mat_fwd')
+                    ops.gemm_tn_batched(grp.WmT, grp.s.view(B, grp.h * grp.w, grp.C), b.sp_in[:, :, grp.off:grp.off + grp.C],
+                                        ws_tag='side')
+                    T.end(tok, 2.0 * B * Kmax * grp.h * grp.w * grp.C)
+            elif self.fuse_pool_fwd:
+                tok = T.begin('sp_pool_up_fwd')
+                ops.sp_pool_upsample_fwd(s_l, meta, b.sp_in, off)
+                T.end(tok, 4.0 * B * (h * w * (co // 2) + H * W + Kmax * (co // 2)))
+            elif s_l is not None:
+                tok = T.begin('upsample_fwd')
+                ops.upsample_fwd(s_l, b.fm, off)
+                T.end(tok, 4.0 * B * H * W * (co // 2))
+
     def forward(self, img, meta, train=True, need_paint=True, head=True):
         """img (B,3,H,W) fp32 on the GPU, meta = ops.sp_preprocess(...).  Returns (feats, sp_pred, pred)
         shaped (B,Kmax,D), (B,Kmax,2), (B,H,W); buffers are reused by the next call of the same shape."""
@@ -580,8 +630,9 @@ class WesupEngine:
                                'one process per GPU (torch.cuda.set_device) -- launches would go to the wrong device')
         b = self._get_bufs(B, H, W, Kmax, train)
         self._last = b
-        self._route = self.route(B, H, W)
-        pk = self._pack_weights(train)
+        self._last_shape = (B, H, W)
+        plan = self._plan(b, train, self._route_of(B, H, W))
+        pk = self._pack_weights(train, plan.route)
         p = self.p
         T = self.timer
         ops.pack_input(img, b.x0)
@@ -594,135 +645,63 @@ class WesupEngine:
                 T.end(tok, 0.0)
         fused = self.fuse_pool_fwd
         pending_side = None              # the side-branch work of the previous layer, when it is queued behind this layer's transform
-        cur, cur_relu = b.x0, False      # the layer's input tensor, and whether its ReLU is still to be applied on load
-        b.x_in, b.x_relu = [None] * 13, [False] * 13
-        b.wino_fwd = list(self._route)
-        b.relu_stored = all(b.yr_wanted[l] for l in range(12) if not POOL_AFTER[l])
         b.fm_valid = not fused
         fm2d = None if fused else b.fm.view(B * H * W, FM_CHANNELS)
-        for l, (ci, co) in enumerate(CONV_CH):
-            h, w = b.dims[l]
-            idx, off = CONV_IDX[l], SIDE_OFF[l]
+        for l, L in enumerate(plan.layers):
             if l == 0 and pk.ready0:
                 ops.sync_wait(self.SLOT_W0)
             if l == 1 and pk.ready:
                 ops.sync_wait(self.SLOT_W)
-            ws = p[f'side_conv{off}.weight'].view(co // 2, co)
-            commute = self._commuted(b, l)
-            b.s_valid[l] = not commute
-            # unfused, full resolution: the side conv writes its slice of fm directly
-            s_l = None if commute else self._side_out(b, l)
-            s2d = None if commute else (fm2d[:, off:off + co // 2] if s_l is None else s_l.view(B * h * w, co // 2))
-            # optional: the side conv of the four widest layers (64 / 128 channels at 480^2 / 240^2: the y re-read is
-            # 236 / 118 MB) in the conv's epilogue, where the output tile sits in LDS anyway
-            side_in_conv = self.fuse_side_fwd and co <= 128 and not self._wino(l) and not commute
-            b.x_in[l], b.x_relu[l] = cur, cur_relu
-            # The ReLU'd copy of this layer's output exists for the next layer's 9-tap re-reads and its weight gradient.
-            # A Winograd-domain consumer reads its input once (input transform) and its weight gradient reads the kept V:
-            # then the copy is not written at all and the transform applies the ReLU while loading y.
-            yr = None
-            if b.yr_wanted[l] and not (l < 12 and self._wino(l + 1) and (self.wgrad_winograd or not train)):
+            ci, co, h, w, m = L.ci, L.co, L.h, L.w, L.m
+            idx = CONV_IDX[l]
+            b.s_valid[l] = not L.commuted
+            x = self._input_of(b, l, L)
+            yr = bits_out = code_out = None
+            if L.write_yr:
                 if b.yr[l] is None:
                     b.yr[l] = torch.empty(B, h, w, co, dtype=torch.float32, device=self.device)
                 yr = b.yr[l]
-            m = self._wino(l)
-            bits_out = code_out = None
-            if l >= 1:
-                b.mbits_ok[l - 1] = False
-            b.pcode_ok[l] = False
-            if train and self.compact_masks and m == 4:
-                # sign bits of y_{l-1}: this layer's input transform reads it (pre-ReLU, not pooled) and this layer's input
-                # gradient is the consumer (one-kernel route: product co -> ci)
-                tiles = ops.winograd_tiles(B, h, w, 4)
-                if l >= 1 and cur is b.y[l - 1] and cur_relu and ops.winograd_fused_supported(co, ci, 4, tiles) == 2:
-                    if b.mbits[l - 1] is None:
-                        b.mbits[l - 1] = torch.empty(B, h, w, ci // 4, dtype=torch.uint8, device=self.device)
-                    bits_out = b.mbits[l - 1]
-                    b.mbits_ok[l - 1] = True
-                # pooling codes of y_l: this layer's pooling epilogue writes them, the input gradient of layer l + 1 (through
-                # the max-pool backward, one-kernel route) reads them
-                if (POOL_AFTER[l] and l < 12 and yr is None and self.fuse_unpool and self._wino(l + 1) == 4
-                        and ops.winograd_fused_supported(ci, co, 4, tiles) >= 1
-                        and ops.winograd_fused_supported(CONV_CH[l + 1][1], CONV_CH[l + 1][0], 4,
-                                                         ops.winograd_tiles(B, h // 2, w // 2, 4)) == 2):
-                    if b.pcode[l] is None:
-                        b.pcode[l] = torch.empty(B, h // 2, w // 2, co // 4, dtype=torch.int16, device=self.device)
-                    code_out = b.pcode[l]
-                    b.pcode_ok[l] = True
+            if L.write_bits:
+                if b.mbits[l - 1] is None:
+                    b.mbits[l - 1] = torch.empty(B, h, w, ci // 4, dtype=torch.uint8, device=self.device)
+                bits_out = b.mbits[l - 1]
+            if L.write_codes:
+                if b.pcode[l] is None:
+                    b.pcode[l] = torch.empty(B, h // 2, w // 2, co // 4, dtype=torch.int16, device=self.device)
+                code_out = b.pcode[l]
             if m:
                 vshape = (ops.winograd_positions(m), ops.winograd_tiles(B, h, w, m), ci)
-                if train and (b.V[l] is None or b.V[l].shape != vshape):      # the transformed input, kept for the weight gradient
+                if L.keep_v and (b.V[l] is None or b.V[l].shape != vshape):      # the transformed input, kept for the weight gradient
                     b.V[l] = torch.empty(vshape, dtype=torch.float32, device=self.device)
                 # timed as 'winograd_gemm' (executed MFMA FLOPs: 4/9 resp. 1/4 of the direct form's) + 'winograd_transform'
                 # (bytes).  (An m x m output tile holds whole windows of the max-pool behind conv2_2 / conv3_3 / conv4_3: the
                 # output transform writes the pooled tensor too and the max-pool launch below is skipped)
                 after, pending_side = pending_side, None
-                ops.conv3x3_fwd_winograd(cur, pk.uf[l], p[f'backbone.{idx}.bias'], relu_in=cur_relu, out=b.y[l],
-                                         out_relu=yr, v_keep=b.V[l] if train else None, ws_tag='wino_main', timer=T,
-                                         out_pool=b.yp[l] if POOL_AFTER[l] else None, pool_relu=b.relu_stored, m=m,
+                ops.conv3x3_fwd_winograd(x, pk.uf[l], p[f'backbone.{idx}.bias'], relu_in=L.relu_in, out=b.y[l],
+                                         out_relu=yr, v_keep=b.V[l] if L.keep_v else None, ws_tag='wino_main', timer=T,
+                                         out_pool=b.yp[l] if L.pool else None, pool_relu=plan.relu_stored, m=m,
                                          relu_bits_out=bits_out, pool_code_out=code_out, after_transform=after)
             else:
                 if pending_side is not None:
                     pending_side()
                     pending_side = None
+                side = None
+                if L.side_in_conv:       # the side conv of the widest layers in the conv's epilogue, where the output tile sits in LDS anyway
+                    side = (p[f'side_conv{SIDE_OFF[l]}.weight'].view(co // 2, co), p[f'side_conv{SIDE_OFF[l]}.bias'],
+                            self._side_2d(b, l, fm2d))
                 tok = T.begin('conv3x3_fwd')
-                ops.conv3x3_fwd(cur, pk.wf[l], p[f'backbone.{idx}.bias'], co, relu_in=cur_relu, out=b.y[l], out_relu=yr,
-                                side=(ws, p[f'side_conv{off}.bias'], s2d) if side_in_conv else None)
-                T.end(tok, 2.0 * B * h * w * co * ((3 if l == 0 else ci) * 9 + (co // 2 if side_in_conv else 0)))
-            # side branch of this layer: 1x1 conv on the pre-ReLU tap, then either the fused upsample+scatter-mean
-            # straight into the superpixel feature slice, or upsample into fm's channel slice
-            def side_work(l=l, ci=ci, co=co, h=h, w=w, off=off, ws=ws, commute=commute, s_l=s_l, s2d=s2d, side_in_conv=side_in_conv):
-              with self._OnSide(self):
-                grp = b.groups[b.group_of[l]] if b.group_of[l] is not None else None
-                if ('side_fwd_shallow' in self._diag_skip and grp is None) or ('side_fwd_deep' in self._diag_skip and grp is not None):
-                    pass                     # timing-only diagnostic: sp_in keeps an earlier step's slice
-                elif commute:
-                    if b.ybar[l] is None:
-                        b.ybar[l] = torch.empty(B, Kmax, co, dtype=torch.float32, device=self.device)
-                    tok = T.begin('sp_pool_up_fwd')          # (commuted layers are the gather layers: no interpolation matrix)
-                    ops.sp_pool_upsample_fwd(b.y[l], meta, b.ybar[l], 0)
-                    T.end(tok, 4.0 * B * (h * w * co + H * W + Kmax * co))
-                    tok = T.begin('side_fwd')
-                    ops.gemm_nt(b.ybar[l].view(B * Kmax, co), ws, p[f'side_conv{off}.bias'],
-                                out=b.sp_in.view(B * Kmax, FM_CHANNELS)[:, off:off + co // 2])
-                    T.end(tok, 2.0 * B * Kmax * co * (co // 2))
-                elif not side_in_conv:
-                    tok = T.begin('side_fwd')
-                    ops.gemm_nt(b.y[l].view(B * h * w, co), ws, p[f'side_conv{off}.bias'], out=s2d)
-                    T.end(tok, 2.0 * B * h * w * co * (co // 2))
-                if commute or ('side_fwd_deep' in self._diag_skip and grp is not None):
-                    pass
-                elif b.group_of[l] is not None:
-                    g = b.groups[b.group_of[l]]
-                    if l == g.layers[-1]:        # all side outputs of this resolution are in: sp_in slice = Wm . s
-                        tok = T.begin('sp_pool_mat_fwd')
-                        ops.gemm_tn_batched(g.WmT, g.s.view(B, g.h * g.w, g.C), b.sp_in[:, :, g.off:g.off + g.C],
-                                            ws_tag='side')
-                        T.end(tok, 2.0 * B * Kmax * g.h * g.w * g.C)
-                elif fused:
-                    tok = T.begin('sp_pool_up_fwd')
-                    ops.sp_pool_upsample_fwd(s_l, meta, b.sp_in, off)
-                    T.end(tok, 4.0 * B * (h * w * (co // 2) + H * W + Kmax * (co // 2)))
-                elif s_l is not None:
-                    tok = T.begin('upsample_fwd')
-                    ops.upsample_fwd(s_l, b.fm, off)
-                    T.end(tok, 4.0 * B * H * W * (co // 2))
+                ops.conv3x3_fwd(x, pk.wf[l], p[f'backbone.{idx}.bias'], co, relu_in=L.relu_in, out=b.y[l], out_relu=yr, side=side)
+                T.end(tok, 2.0 * B * h * w * co * ((3 if l == 0 else ci) * 9 + (co // 2 if L.side_in_conv else 0)))
             # Queued now, the memory-bound pooling of y_l would run beside the equally memory-bound input transform of layer
             # l + 1 (both read y_l); deferred until that transform has been queued (ops: after_transform), it runs beside the
             # layer's products instead -- a memory-bound kernel next to an MFMA-bound one.
             # (the deep layers too: deferring only the memory-bound shallow ones measured 0.03 ms worse)
-            if self.two_streams and l < 12 and self._wino(l + 1):
-                pending_side = side_work
+            if L.defer_side:
+                pending_side = lambda l=l, L=L: self._side_fwd(b, meta, l, L, fm2d)
             else:
-                side_work()
-            if POOL_AFTER[l]:
-                if not self._wino(l):
-                    ops.maxpool2_fwd(b.y[l], b.yp[l], relu=b.relu_stored)
-                cur, cur_relu = b.yp[l], not b.relu_stored
-            elif yr is not None:
-                cur, cur_relu = yr, False
-            else:
-                cur, cur_relu = b.y[l], True
+                self._side_fwd(b, meta, l, L, fm2d)
+            if L.pool and not m:
+                ops.maxpool2_fwd(b.y[l], b.yp[l], relu=plan.relu_stored)
         self._join_side()
         if train:
             self._pack_weights_bwd(pk)
@@ -793,8 +772,8 @@ class WesupEngine:
         # autograd in the reference then never computes their weight gradients nor any activation gradient that only
         # they would need.  Same here: a frozen layer has no wgrad launch, and below the lowest trainable layer there
         # is no dgrad chain and no side-conv dgrad at all (the side convs' own wgrads only need ds_l and y_l).
-        trainable = [not {f'backbone.{i}.weight', f'backbone.{i}.bias'} <= self.frozen for i in CONV_IDX]
-        lowest = min([l for l in range(13) if trainable[l]], default=13)
+        plan = self._plan(b, True, b.plans[True][1].route)       # (the forward's routing; the switches as they are now)
+        Ls, lowest = plan.layers, plan.lowest
         # ---- classifier + fc_layers.  Between the last forward conv and the first dgrad the step has ONE chain of small
         # kernels (head forward, loss, head backward, pooling backward of the deepest layers: ~1.7 ms in which the chip
         # is mostly idle), so only what that chain needs stays on it: the input-gradient GEMMs dfeat -> dh2 -> dh1 -> gsp.
@@ -866,41 +845,18 @@ class WesupEngine:
                     b.dybar[l] = torch.empty(B, Kmax, co, dtype=torch.float32, device=self.device)
                 tok = T.begin('side_bwd')
                 ops.gemm_nt(gsp2d[:, off:off + co // 2], pk.sideT[l], None, out=b.dybar[l].view(R, co))
-                if gat[l]:      # gathered per pixel by the epilogue of layer l + 1's input gradient: rows divided by their areas here, once
+                if Ls[l].gather:      # gathered per pixel by the epilogue of layer l + 1's input gradient: rows divided by their areas here, once
                     ops.scale_rows_by_area(b.dybar[l], meta.area_new)
                 T.end(tok, 2.0 * R * co * (co // 2))
             tok = T.begin('upsample_bwd')
             if (h, w) == (H, W) or sum(CONV_CH[l][1] for l in ls) > 768:
                 for l in ls:
-                    if not gat[l]:           # (gat: the dgrad epilogue of layer l + 1 gathers from dYbar_l itself)
+                    if not Ls[l].gather:           # (the dgrad epilogue of layer l + 1 gathers from dYbar_l itself)
                         ops.upsample_bwd_fused(b.dybar[l], meta.new_row, meta.area_new, H, W, 0, h, w, CONV_CH[l][1], out=b.G[l])
             else:
                 ops.upsample_bwd_fused_group([b.dybar[l] for l in ls], meta.new_row, meta.area_new, H, W, h, w,
                                              [b.G[l] for l in ls])
-            T.end(tok, 4.0 * B * sum(h * w * CONV_CH[l][1] + H * W + Kmax * CONV_CH[l][1] for l in ls if not gat[l]))
-
-        # native-resolution commuted layers whose G is written by the dgrad epilogue of the layer above (gather form)
-        gat = [False] * 13
-        if self.gather_side_grad:
-            for l in range(0, 12):
-                ci1, co1 = CONV_CH[l + 1]
-                if (b.group_of[l] is None and self._commuted(b, l) and b.dims[l] == (H, W) and l >= lowest
-                        and b.wino_fwd[l + 1] == 4
-                        and ops.winograd_fused_supported(co1, ci1, 4, ops.winograd_tiles(B, *b.dims[l + 1], 4)) == 2
-                        and (not POOL_AFTER[l] or (self.fuse_unpool and H % 2 == 0 and W % 2 == 0))):
-                    gat[l] = True
-
-        def commuted_runs():
-            """The commuted layers whose G the dgrad chain needs, deepest first, in runs of (at most three) layers that share a
-            resolution."""
-            runs = []
-            for l in range(12, -1, -1):
-                if b.group_of[l] is None and self._commuted(b, l) and l >= lowest:
-                    if runs and b.dims[runs[-1][0]] == b.dims[l] and len(runs[-1]) < 3:
-                        runs[-1].append(l)
-                    else:
-                        runs.append([l])
-            return runs
+            T.end(tok, 4.0 * B * sum(h * w * CONV_CH[l][1] + H * W + Kmax * CONV_CH[l][1] for l in ls if not Ls[l].gather))
 
         def queue_shallow():
             # ... at the head of the wgrad stream, which has nothing to do until the first weight gradient is queued.
@@ -910,15 +866,13 @@ class WesupEngine:
             aux = self._wg()
             self._edge(torch.cuda.current_stream(), aux)
             with self._On(aux):
-                for ls in commuted_runs():
+                for ls in plan.runs:
                     commuted_G(ls)
                     ops.sync_record(self.SLOT_G + ls[0])
                     for l in ls:
                         g_ready[l] = self.SLOT_G + ls[0]
                 for l in range(12, -1, -1):
-                    if b.group_of[l] is None and self._commuted(b, l):
-                        pass
-                    elif b.group_of[l] is None:
+                    if Ls[l].group is None and not Ls[l].commuted:
                         h, w = b.dims[l]
                         tok = T.begin('upsample_bwd')
                         ops.upsample_bwd_fused(b.gsp, meta.new_row, meta.area_new, H, W, SIDE_OFF[l], h, w,
@@ -930,7 +884,7 @@ class WesupEngine:
                         ops.sync_record(ds_ready[l])
 
         # the shallow layers' side-branch gradients: at the head of the weight-gradient stream
-        if self.two_streams and self.fuse_pool_bwd:
+        if plan.shallow_first:
             queue_shallow()
         ds2ds = [None] * 13
 
@@ -942,7 +896,7 @@ class WesupEngine:
             off = SIDE_OFF[l]
             P = B * h * w
             tok = T.begin('side_bwd')
-            if self._commuted(b, l):         # dW = g_slice^T . Ybar, db = column sums of g_slice (the rows of upsample+mean sum to 1)
+            if Ls[l].commuted:         # dW = g_slice^T . Ybar, db = column sums of g_slice (the rows of upsample+mean sum to 1)
                 ops.gemm_tn(gsp2d[:, off:off + co // 2], b.ybar[l].view(R, co), out=g[f'side_conv{off}.weight'].view(co // 2, co),
                             ws_tag='side', colsum=g[f'side_conv{off}.bias'])
                 T.end(tok, 2.0 * R * co * (co // 2))
@@ -960,15 +914,15 @@ class WesupEngine:
                 h, w = b.dims[l]
                 off = SIDE_OFF[l]
                 P = B * h * w
-                if self._commuted(b, l):
-                    if not self.two_streams and l >= lowest:     # single-stream schedule: not queued above
-                        for ls in commuted_runs():
+                if Ls[l].commuted:
+                    if not self.two_streams:         # single-stream schedule: not queued above
+                        for ls in plan.runs:
                             if ls[0] == l:
                                 commuted_G(ls)
                     continue
                 self._side_grad(b, l)            # (allocated on first use; a group's buffer serves all its layers)
-                if b.group_of[l] is not None:
-                    grp = b.groups[b.group_of[l]]
+                if Ls[l].group is not None:
+                    grp = b.groups[Ls[l].group]
                     if l == grp.layers[-1]:      # ds of every layer of this resolution at once: ds = Wm^T . gsp slice
                         tok = T.begin('upsample_mat_bwd')
                         ops.gemm_tn_batched(grp.Wm, b.gsp[:, :, grp.off:grp.off + grp.C],
@@ -991,7 +945,6 @@ class WesupEngine:
                     ds2d = b.ds[l].view(P, co // 2)
                 T.end(tok, 4.0 * B * ((h * w * (co // 2) + H * W + Kmax * (co // 2)) if self.fuse_pool_bwd else H * W * (co // 2)))
                 ds2ds[l] = ds2d
-                grp = b.groups[b.group_of[l]] if b.group_of[l] is not None else None
                 if l >= lowest:              # G_l is only needed by backbone layers that train
                     tok = T.begin('side_bwd')
                     ops.gemm_nt(ds2d, pk.sideT[l], None, out=b.G[l].view(P, co))
@@ -1001,12 +954,8 @@ class WesupEngine:
                         ops.sync_record(g_ready[l])
             # The side convs' own weight gradients are parameter gradients nobody waits for before the optimiser, while the
             # dgrad chain waits for every G_l: all the G_l first (13 GEMMs), the weight gradients behind them.
-            late_at = self._DEEP_SIDE_WGRAD_AT if self.two_streams else None
-            if late_at is not None and not (lowest < late_at <= 12):      # the main loop below never reaches such a layer
-                late_at = None
-            late_side = [l for l in range(12, -1, -1) if late_at is not None and b.group_of[l] is not None]
             for l in range(12, -1, -1):
-                if l not in late_side:
+                if l not in plan.late_side:
                     side_wgrad(l)
         # ---- main path, conv5_3 down to conv1_1.  The dgrad chain stays on the caller's stream; each layer's wgrad
         # (which only produces parameter gradients) goes to a third stream so that it fills the tails of the dgrad
@@ -1014,69 +963,55 @@ class WesupEngine:
         main = torch.cuda.current_stream()
         wg = self._wg() if self.two_streams else None
         for l in range(12, lowest - 1, -1):
-            ci, co = CONV_CH[l]
-            h, w = b.dims[l]
+            L = Ls[l]
+            ci, co, h, w = L.ci, L.co, L.h, L.w
             idx = CONV_IDX[l]
             if g_ready[l] is not None:
                 ops.sync_wait(g_ready[l], main.cuda_stream)
-            if late_side and l == late_at:
+            if plan.late_side and l == plan.late_at:
                 # the deep layers' side-conv weight gradients (TN products with K = pixels: MFMA-bound) only now, beside the
                 # memory-bound transforms and 64-channel products of the last layers instead of beside conv5 / conv4
                 with self._OnSide(self):
-                    for ls_ in late_side:
+                    for ls_ in plan.late_side:
                         side_wgrad(ls_)
-                late_side = []
-            x_in, relu_x = b.x_in[l], b.x_relu[l]      # what the forward of this layer read
-            # one pass over G_l for both consumers (F(4x4) input gradient and weight gradient)
-            dual = (self.dual_transform and b.wino_fwd[l] == 4 and l > lowest and trainable[l] and self.wgrad_winograd
-                    and b.V[l] is not None and 'wgrad' not in self._diag_skip and ops.winograd_bias_rows(B, h, w, co) > 0
-                    and not (POOL_AFTER[l - 1] and not self.fuse_unpool))
             v_dy = None
-            if dual:
+            if L.dual:      # one pass over G_l for both consumers (F(4x4) input gradient and weight gradient)
                 Tl = ops.winograd_tiles(B, h, w, 4)
                 if b.dV is None:
                     b.dV = torch.empty(max(36 * ops.winograd_tiles(B, *b.dims[i], 4) * CONV_CH[i][1] for i in range(1, 13)),
                                        dtype=torch.float32, device=self.device)
                 if b.dM[l] is None:
                     b.dM[l] = torch.empty(36, Tl, co, dtype=torch.float32, device=self.device)
-                    b.bpart[l] = torch.empty(ops.winograd_bias_rows(B, h, w, co), co, dtype=torch.float32, device=self.device)
+                    b.bpart[l] = torch.empty(L.bias_rows, co, dtype=torch.float32, device=self.device)
                 v_dy = b.dV[:36 * Tl * co].view(36, Tl, co)
                 tok = T.begin('winograd_transform')
                 if 'dual' not in self._diag_skip:
                     ops.winograd_dual_transform(b.G[l], v_dy, b.dM[l], b.bpart[l])
                 T.end(tok, 4.0 * (B * h * w + 2 * 36 * Tl) * co)
+
             def wgrad(ws_tag):
                 tok = T.begin('conv3x3_wgrad')
                 dw, db = g[f'backbone.{idx}.weight'], g[f'backbone.{idx}.bias']
-                mw = b.wino_fwd[l]                             # this forward went through the Winograd domain: its V was kept
-                v_pre = b.V[l] if mw else None
-                if dual:
+                v_pre = b.V[l] if L.m else None               # this forward went through the Winograd domain: its V was kept
+                if L.wgrad == 'pre':
                     ops.conv3x3_wgrad_winograd_pre(v_pre, b.dM[l], b.bpart[l], B, h, w, dw, db, ws_tag=ws_tag)
                     T.end(tok, 2.0 * 36 * ops.winograd_tiles(B, h, w, 4) * ci * co)
-                    ready([f'backbone.{idx}.weight', f'backbone.{idx}.bias'])
-                    return
-                # the forward's kept V decides; without one (direct forward) only the layers where a transform pass of
-                # its own still pays
-                if self.wgrad_winograd and (v_pre is not None or (ci >= self.WINOGRAD_MIN_CI and co >= self.WINOGRAD_MIN_CO)):
-                    mw = mw or self.WINOGRAD_TILE
-                    ops.conv3x3_wgrad_winograd(x_in, b.G[l], relu_in=relu_x, dw=dw, db=db, ws_tag=ws_tag, v_pre=v_pre, m=mw)
+                elif L.wgrad in ('winograd_v', 'winograd'):
+                    mw = L.wgrad_m
+                    ops.conv3x3_wgrad_winograd(self._input_of(b, l, L), b.G[l], relu_in=L.relu_in, dw=dw, db=db, ws_tag=ws_tag,
+                                               v_pre=v_pre, m=mw)
                     # the FLOPs the MFMA pipe executes: (m+2)^2 positions x (m x m tiles) instead of 9 taps x pixels
                     T.end(tok, 2.0 * ops.winograd_positions(mw) * ops.winograd_tiles(B, h, w, mw) * ci * co)
                 else:
-                    ops.conv3x3_wgrad(x_in, b.G[l], ci, relu_in=relu_x, dw=dw, db=db, ws_tag=ws_tag)
+                    ops.conv3x3_wgrad(self._input_of(b, l, L), b.G[l], ci, relu_in=L.relu_in, dw=dw, db=db, ws_tag=ws_tag)
                     T.end(tok, 2.0 * B * h * w * ci * co * 9)
                 ready([f'backbone.{idx}.weight', f'backbone.{idx}.bias'])
-            # With its operands ready (dual transform) a weight gradient can start any time.  Queued behind the layer's input
-            # gradient instead of in front of it, its TN products run beside the NEXT layer's (memory-bound) transform rather
-            # than beside this layer's products: 9.35 -> 9.20 ms.
-            late_wgrad = wg is not None and dual and l > lowest + self._WGRAD_EARLY_LAYERS
-            if l == lowest and wg is not None and self.on_tail is not None and trainable[l]:
+
+            if l == lowest and wg is not None and self.on_tail is not None and L.trainable:
                 # every gradient but this layer's is queued (conv and fc weight gradients on wg, the side convs' on the side
                 # stream): the step runner puts the bulk of the optimiser step on wg here, beside the last input gradient
                 self.on_tail(wg, [f'backbone.{idx}.weight', f'backbone.{idx}.bias'])
-            if not trainable[l] or 'wgrad' in self._diag_skip:
-                pass
-            elif late_wgrad:
+            if L.wgrad is None or L.wgrad_late:
                 pass
             elif wg is not None:
                 self._edge(main, wg)                       # G_l is final here
@@ -1084,42 +1019,36 @@ class WesupEngine:
                     wgrad('wgrad')
             else:
                 wgrad('default')
-            if l > lowest:
+            if L.dgrad is not None:
                 if g_ready[l - 1] is not None:
                     ops.sync_wait(g_ready[l - 1], main.cuda_stream)
-                unpooled = False
-                mbits = b.mbits[l - 1] if (self.compact_masks and b.mbits_ok[l - 1]) else None
-                pcode = b.pcode[l - 1] if (self.compact_masks and b.pcode_ok[l - 1]) else None
-                if gat[l - 1]:
-                    pooled = POOL_AFTER[l - 1]
+                pooled = Ls[l - 1].pool
+                mbits = b.mbits[l - 1] if L.write_bits else None
+                pcode = b.pcode[l - 1] if Ls[l - 1].write_codes else None
+                if L.dgrad == 'gather':
                     ops.conv3x3_dgrad_winograd_gather(b.G[l], pk.ud[l], b.dybar[l - 1], meta.new_row, None, out=b.G[l - 1],
                                                       mask_src=None if pooled else b.y[l - 1],
                                                       unpool_src=b.y[l - 1] if pooled else None, ws_tag='wino_main', timer=T,
                                                       mask_bits=None if pooled else mbits, unpool_code=pcode if pooled else None,
                                                       v_pre=v_dy)
-                    unpooled = True
-                elif b.wino_fwd[l]:
-                    if POOL_AFTER[l - 1] and self.fuse_unpool and b.wino_fwd[l] == 4:
-                        ops.conv3x3_dgrad_winograd_unpool(b.G[l], pk.ud[l], b.y[l - 1], b.G[l - 1], ws_tag='wino_main', timer=T,
-                                                          unpool_code=pcode, v_pre=v_dy)
-                        unpooled = True
-                    elif POOL_AFTER[l - 1]:
-                        ops.conv3x3_dgrad_winograd(b.G[l], pk.ud[l], out=b.dxp[l - 1], ws_tag='wino_main', timer=T,
-                                                   m=b.wino_fwd[l], v_pre=v_dy)
-                    else:
-                        ops.conv3x3_dgrad_winograd(b.G[l], pk.ud[l], mask_src=None if mbits is not None else b.y[l - 1], out=b.G[l - 1],
-                                                   accumulate=True, ws_tag='wino_main', timer=T, m=b.wino_fwd[l], mask_bits=mbits,
-                                                   v_pre=v_dy)
+                elif L.dgrad == 'unpool':
+                    ops.conv3x3_dgrad_winograd_unpool(b.G[l], pk.ud[l], b.y[l - 1], b.G[l - 1], ws_tag='wino_main', timer=T,
+                                                      unpool_code=pcode, v_pre=v_dy)
+                elif L.dgrad == 'winograd' and pooled:
+                    ops.conv3x3_dgrad_winograd(b.G[l], pk.ud[l], out=b.dxp[l - 1], ws_tag='wino_main', timer=T, m=L.m, v_pre=v_dy)
+                elif L.dgrad == 'winograd':
+                    ops.conv3x3_dgrad_winograd(b.G[l], pk.ud[l], mask_src=None if mbits is not None else b.y[l - 1], out=b.G[l - 1],
+                                               accumulate=True, ws_tag='wino_main', timer=T, m=L.m, mask_bits=mbits, v_pre=v_dy)
                 else:
                     tok = T.begin('conv3x3_dgrad')
-                    if POOL_AFTER[l - 1]:
+                    if pooled:
                         ops.conv3x3_dgrad(b.G[l], pk.wd[l], ci, out=b.dxp[l - 1])
                     else:
                         ops.conv3x3_dgrad(b.G[l], pk.wd[l], ci, mask_src=b.y[l - 1], out=b.G[l - 1], accumulate=True)
                     T.end(tok, 2.0 * B * h * w * ci * co * 9)
-                if POOL_AFTER[l - 1] and not unpooled:
+                if L.pool_bwd:
                     ops.maxpool2_bwd(b.y[l - 1], b.dxp[l - 1], b.G[l - 1], accumulate=True)
-                if late_wgrad and trainable[l] and 'wgrad' not in self._diag_skip:
+                if L.wgrad_late:
                     self._edge(main, wg)
                     with self._On(wg):
                         wgrad('wgrad')

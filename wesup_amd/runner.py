@@ -140,7 +140,6 @@ class StepRunner:
         if trainer.kwargs.get('gc_freeze', False):
             freeze_startup_objects()
         self._cuts = None
-        self._routes = {}
 
     # ------------------------------------------------------------------ which iterations take this path
     def parse(self, phase, data):
@@ -176,13 +175,14 @@ class StepRunner:
         (a plan holds raw device addresses: replaying it over a freed or re-made buffer corrupts silently)."""
         t, o = self.t, self.t.optimizer
         g = o.param_groups[0]
-        sw = tuple(sorted((k, v) for k, v in vars(eng).items() if isinstance(v, (bool, int, type(None))) and not k.startswith('_')
-                          and k not in ('buf_generation', 'max_cached_shapes', 'max_cached_pixels')))
+        # what shapes the engine's walk: its plan key (switches, routing result of this shape, the process-wide rule behind the
+        # one-kernel route, frozen parameters, diagnostics), and the rest of its public state a walk reads
+        walk = (eng.plan_key(B, H, W), eng.D, eng.ctx is None, eng.on_grads_ready is None, eng.on_tail is None)
         red = t.reducer
         m = t.model
         pk = eng._packed
         panels = None if pk is None else tuple(0 if u is None else u.data_ptr() for u in list(pk.uf) + list(pk.ud))
-        return (sw, eng.route_fn, type(eng).WINOGRAD_CONV_MIN_CI, type(eng).WINOGRAD_TILE, tuple(sorted(eng._diag_skip)),
+        return (walk, eng.route_fn, type(eng).WINOGRAD_CONV_MIN_CI, type(eng).WINOGRAD_TILE,
                 ops.STREAMK, tuple(sorted(ops.DIAG)),
                 g['lr'], g['momentum'], g['weight_decay'], o.grad_scale, o._first,
                 tuple(p.requires_grad for _, p in t.model._named),
@@ -190,20 +190,10 @@ class StepRunner:
                 bool(t.kwargs.get('enable_propagation')), float(t.kwargs.get('epsilon')), self.fuse_head, self.split_sgd,
                 None if red is None else (id(red), t.world_size, red.bucket_elems, red.force),
                 ops._stream().value,
-                # the engine object itself (model.to(device) re-makes it and restarts buf_generation), the per-shape routing result
-                # and the process-wide rule behind it, the flat parameter / gradient / momentum buffers, the Winograd filter panels
-                id(eng), self._route_of(eng, B, H, W), ops.winograd_fused_min_blocks(),
+                # the engine object itself (model.to(device) re-makes it and restarts buf_generation), the flat parameter / gradient /
+                # momentum buffers, the Winograd filter panels
+                id(eng),
                 m._flat.data_ptr(), m._flat_grad.data_ptr(), o._vflat.data_ptr(), panels)
-
-    def _route_of(self, eng, B, H, W):
-        """eng.route(B, H, W) as a tuple, remembered per (routing rule, shape): thirteen calls of the rule per iteration otherwise."""
-        key = (id(eng), eng.route_fn, eng.conv_winograd, ops.winograd_fused_min_blocks(), B, H, W)
-        r = self._routes.get(key)
-        if r is None:
-            if len(self._routes) > 4 * MAX_STATES:
-                self._routes.clear()
-            r = self._routes[key] = tuple(eng.route(B, H, W))
-        return r
 
     # ------------------------------------------------------------------ the iteration
     def run(self, parsed):
