@@ -521,5 +521,125 @@ def test_the_engine_rebuilds_its_plan_when_its_key_changes_and_only_then(queries
 def test_layer_plan_imports_without_torch():
     code = ('import sys; import wesup_amd.layer_plan as lp; assert "torch" not in sys.modules, "torch imported"; '
             'lp.build((1, 32, 32), lp.groups_for(1, 32, 32, 16, lp.Switches())[1], (0,) + (4,) * 12, lp.Switches(), set(), set(), True, '
-            'lambda *a: 0, lambda *a: 0); assert "torch" not in sys.modules')
+            'lambda *a: 0, lambda *a: 0); assert "torch" not in sys.modules; '
+            'sw = lp.Switches(); gr, go = lp.groups_for(1, 32, 32, 16, sw); '
+            'pl = lp.build((1, 32, 32), go, (0,) + (4,) * 12, sw, set(), set(), True, lambda *a: 2, lambda *a: 3); '
+            't = lp.buffers(pl, gr, 16, 32, lambda R, D: 4096); assert lp.nbytes(t) > lp.nbytes(lp.buffers(pl, gr, 16, 32, 0)) > 0; '
+            'assert {e.name for e in t} >= {"x0", "y", "V", "G", "dV", "dM", "cls_part", "g.Wm"}; assert "torch" not in sys.modules')
     subprocess.run([sys.executable, '-c', code], cwd=ROOT, check=True, timeout=120)
+
+
+def table_bytes(B, H, W, Kmax, train=True):
+    """What a new set of that shape costs under the default switches, from layer_plan alone (the library answers its size queries
+    on the CPU)."""
+    from wesup_amd import _lib
+    lib = _lib.load()
+    sw = lp.Switches()
+    groups, group_of = lp.groups_for(B, H, W, Kmax, sw)
+    plan = lp.build((B, H, W), group_of, lp.route(default_rule(4, 64), True, B, H, W), sw, set(), set(), train,
+                    lambda K, N, m=4, tiles=0: int(lib.wesup_winograd_fused_route(K, N, m, int(tiles))),
+                    lambda *a: int(lib.wesup_winograd_bias_rows(*a)))
+    return lp.nbytes(lp.buffers(plan, groups, Kmax, 32, lambda R, D: int(lib.wesup_classifier_bwd_workspace_bytes(R, D))))
+
+
+def test_a_new_shape_evicts_exactly_when_free_plus_idle_memory_is_below_its_table(queries, monkeypatch):
+    """WesupEngine._memory_short: a new shape is short exactly when free + idle bytes < 1.1 x its table's bytes -- known before
+    any tensor of the set exists, whatever the sets cached so far cost per pixel."""
+    import math
+    import torch
+    from wesup_amd import engine
+
+    def old_set_survives(shape, free, reserved, allocated):
+        eng = engine.WesupEngine({'w': torch.zeros(4)}, {'w': torch.zeros(4)})
+        monkeypatch.setattr(torch.cuda, 'mem_get_info', lambda device=None: (free, 1 << 40))
+        monkeypatch.setattr(torch.cuda, 'memory_reserved', lambda device=None: reserved)
+        monkeypatch.setattr(torch.cuda, 'memory_allocated', lambda device=None: allocated)
+        eng._bufs[(1, 8, 8, 4)] = engine._Bufs()
+        b = eng._get_bufs(*shape, True)
+        assert b.x0 is None and b.y == [None] * 13 and list(eng._bufs)[-1] == shape     # a bare record: nothing allocated yet
+        return (1, 8, 8, 4) in eng._bufs
+
+    n = table_bytes(4, 480, 480, 576)
+    assert 5 << 30 < n < 8 << 30
+    enough = math.ceil(1.1 * n)
+    assert old_set_survives((4, 480, 480, 576), enough, 0, 0)                   # free memory alone
+    assert old_set_survives((4, 480, 480, 576), enough // 2, 3 * enough, 3 * enough - (enough - enough // 2))   # ... with the idle blocks
+    assert not old_set_survives((4, 480, 480, 576), enough // 2, 3 * enough, 3 * enough - (enough - enough // 2) + 1)   # one byte less
+    assert not old_set_survives((4, 480, 480, 576), enough - 1, 0, 0)
+    # many superpixels per pixel: such a set costs more than 16 KiB per pixel -- a per-pixel constant (what the estimate was
+    # before any set had been measured) calls this case "not short"
+    dense = table_bytes(1, 96, 80, 3072)
+    assert dense > 96 * 80 * 16 * 1024
+    assert not old_set_survives((1, 96, 80, 3072), 96 * 80 * 16 * 1024, 0, 0)
+    assert old_set_survives((1, 96, 80, 3072), math.ceil(1.1 * dense), 0, 0)
+    # an evaluation set is sized by the evaluation plan's table
+    ev = table_bytes(4, 480, 480, 576, train=False)
+    assert ev < n // 2
+    eng = engine.WesupEngine({'w': torch.zeros(4)}, {'w': torch.zeros(4)})
+    b = eng._get_bufs(4, 480, 480, 576, False)
+    assert lp.nbytes(eng._table(b, eng._plan(b, False))) == ev and lp.nbytes(eng._table(b, eng._plan(b, True))) == n
+
+
+# ---- The buffer sets the PARENT commit (first-use allocation inside the walks) held, per configuration: after one evaluation
+# forward and after one training step (forward + backward), each on a fresh engine -- every tensor reachable from the set with its
+# name, shape, element type and, for a view, the buffer that owns its storage; the set's bytes (storages counted once); and the
+# names of the buffers that no ops.* call of that walk received.  tests/golden/parent_buffer_sets.json is that recording, taken
+# from the parent the way the decision tables above were; layer_plan.buffers produced none of it.
+# HOW IT WAS TAKEN: by the parent's own engine.py walking forward() / backward() with every ops.* launch replaced by a no-op on
+# the host (what a set holds is decided by host code alone; the library's size / route queries were answered by the built
+# library).  It was NOT taken on an MI355X: no GPU was to be had when this was written.  The GPU test
+# tests/test_buffer_fit_gpu.py checks the same bytes against torch's own storages on the device.
+#
+# DEAD: what the table leaves out of the parent's training set, by configuration -- dxp[l], the input gradient of layer l + 1 at
+# pooled resolution, where that layer has no max-pool backward launch (its input gradient takes the gather / unpool form and
+# writes G[l] itself, or it is at or below the lowest trainable layer and has none).  In the recording none of them is handed to
+# an ops.* call in any of the eleven configurations.  layer -> bytes, per shape.
+DXP = {(4, 480, 480): {1: 4 * 240 * 240 * 64 * 4, 3: 4 * 120 * 120 * 128 * 4, 6: 4 * 60 * 60 * 256 * 4, 9: 4 * 30 * 30 * 512 * 4},
+       (1, 96, 80): {1: 48 * 40 * 64 * 4, 3: 24 * 20 * 128 * 4, 6: 12 * 10 * 256 * 4, 9: 6 * 5 * 512 * 4},
+       (8, 1024, 1024): {1: 8 * 512 * 512 * 64 * 4, 3: 8 * 256 * 256 * 128 * 4, 6: 8 * 128 * 128 * 256 * 4, 9: 8 * 64 * 64 * 512 * 4},
+       (1, 1024, 1024): {1: 512 * 512 * 64 * 4, 3: 256 * 256 * 128 * 4, 6: 128 * 128 * 256 * 4, 9: 64 * 64 * 512 * 4}}
+DEAD = {'c01_default': (1, 3, 6, 9),              # 58 982 400 + 29 491 200 + 14 745 600 + 7 372 800 = 110 592 000 bytes
+        'c02_plain': (),                          # every pooled layer's input gradient is followed by a max-pool backward
+        'c03_plain_unfused': (),
+        'c04_direct': (),
+        'c05_one_stream': (1, 3, 6, 9),
+        'c07a_frozen_to_conv3_3': (1, 3, 6, 9),   # (conv4_1 is the lowest trainable layer: no input gradient at or below it)
+        'c07b_frozen_all': (1, 3, 6, 9),
+        'c08_odd_96x80': (1, 3, 6, 9),            # 491 520 + 245 760 + 122 880 + 61 440 = 921 600 bytes
+        'c09_8x1024': (1, 3, 6, 9),               # 1 006 632 960 bytes
+        'c09b_1x1024': (1, 3, 6, 9),              # 125 829 120 bytes
+        'c10_f2_min128': ()}
+
+
+def table_of(name, queries, train):
+    from wesup_amd import _lib
+    lib = _lib.load()
+    B, H, W, Kmax, _, _, _ = CONFIGS[name]
+    groups, _, plans = plans_of(name, queries)
+    return lp.buffers(plans[0 if train else 1], groups, Kmax, 32, lambda R, D: int(lib.wesup_classifier_bwd_workspace_bytes(R, D)))
+
+
+def set_name(e):
+    return f'groups[{e.layer}].{e.name[2:]}' if e.name.startswith('g.') else e.name if e.layer is None else f'{e.name}[{e.layer}]'
+
+
+@pytest.mark.parametrize('train', [True, False], ids=['train', 'eval'])
+@pytest.mark.parametrize('name', sorted(CONFIGS))
+def test_buffer_table_equals_the_set_the_parent_held(name, train, queries):
+    import json
+    with open(os.path.join(ROOT, 'tests', 'golden', 'parent_buffer_sets.json')) as f:
+        rec = json.load(f)[name]
+    want = rec['train' if train else 'eval']
+    table = table_of(name, queries, train)
+    assert len({set_name(e) for e in table}) == len(table)
+    got = {set_name(e): [list(e.shape), e.dtype, None if e.group is None else f'groups[{e.group}].{e.name}'] for e in table}
+    B, H, W = CONFIGS[name][:3]
+    dead = {f'dxp[{l}]': DXP[(B, H, W)][l] for l in DEAD[name]} if train else {}
+    for n, nbytes in dead.items():        # itemised: in the parent's set, of that size, never handed to an ops.* call
+        shape, dtype, owner = want['bufs'][n]
+        assert owner is None and dtype == 'float32' and 4 * shape[0] * shape[1] * shape[2] * shape[3] == nbytes
+        assert n in rec['train_never_handed_to_ops']
+    assert got == {n: v for n, v in want['bufs'].items() if n not in dead}
+    assert lp.nbytes(table) == want['bytes'] - sum(dead.values())
+    if name == 'c01_default' and train:
+        assert sum(dead.values()) == 110592000

@@ -241,161 +241,98 @@ class WesupEngine:
             self._edge(self._side(), torch.cuda.current_stream())
 
     # ------------------------------------------------------------------ buffers
-    BYTES_PER_PIXEL = 16 * 1024      # a training buffer set before one has been measured (9.3 GiB at 4 x 480 x 480 = 10.6 KiB per pixel)
-
-    @staticmethod
-    def _set_bytes(b):
-        """Device bytes a buffer set holds right now (every tensor reachable from it, storages counted once)."""
-        seen, total, todo = set(), 0, [b]
-        while todo:
-            o = todo.pop()
-            if torch.is_tensor(o):
-                st = o.untyped_storage()
-                if st.data_ptr() not in seen:
-                    seen.add(st.data_ptr())
-                    total += st.nbytes()
-            elif isinstance(o, (list, tuple)):
-                todo.extend(o)
-            elif isinstance(o, _Bufs):
-                todo.extend(vars(o).values())
-        return total
-
-    def _bytes_per_pixel(self):
-        """What a buffer set costs per pixel of its batch: the largest figure among the cached sets that have been through a training
-        step (their lazily allocated parts exist), else the constant above."""
-        best = 0.0
-        for (B, H, W, _), b in self._bufs.items():
-            if getattr(b, 'train', False) and b.plans:
-                best = max(best, self._set_bytes(b) / float(B * H * W))
-        return best * 1.1 if best > 0 else float(self.BYTES_PER_PIXEL)
-
-    def _memory_short(self, pixels):
-        """The cache bounds above are counts; what ends a run is the allocator failing.  Before a set for a new shape is made: is
-        there room for it -- free device memory plus what torch's caching allocator holds unused?  If not the least recently used
-        sets go first (a co-resident job, a smaller GPU, or other tensors of the caller's have taken the room the bounds assume).
-        The need is estimated from the sets this engine has already made (measured bytes per pixel), not from a constant."""
+    def _memory_short(self, nbytes):
+        """The cache bounds above are counts; what ends a run is the allocator failing.  Before the tensors of a set for a new shape
+        are made: is there room for it -- free device memory plus what torch's caching allocator holds unused?  If not the least
+        recently used sets go first (a co-resident job, a smaller GPU, or other tensors of the caller's have taken the room the
+        bounds assume).  nbytes: the set's own size, layer_plan.nbytes of its table; the margin on top stands for what the set does
+        not hold -- the shared workspaces and the allocator's rounding."""
+        need = 1.1 * nbytes
         try:
             free, _ = torch.cuda.mem_get_info(self.device)
-            if free >= pixels * self.BYTES_PER_PIXEL:      # (the common case, one driver query; walking the sets / torch's statistics cost ms)
-                return False
-            need = pixels * self._bytes_per_pixel()
-            if free >= need:
+            if free >= need:                 # (the common case: one driver query; torch's statistics cost ms)
                 return False
             idle = torch.cuda.memory_reserved(self.device) - torch.cuda.memory_allocated(self.device)
         except Exception:
             return False
         return free + idle < need
 
+    def _table(self, b, plan):
+        """layer_plan.buffers of set b under plan: every buffer that walk touches."""
+        return layer_plan.buffers(plan, b.groups, b.Kmax, self.D,
+                                  lambda R, D: ops._lib.load().wesup_classifier_bwd_workspace_bytes(R, D))
+
     def _get_bufs(self, B, H, W, Kmax, train):
+        """The buffer set of a shape, most recently used.  A new one is a bare record here -- its grouping and empty slots; _fit
+        creates the tensors -- so that what it will cost is known (its plan's table) before anything is allocated."""
         key = (B, H, W, Kmax)
         b = self._bufs.get(key)
         if b is not None:
             self._bufs.move_to_end(key)
-        else:
-            # Bounded cache: training on multi-scale crops (utils/data.py: random rescale per item) or inference over
-            # images of varying size meets a new shape almost every call; every entry is a full set of activation and
-            # gradient buffers (~0.6 GB per 480x480 image in training), so only the most recent shapes are kept and the
-            # evicted buffers go back to torch's caching allocator, which hands their blocks to the next shape.
-            px = lambda k: k[0] * k[1] * k[2]
-            while self._bufs and (len(self._bufs) >= max(1, self.max_cached_shapes)
-                                  or sum(px(k) for k in self._bufs) + px(key) > self.max_cached_pixels
-                                  or self._memory_short(px(key))):
-                _, old = self._bufs.popitem(last=False)
-                if old is self._last:
-                    self._last = None
-                if self.ctx is not None and self.ctx[0] is old:
-                    self.ctx = None
-        dev = self.device
-        f32 = dict(dtype=torch.float32, device=dev)
-        if b is None:
-            b = _Bufs()
-            self.buf_generation += 1
-            b.gen = self.buf_generation
-            b.x0 = torch.empty(B, H, W, 4, **f32)
-            b.y, b.yp, b.s, b.dims, b.yr = [], [], [], [], []
-            b.V = [None] * 13            # Winograd-transformed layer inputs (training forward), allocated on first use
-            h, w = H, W
-            for l, (ci, co) in enumerate(CONV_CH):
-                b.dims.append((h, w))
-                b.y.append(torch.empty(B, h, w, co, **f32))
-                b.s.append(None)         # side outputs: views of the group buffers below, or allocated on first use (_side_out)
-                b.yr.append(None)        # the ReLU'd copy, allocated on first use (forward): a Winograd-domain consumer never needs it
-                if POOL_AFTER[l]:
-                    h, w = h // 2, w // 2
-                    b.yp.append(torch.empty(B, h, w, co, **f32))
-                else:
-                    b.yp.append(None)
-            # the matrix-form groups of this set (layer_plan.groups_for): a set keeps the grouping it was made with
-            groups, group_of = layer_plan.groups_for(B, H, W, Kmax, self._switches())
-            b.group_of = list(group_of)
-            b.groups = []
-            for grp in groups:
-                g = _Bufs()
-                g.layers, g.h, g.w, g.off, g.C = list(grp.layers), grp.h, grp.w, grp.off, grp.C
-                g.s = g.ds = None    # side outputs / their gradients side by side: allocated on first use
-                g.Wm = torch.empty(B, Kmax, g.h * g.w, **f32)
-                g.WmT = torch.empty(B, g.h * g.w, Kmax, **f32)
-                b.groups.append(g)
-            # the (B,HW,2112) feature map only exists on the unfused path (or when somebody asks for it)
-            b.fm = None if self.fuse_pool_fwd else torch.empty(B, H, W, FM_CHANNELS, **f32)
-            b.fm_valid = False
-            b.ybar, b.dybar = [None] * 13, [None] * 13       # commuted side branch: mean_r(upsample(y_l)) and its gradient
-            b.dM, b.bpart, b.dV = [None] * 13, [None] * 13, None   # dual_transform: per layer dM + bias rows, one shared V'
-            b.mbits, b.pcode = [None] * 13, [None] * 13      # compact_masks: sign bits / pooling codes of y_l, allocated on first use
-            b.s_valid = [False] * 13
-            b.plans = {}                 # train -> (key, StepPlan): see _plan
-            b.shape = (B, H, W)
-            R = B * Kmax
-            b.sp_in = torch.empty(B, Kmax, FM_CHANNELS, **f32)
-            b.h1 = torch.empty(R, 1024, **f32)
-            b.h2 = torch.empty(R, 1024, **f32)
-            b.feats = torch.empty(R, self.D, **f32)
-            b.sp_pred = torch.empty(R, 2, **f32)
-            b.pred = torch.empty(B, H, W, **f32)
-            b.train = False
-            self._bufs[key] = b
-        if train and not b.train:
-            R = B * Kmax
-            b.G = [torch.empty_like(y) for y in b.y]
-            b.ds = [None] * 13           # views of the group buffers, or allocated on first use (_side_grad)
-            b.dxp = [None if yp is None else torch.empty(yp.shape[0], yp.shape[1], yp.shape[2], CONV_CH[l + 1][0], **f32)
-                     for l, yp in enumerate(b.yp)]
-            b.dfm = None if self.fuse_pool_bwd else torch.empty(B, H, W, FM_CHANNELS, **f32)
-            b.dfeat = torch.empty(R, self.D, **f32)
-            b.dh2 = torch.empty(R, 1024, **f32)
-            b.dh1 = torch.empty(R, 1024, **f32)
-            b.gsp = torch.empty(B, Kmax, FM_CHANNELS, **f32)
-            # partial sums of the classifier's weight gradient between ops.head_bwd and ops.classifier_bwd_finish (another stream,
-            # three GEMMs later): this set's own buffer, never a shared workspace a growth elsewhere could replace in between
-            b.cls_part = ops.head_bwd_partials(R, self.D, dev)
-            b.train = True
+            return b
+        b = _Bufs()
+        b.shape, b.Kmax, b.dims = (B, H, W), Kmax, layer_plan.layer_dims(H, W)
+        # the matrix-form groups of this set (layer_plan.groups_for): a set keeps the grouping it was made with
+        groups, group_of = layer_plan.groups_for(B, H, W, Kmax, self._switches())
+        b.group_of = list(group_of)
+        b.groups = []
+        for grp in groups:
+            g = _Bufs()
+            g.layers, g.h, g.w, g.off, g.C = list(grp.layers), grp.h, grp.w, grp.off, grp.C
+            g.s = g.ds = g.Wm = g.WmT = None
+            b.groups.append(g)
+        for name in ('y', 'yp', 'yr', 's', 'V', 'ybar', 'mbits', 'pcode', 'G', 'dxp', 'ds', 'dybar', 'dM', 'bpart'):
+            setattr(b, name, [None] * 13)
+        for name in ('x0', 'fm', 'sp_in', 'h1', 'h2', 'feats', 'sp_pred', 'pred', 'dfm', 'dV', 'dfeat', 'dh2', 'dh1', 'gsp', 'cls_part'):
+            setattr(b, name, None)
+        b.fm_valid = False
+        b.s_valid = [False] * 13
+        b.plans = {}                 # train -> (key, StepPlan): see _plan
+        b.fitted = {}                # train -> the StepPlan the set was last fitted to: see _fit
+        # Bounded cache: training on multi-scale crops (utils/data.py: random rescale per item) or inference over
+        # images of varying size meets a new shape almost every call; every entry is a full set of activation and
+        # gradient buffers (~0.6 GB per 480x480 image in training), so only the most recent shapes are kept and the
+        # evicted buffers go back to torch's caching allocator, which hands their blocks to the next shape.
+        need = layer_plan.nbytes(self._table(b, self._plan(b, train)))
+        px = lambda k: k[0] * k[1] * k[2]
+        while self._bufs and (len(self._bufs) >= max(1, self.max_cached_shapes)
+                              or sum(px(k) for k in self._bufs) + px(key) > self.max_cached_pixels
+                              or self._memory_short(need)):
+            _, old = self._bufs.popitem(last=False)
+            if old is self._last:
+                self._last = None
+            if self.ctx is not None and self.ctx[0] is old:
+                self.ctx = None
+        self.buf_generation += 1
+        b.gen = self.buf_generation
+        self._bufs[key] = b
         return b
 
-    def _side_out(self, b, l):
-        """Buffer of layer l's side output at native resolution (B,h,w,C/2); None where the unfused path writes the side
-        conv straight into the feature map (full-resolution layers)."""
-        if b.s[l] is None and b.group_of[l] is not None:
-            g = b.groups[b.group_of[l]]
-            g.s = torch.empty(b.shape[0], g.h, g.w, g.C, dtype=torch.float32, device=self.device)
-            for i in g.layers:
-                c0 = SIDE_OFF[i] - g.off
-                b.s[i] = g.s[..., c0:c0 + CONV_CH[i][1] // 2]
-        elif b.s[l] is None and not (b.dims[l] == b.shape[1:] and not self.fuse_pool_fwd):
-            h, w = b.dims[l]
-            b.s[l] = torch.empty(b.shape[0], h, w, CONV_CH[l][1] // 2, dtype=torch.float32, device=self.device)
-        return b.s[l]
+    def _fit(self, b, plan):
+        """Top set b up to what the walk under plan touches (its table): the one place a set's tensors are created, in front of
+        the walk's first launch.  Nothing is ever freed or shrunk -- a switch flipped on a live engine adds what the new plan
+        needs to what the set holds."""
+        if b.fitted.get(plan.train) is not plan:
+            self._hold(b, self._table(b, plan))
+            b.fitted[plan.train] = plan
 
-    def _side_grad(self, b, l):
-        if b.ds[l] is None and b.group_of[l] is not None:
-            g = b.groups[b.group_of[l]]
-            g.ds = torch.empty(b.shape[0], g.h, g.w, g.C, dtype=torch.float32, device=self.device)
-            for i in g.layers:
-                c0 = SIDE_OFF[i] - g.off
-                b.ds[i] = g.ds[..., c0:c0 + CONV_CH[i][1] // 2]
-        elif b.ds[l] is None and not (b.dims[l] == b.shape[1:] and not self.fuse_pool_bwd):
-            h, w = b.dims[l]
-            b.ds[l] = torch.empty(b.shape[0], h, w, CONV_CH[l][1] // 2, dtype=torch.float32, device=self.device)
-        return b.ds[l]
+    def _hold(self, b, table):
+        """Create what set b does not hold of table (Buf records) with that shape."""
+        for e in table:
+            if e.name.startswith('g.'):
+                slots, k = vars(b.groups[e.layer]), e.name[2:]
+            elif e.layer is None:
+                slots, k = vars(b), e.name
+            else:
+                slots, k = getattr(b, e.name), e.layer
+            if slots[k] is not None and slots[k].shape == e.shape:
+                continue
+            if e.group is None:
+                slots[k] = torch.empty(e.shape, dtype=getattr(torch, e.dtype), device=self.device)
+            else:                    # side outputs (gradients) of a resolution side by side: a channel slice of the group's buffer
+                g = b.groups[e.group]
+                c0 = SIDE_OFF[k] - g.off
+                slots[k] = getattr(g, e.name)[..., c0:c0 + e.shape[-1]]
 
     def bufs_gen(self, B, H, W, Kmax):
         """The identity of the cached buffer set of a shape (None: not cached), marking it most recently used: what a
@@ -571,7 +508,7 @@ class WesupEngine:
 
     def _side_2d(self, b, l, fm2d):
         """Layer l's side output as a (pixels, C/2) matrix: its own buffer, or (unfused, full resolution) its slice of fm."""
-        s_l = self._side_out(b, l)
+        s_l = b.s[l]
         co = CONV_CH[l][1]
         return fm2d[:, SIDE_OFF[l]:SIDE_OFF[l] + co // 2] if s_l is None else s_l.view(-1, co // 2)
 
@@ -584,13 +521,11 @@ class WesupEngine:
         p, T = self.p, self.timer
         ws = p[f'side_conv{off}.weight'].view(co // 2, co)
         grp = b.groups[L.group] if L.group is not None else None
-        s_l = None if L.commuted else self._side_out(b, l)       # (None too where, unfused, the side conv writes its slice of fm)
+        s_l = None if L.commuted else b.s[l]     # (None too where, unfused, the side conv writes its slice of fm)
         with self._OnSide(self):
             if ('side_fwd_shallow' in self._diag_skip and grp is None) or ('side_fwd_deep' in self._diag_skip and grp is not None):
                 pass                     # timing-only diagnostic: sp_in keeps an earlier step's slice
             elif L.commuted:
-                if b.ybar[l] is None:
-                    b.ybar[l] = torch.empty(B, Kmax, co, dtype=torch.float32, device=self.device)
                 tok = T.begin('sp_pool_up_fwd')          # (commuted layers are the gather layers: no interpolation matrix)
                 ops.sp_pool_upsample_fwd(b.y[l], meta, b.ybar[l], 0)
                 T.end(tok, 4.0 * B * (h * w * co + H * W + Kmax * co))
@@ -632,6 +567,7 @@ class WesupEngine:
         self._last = b
         self._last_shape = (B, H, W)
         plan = self._plan(b, train, self._route_of(B, H, W))
+        self._fit(b, plan)
         pk = self._pack_weights(train, plan.route)
         p = self.p
         T = self.timer
@@ -656,23 +592,10 @@ class WesupEngine:
             idx = CONV_IDX[l]
             b.s_valid[l] = not L.commuted
             x = self._input_of(b, l, L)
-            yr = bits_out = code_out = None
-            if L.write_yr:
-                if b.yr[l] is None:
-                    b.yr[l] = torch.empty(B, h, w, co, dtype=torch.float32, device=self.device)
-                yr = b.yr[l]
-            if L.write_bits:
-                if b.mbits[l - 1] is None:
-                    b.mbits[l - 1] = torch.empty(B, h, w, ci // 4, dtype=torch.uint8, device=self.device)
-                bits_out = b.mbits[l - 1]
-            if L.write_codes:
-                if b.pcode[l] is None:
-                    b.pcode[l] = torch.empty(B, h // 2, w // 2, co // 4, dtype=torch.int16, device=self.device)
-                code_out = b.pcode[l]
+            yr = b.yr[l] if L.write_yr else None
+            bits_out = b.mbits[l - 1] if L.write_bits else None
+            code_out = b.pcode[l] if L.write_codes else None
             if m:
-                vshape = (ops.winograd_positions(m), ops.winograd_tiles(B, h, w, m), ci)
-                if L.keep_v and (b.V[l] is None or b.V[l].shape != vshape):      # the transformed input, kept for the weight gradient
-                    b.V[l] = torch.empty(vshape, dtype=torch.float32, device=self.device)
                 # timed as 'winograd_gemm' (executed MFMA FLOPs: 4/9 resp. 1/4 of the direct form's) + 'winograd_transform'
                 # (bytes).  (An m x m output tile holds whole windows of the max-pool behind conv2_2 / conv3_3 / conv4_3: the
                 # output transform writes the pooled tensor too and the max-pool launch below is skipped)
@@ -733,10 +656,13 @@ class WesupEngine:
             return None
         if not b.fm_valid:
             B, H, W = b.shape
-            if b.fm is None:
-                b.fm = torch.empty(B, H, W, FM_CHANNELS, dtype=torch.float32, device=self.device)
+            # fm, and the side outputs the step never formed (commuted layers), for the caller who asks: as the table has them
+            # for the walk with every side conv in front -- with fm (its own entry) and without (all thirteen side outputs)
+            plan = self._plan(b, False)
+            front = plan._replace(layers=tuple(L._replace(commuted=False) for L in plan.layers))
+            self._hold(b, [e for fm in (True, False) for e in self._table(b, front._replace(fm=fm)) if e.name in ('fm', 's')])
             for l, off in enumerate(SIDE_OFF):
-                s_l = self._side_out(b, l)
+                s_l = b.s[l]
                 if not b.s_valid[l]:          # commuted side branch: the step never formed this side output
                     h, w = b.dims[l]
                     co = CONV_CH[l][1]
@@ -773,6 +699,7 @@ class WesupEngine:
         # they would need.  Same here: a frozen layer has no wgrad launch, and below the lowest trainable layer there
         # is no dgrad chain and no side-conv dgrad at all (the side convs' own wgrads only need ds_l and y_l).
         plan = self._plan(b, True, b.plans[True][1].route)       # (the forward's routing; the switches as they are now)
+        self._fit(b, plan)
         Ls, lowest = plan.layers, plan.lowest
         # ---- classifier + fc_layers.  Between the last forward conv and the first dgrad the step has ONE chain of small
         # kernels (head forward, loss, head backward, pooling backward of the deepest layers: ~1.7 ms in which the chip
@@ -841,8 +768,6 @@ class WesupEngine:
             h, w = b.dims[ls[0]]
             for l in ls:
                 co, off = CONV_CH[l][1], SIDE_OFF[l]
-                if b.dybar[l] is None:
-                    b.dybar[l] = torch.empty(B, Kmax, co, dtype=torch.float32, device=self.device)
                 tok = T.begin('side_bwd')
                 ops.gemm_nt(gsp2d[:, off:off + co // 2], pk.sideT[l], None, out=b.dybar[l].view(R, co))
                 if Ls[l].gather:      # gathered per pixel by the epilogue of layer l + 1's input gradient: rows divided by their areas here, once
@@ -876,7 +801,7 @@ class WesupEngine:
                         h, w = b.dims[l]
                         tok = T.begin('upsample_bwd')
                         ops.upsample_bwd_fused(b.gsp, meta.new_row, meta.area_new, H, W, SIDE_OFF[l], h, w,
-                                               CONV_CH[l][1] // 2, out=self._side_grad(b, l))
+                                               CONV_CH[l][1] // 2, out=b.ds[l])
                         # own byte model (pool-backward fused in): the gradient at native resolution out, the pixel labels
                         # and one row of g per superpixel in -- not the (H, W, C/2) slice of a materialised gradient
                         T.end(tok, 4.0 * B * (h * w * (CONV_CH[l][1] // 2) + H * W + Kmax * (CONV_CH[l][1] // 2)))
@@ -920,7 +845,6 @@ class WesupEngine:
                             if ls[0] == l:
                                 commuted_G(ls)
                     continue
-                self._side_grad(b, l)            # (allocated on first use; a group's buffer serves all its layers)
                 if Ls[l].group is not None:
                     grp = b.groups[Ls[l].group]
                     if l == grp.layers[-1]:      # ds of every layer of this resolution at once: ds = Wm^T . gsp slice
@@ -936,9 +860,9 @@ class WesupEngine:
                     ds2d = b.ds[l].view(P, co // 2)
                 elif self.fuse_pool_bwd:
                     tok = T.begin('upsample_bwd')
-                    ops.upsample_bwd_fused(b.gsp, meta.new_row, meta.area_new, H, W, off, h, w, co // 2, out=self._side_grad(b, l))
+                    ops.upsample_bwd_fused(b.gsp, meta.new_row, meta.area_new, H, W, off, h, w, co // 2, out=b.ds[l])
                     ds2d = b.ds[l].view(P, co // 2)
-                elif self._side_grad(b, l) is None:
+                elif b.ds[l] is None:            # (unfused, full resolution: its slice of dfm)
                     ds2d = dfm2d[:, off:off + co // 2]
                 else:
                     ops.upsample_bwd(b.dfm, off, h, w, co // 2, out=b.ds[l])
@@ -977,12 +901,6 @@ class WesupEngine:
             v_dy = None
             if L.dual:      # one pass over G_l for both consumers (F(4x4) input gradient and weight gradient)
                 Tl = ops.winograd_tiles(B, h, w, 4)
-                if b.dV is None:
-                    b.dV = torch.empty(max(36 * ops.winograd_tiles(B, *b.dims[i], 4) * CONV_CH[i][1] for i in range(1, 13)),
-                                       dtype=torch.float32, device=self.device)
-                if b.dM[l] is None:
-                    b.dM[l] = torch.empty(36, Tl, co, dtype=torch.float32, device=self.device)
-                    b.bpart[l] = torch.empty(L.bias_rows, co, dtype=torch.float32, device=self.device)
                 v_dy = b.dV[:36 * Tl * co].view(36, Tl, co)
                 tok = T.begin('winograd_transform')
                 if 'dual' not in self._diag_skip:

@@ -2,9 +2,10 @@
 
 ``groups_for`` says which resolutions take the interpolation-matrix form, ``build`` turns a shape, that grouping, the
 routing and the switches into an immutable ``StepPlan`` (thirteen ``LayerPlan`` records + a few step-level facts).  The
-engine (engine.py) allocates and launches what the plan says; nothing here imports torch or touches the GPU, so the whole
-decision table can be checked on the CPU (tests/test_engine_plan_cpu.py).  The two queries of the library a decision
-depends on (ops.winograd_fused_supported, ops.winograd_bias_rows) come in as callables.
+engine (engine.py) launches what the plan says, on the buffers ``buffers`` lists for it (what a set of that shape holds, and
+costs: ``nbytes``); nothing here imports torch or touches the GPU, so the whole decision table can be checked on the CPU
+(tests/test_engine_plan_cpu.py).  The queries of the library a decision or a size depends on (ops.winograd_fused_supported,
+ops.winograd_bias_rows, the classifier's partial-sum block) come in as callables.
 """
 from collections import namedtuple
 
@@ -59,7 +60,13 @@ StepPlan = namedtuple('StepPlan', [
     'runs',           # commuted layers whose G the input-gradient chain needs, deepest first, <= 3 layers of one resolution per run
     'late_at', 'late_side',   # the grouped layers' side-conv weight gradients are queued when the chain reaches late_at
     'shallow_first',  # the shallow layers' side gradients go to the head of the weight-gradient stream
+    'fm', 'dfm',      # the (B,H,W,2112) feature map / its gradient are materialised (the unfused switches)
 ])
+
+# One buffer of a set: b.<name> (layer None), b.<name>[layer], or b.groups[layer].<name[2:]> for the 'g.' names (layer = the group's
+# index).  group: the side output (gradient) of a grouped layer is a channel slice of that group's 'g.s' ('g.ds'), no storage of its own
+Buf = namedtuple('Buf', 'name layer shape dtype group')
+ITEMSIZE = {'float32': 4, 'int16': 2, 'uint8': 1}
 
 
 def tiles(B, H, W, m):
@@ -213,4 +220,96 @@ def build(shape, group_of, route, switches, diag_skip, frozen, train, fused_supp
     return StepPlan(shape=tuple(shape), route=tuple(route), train=bool(train),
                     layers=tuple(LayerPlan(**f, **r) for f, r in zip(fwd, bwd)),
                     lowest=lowest, relu_stored=relu_stored, runs=tuple(tuple(r) for r in runs), late_at=late_at,
-                    late_side=late_side, shallow_first=bool(train and sw.two_streams and sw.fuse_pool_bwd))
+                    late_side=late_side, shallow_first=bool(train and sw.two_streams and sw.fuse_pool_bwd),
+                    fm=not sw.fuse_pool_fwd, dfm=bool(train and not sw.fuse_pool_bwd))
+
+
+def buffers(plan, groups, Kmax, D, cls_part_bytes):
+    """Every buffer the walk under ``plan`` reads or writes, as Buf records: what a set of that shape holds once it has been fitted
+    to the plan (engine._fit), and so what it costs (``nbytes``).  groups: the set's Group records (groups_for); cls_part_bytes: the
+    size of the classifier's partial-sum block, a number or a callable (rows, D) -> bytes (what ops.head_bwd_partials asks the
+    library for)."""
+    B, H, W = plan.shape[:3]
+    R, Ls = B * Kmax, plan.layers
+    out = []
+
+    def add(name, layer, shape, dtype='float32', group=None):
+        out.append(Buf(name, layer, tuple(int(n) for n in shape), dtype, group))
+
+    def side(name, l, L, in_fm):
+        # a side output / its gradient at native resolution: a slice of the group's buffer, a buffer of its own, or nothing at all
+        # where the unfused path reads / writes the full-resolution layer's channel slice of fm / dfm itself
+        if L.group is not None:
+            add(name, l, (B, L.h, L.w, L.co // 2), group=L.group)
+        elif not ((L.h, L.w) == (H, W) and in_fm):
+            add(name, l, (B, L.h, L.w, L.co // 2))
+
+    add('x0', None, (B, H, W, 4))
+    for i, g in enumerate(groups):      # (in front of their layers' slices)
+        add('g.s', i, (B, g.h, g.w, g.C))
+        add('g.Wm', i, (B, Kmax, g.h * g.w))
+        add('g.WmT', i, (B, g.h * g.w, Kmax))
+    for l, L in enumerate(Ls):
+        add('y', l, (B, L.h, L.w, L.co))
+        if L.pool:
+            add('yp', l, (B, L.h // 2, L.w // 2, L.co))
+        if L.write_yr:
+            add('yr', l, (B, L.h, L.w, L.co))
+        if L.keep_v:
+            add('V', l, ((L.m + 2) ** 2, tiles(B, L.h, L.w, L.m), L.ci))
+        if L.write_bits:
+            add('mbits', l - 1, (B, L.h, L.w, L.ci // 4), 'uint8')
+        if L.write_codes:
+            add('pcode', l, (B, L.h // 2, L.w // 2, L.co // 4), 'int16')
+        if L.commuted:
+            add('ybar', l, (B, Kmax, L.co))
+        else:
+            side('s', l, L, plan.fm)
+    if plan.fm:
+        add('fm', None, (B, H, W, FM_CHANNELS))
+    add('sp_in', None, (B, Kmax, FM_CHANNELS))
+    add('h1', None, (R, 1024))
+    add('h2', None, (R, 1024))
+    add('feats', None, (R, D))
+    add('sp_pred', None, (R, 2))
+    add('pred', None, (B, H, W))
+    if not plan.train:
+        return tuple(out)
+    for i, g in enumerate(groups):
+        add('g.ds', i, (B, g.h, g.w, g.C))
+    for l, L in enumerate(Ls):
+        add('G', l, (B, L.h, L.w, L.co))
+        # layer l + 1's input gradient at pooled resolution, in front of the max-pool backward launch: the 'gather' / 'unpool' forms
+        # write G[l] themselves, and at or below the lowest trainable layer there is no input gradient
+        if L.pool and Ls[l + 1].pool_bwd:
+            add('dxp', l, (B, L.h // 2, L.w // 2, Ls[l + 1].ci))
+        if not L.commuted:
+            side('ds', l, L, plan.dfm)
+        if L.dual:
+            add('dM', l, (36, tiles(B, L.h, L.w, 4), L.co))
+            add('bpart', l, (L.bias_rows, L.co))
+    for l in (l for run in plan.runs for l in run):
+        add('dybar', l, (B, Kmax, Ls[l].co))
+    if any(L.dual for L in Ls):       # one V' = B^T dY B for all layers, the largest of them
+        add('dV', None, (max(36 * tiles(B, L.h, L.w, 4) * L.co for L in Ls[1:]),))
+    if plan.dfm:
+        add('dfm', None, (B, H, W, FM_CHANNELS))
+    add('dfeat', None, (R, D))
+    add('dh2', None, (R, 1024))
+    add('dh1', None, (R, 1024))
+    add('gsp', None, (B, Kmax, FM_CHANNELS))
+    # (partial sums of the classifier's weight gradient between ops.head_bwd and ops.classifier_bwd_finish: the set's own block)
+    add('cls_part', None, (max(int(cls_part_bytes(R, D) if callable(cls_part_bytes) else cls_part_bytes), 256),), 'uint8')
+    return tuple(out)
+
+
+def nbytes(bufs):
+    """Device bytes of a buffer table; a slice of a group's buffer has no storage of its own."""
+    total = 0
+    for b in bufs:
+        if b.group is None:
+            n = ITEMSIZE[b.dtype]
+            for d in b.shape:
+                n *= d
+            total += n
+    return total

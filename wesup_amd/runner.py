@@ -14,8 +14,8 @@ pixel masks as (B,C,H,W) tensors, accuracy / dice as metrics, the fused SGD -- i
 * the FIRST occurrence of a shape records the walk into a step plan (csrc/plan.hip), the second records it again and the
   two recordings are compared node by node; when they are identical, the third and later iterations of that shape REPLAY the
   plan from C (round 4 walked twice before the first recording: with the reference's ~100 shapes x 85 images per epoch,
-  utils/data.py:98-101, the first epochs hardly replayed.  A first walk that allocates -- the shape's buffer set, a workspace
-  that grows -- records addresses that are final when the walk ends; the twin either confirms them or replaces the candidate)
+  utils/data.py:98-101, the first epochs hardly replayed.  A shape's buffer set is complete before the walk's first launch
+  (engine._fit); a first walk in which a workspace grows is discarded, and the twin confirms the rest or replaces the candidate)
   (``wesup_plan_replay``): ~330 launches without Python or ctypes in between.  Host work inside the iteration (the NaN check, a
   gradient bucket handed to RCCL) splits the replay into segments.  Anything that moves a buffer (a workspace that grew, the
   engine's buffer cache evicting the shape) or changes the walk (an engine switch, the learning rate, frozen parameters)
