@@ -479,6 +479,25 @@ int wesup_window_gather(const uint8_t* img, const int32_t* tops, const int32_t* 
 int wesup_window_merge(const float* pred, const int32_t* tops, const int32_t* lefts, double* out, int H, int W, int C, int n_h,
                        int n_w, int p, int round_first, void* stream);
 
+/* ------------------------------------------------------------------ whole-image multi-scale pixel inference (csrc/pixel.hip)
+ * pixel_infer.py:38-56 rescales an image by every factor of --scales (bilinear, align_corners=True), runs the pixel-wise
+ * model, resizes class 1 back and averages.  Source coordinates are torch's fp32 formula (csrc/bilinear.hpp).
+ *
+ * wesup_image_resize_u8: img uint8 [H][W][3] -> out fp32 [3][h][w] = bilinear_ac(img / 255.f): to_tensor + F.interpolate
+ * (pixel_infer.py:40,46); at h == H, w == W the value is img / 255.f bit for bit. */
+int wesup_image_resize_u8(const uint8_t* img, float* out, int H, int W, int h, int w, void* stream);
+/* out[H][W] = (accumulate ? out : 0) + alpha * bilinear_ac(in); in is an [h][w] plane whose elements sit `stride` floats
+ * apart (2: class 1 of an [h][w][2] prediction, read in place).  alpha = 1 / len(scales): the mean needs no pass of its own */
+int wesup_plane_resize_acc(const float* in, float* out, int h, int w, int H, int W, int stride, float alpha, int accumulate,
+                           void* stream);
+/* First fc layer of the pixel head from per-resolution products:
+ *   out[b][y][x][n] = ReLU(bias[n] + p0[b][y][x][n] + sum_r bilinear_ac(levels[r].p[b])(y, x)[n]),  r < n_levels <= 4,
+ * p0 / out [B][H][W][N], levels[r].p [B][h][w][N], N % 4 == 0, every pointer 16-byte aligned.  Every level is interpolated
+ * straight to (H, W).  out may be p0 (an element reads only its own element of p0).  levels is a HOST array */
+typedef struct WesupCoarseMap { const float* p; int h, w; } WesupCoarseMap;
+int wesup_pixel_gather_fwd(const float* p0, const float* bias, float* out, const WesupCoarseMap* levels /* host */, int n_levels,
+                           int B, int H, int W, int N, void* stream);
+
 /* ------------------------------------------------------------------ entries by the names of SURVEY.md 8(b)
  * One call per ATen op of the reference for a binding that replaces them one by one; each is a thin entry over the
  * kernels above (csrc/named.hip).  Matrices are row-major with the channel / feature index contiguous (NHWC pixels). */

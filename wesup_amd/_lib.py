@@ -124,6 +124,10 @@ _SIGS = {
     # window inference on large images (csrc/tiles.hip)
     'wesup_window_gather': (c_int, 'pppp' + 'iiiiiii' + 'p'),
     'wesup_window_merge': (c_int, 'pppp' + 'iiiiiii' + 'p'),
+    # whole-image multi-scale pixel inference (csrc/pixel.hip)
+    'wesup_image_resize_u8': (c_int, 'pp' + 'iiii' + 'p'),
+    'wesup_plane_resize_acc': (c_int, 'pp' + 'iiiii' + 'fi' + 'p'),
+    'wesup_pixel_gather_fwd': (c_int, 'pppp' + 'iiiii' + 'p'),
     # entries by the names of SURVEY.md 8(b) (csrc/named.hip)
     'wesup_sp_stats': (c_int, 'ppiiiipppp'),
     'wesup_conv1x1_workspace_bytes': (c_size_t, 'iii'),
@@ -176,6 +180,10 @@ class WinoFilter(ctypes.Structure):            # WesupWinoFilter (include/wesup_
 
 class TransposeItem(ctypes.Structure):         # WesupTransposeItem
     _fields_ = [('src', c_void_p), ('dst', c_void_p), ('rows', c_int), ('cols', c_int)]
+
+
+class CoarseMap(ctypes.Structure):             # WesupCoarseMap
+    _fields_ = [('p', c_void_p), ('h', c_int), ('w', c_int)]
 
 
 def build(verbose=False):

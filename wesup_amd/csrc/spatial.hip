@@ -2,6 +2,7 @@
 // upsample fwd and its gather-form backward (optionally fused with the superpixel-pooling backward).
 // All of them move 16 B per lane along the channel axis (coalesced), no atomics, deterministic.
 #include "common.hpp"
+#include "bilinear.hpp"
 
 // ------------------------------------------------------------------ input packing
 __global__ void pack_input_kernel(const float* __restrict__ img, float* __restrict__ out, int B, long HW) {
@@ -221,23 +222,7 @@ extern "C" int wesup_maxpool2_bwd(const float* y, const float* dyp, float* dy, i
 }
 
 // ------------------------------------------------------------------ bilinear, align_corners=True
-// torch: scale = (in-1)/(out-1) (float); src = scale*dst; i0 = min(int(src), in-1); i1 = i0 + (i0 < in-1);
-// l1 = clamp(src - i0, 0, 1); l0 = 1 - l1.
-struct Lerp {
-    int i0, i1;
-    float l0, l1;
-};
-__device__ __forceinline__ Lerp lerp_of(int dst, float scale, int in) {
-    Lerp r;
-    const float src = scale * (float)dst;
-    r.i0 = min((int)src, in - 1);
-    r.i1 = r.i0 + ((r.i0 < in - 1) ? 1 : 0);
-    r.l1 = fminf(fmaxf(src - (float)r.i0, 0.f), 1.f);
-    r.l0 = 1.f - r.l1;
-    return r;
-}
-static inline float ac_scale(int in, int out) { return out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f; }
-
+// (source coordinates and weights: lerp_of / ac_scale, bilinear.hpp)
 __global__ void upsample_fwd_kernel(const float* __restrict__ s, float* __restrict__ fm, int B, int h, int w, int H,
                                     int W, int C4, int ldf, int coff, float sh, float sw) {
     const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;

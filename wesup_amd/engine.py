@@ -132,6 +132,7 @@ class WesupEngine:
         self.max_cached_shapes = 256
         self.max_cached_pixels = 10 * 1024 * 1024
         self._last = None                # buffers of the most recent forward (feature_maps() reads these)
+        self._backbone_sets = OrderedDict()      # (B,H,W) -> the taps of backbone(), least recently used first
         self.frozen = set()              # names of parameters with requires_grad=False (set by WESUP.forward)
         self._packed = None
         self._prefetched = None
@@ -345,6 +346,7 @@ class WesupEngine:
 
     def release_buffers(self):
         self._bufs.clear()
+        self._backbone_sets.clear()
         self._last = None
         self.ctx = None
 
@@ -672,6 +674,63 @@ class WesupEngine:
                 ops.upsample_fwd(s_l.contiguous(), b.fm, off)
             b.fm_valid = True
         return b.fm
+
+    # ------------------------------------------------------------------ the conv chain alone
+    MAX_BACKBONE_SHAPES = 4
+
+    def backbone(self, img):
+        """The thirteen convolutions of an evaluation walk and nothing else: img (B,3,H,W) fp32 on the GPU -> the pre-ReLU taps
+        y[0..12], (B,h_l,w_l,co_l) NHWC.  No superpixel description, and none of the side-branch, interpolation-matrix,
+        scatter-mean, fc, classifier or paint launches of forward().  The convolutions take the forms forward(train=False) gives
+        them (same routing, same plan fields).  The taps live in a small cache of their own, keyed by shape and reused by the next
+        call of that shape: the buffer sets, plans and context of forward() / backward() are not touched."""
+        B, _, H, W = img.shape
+        if torch.cuda.current_device() != self.device.index:
+            raise RuntimeError(f'the model lives on {self.device} but the current device is cuda:{torch.cuda.current_device()}: '
+                               'one process per GPU (torch.cuda.set_device) -- launches would go to the wrong device')
+        route = self._route_of(B, H, W)
+        key = (self._switches(), route, ops.winograd_fused_min_blocks())
+        cache = self._backbone_sets
+        b = cache.get((B, H, W))
+        if b is None or b.key != key:
+            b = _Bufs()
+            b.key = key
+            # no layer is grouped and none is trained: only the forward fields of the plan are read here
+            b.plan = layer_plan.build((B, H, W), (None,) * 13, route, key[0], frozenset(), frozenset(), False,
+                                      ops.winograd_fused_supported, ops.winograd_bias_rows)
+            new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=self.device)
+            b.x0 = new(B, H, W, 4)
+            b.y = [new(B, L.h, L.w, L.co) for L in b.plan.layers]
+            b.yp = [new(B, L.h // 2, L.w // 2, L.co) if L.pool else None for L in b.plan.layers]
+            b.yr = [new(B, L.h, L.w, L.co) if L.write_yr else None for L in b.plan.layers]
+            cache.pop((B, H, W), None)
+            while len(cache) >= self.MAX_BACKBONE_SHAPES:
+                cache.popitem(last=False)
+            cache[(B, H, W)] = b
+        cache.move_to_end((B, H, W))
+        plan = b.plan
+        pk = self._pack_weights(False, route)
+        p, T = self.p, self.timer
+        ops.pack_input(img, b.x0)
+        for l, L in enumerate(plan.layers):
+            if l == 0 and pk.ready0:
+                ops.sync_wait(self.SLOT_W0)
+            if l == 1 and pk.ready:
+                ops.sync_wait(self.SLOT_W)
+            x = self._input_of(b, l, L)
+            yr = b.yr[l] if L.write_yr else None
+            bias = p[f'backbone.{CONV_IDX[l]}.bias']
+            if L.m:
+                ops.conv3x3_fwd_winograd(x, pk.uf[l], bias, relu_in=L.relu_in, out=b.y[l], out_relu=yr, ws_tag='wino_main', timer=T,
+                                         out_pool=b.yp[l] if L.pool else None, pool_relu=plan.relu_stored, m=L.m)
+            else:
+                tok = T.begin('conv3x3_fwd')
+                ops.conv3x3_fwd(x, pk.wf[l], bias, L.co, relu_in=L.relu_in, out=b.y[l], out_relu=yr)
+                T.end(tok, 2.0 * B * L.h * L.w * L.co * (3 if l == 0 else L.ci) * 9)
+                if L.pool:
+                    ops.maxpool2_fwd(b.y[l], b.yp[l], relu=plan.relu_stored)
+        self._join_side()
+        return b.y
 
     # ------------------------------------------------------------------ backward
     def abort_backward(self):

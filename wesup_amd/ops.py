@@ -1443,3 +1443,59 @@ def window_merge(pred, tops, lefts, H, W, round_first=False, out=None):
               int(bool(round_first)), _stream())
     _tend(tok, 4.0 * N * p * p * C + 8.0 * H * W * C)
     return out
+
+
+# ---------------------------------------------------------------- whole-image multi-scale pixel inference (csrc/pixel.hip)
+def image_resize_u8(img_u8_hwc, h, w, out=None):
+    """to_tensor + F.interpolate(mode='bilinear', align_corners=True) of pixel_infer.py:40,46 in one pass: img (H,W,3) uint8 on
+    the device -> (1,3,h,w) fp32, ``img / 255.f`` resampled (at the image's own size: ``img / 255.f`` bit for bit)."""
+    if not isinstance(img_u8_hwc, torch.Tensor) or img_u8_hwc.dim() != 3 or img_u8_hwc.shape[-1] != 3:
+        raise _lib.WesupHipError('image_resize_u8: expected an (H,W,3) uint8 image')
+    _chk(img_u8_hwc, torch.uint8, 'img')
+    H, W, _ = img_u8_hwc.shape
+    h, w = int(h), int(w)
+    if h < 1 or w < 1:
+        raise _lib.WesupHipError(f'image_resize_u8: target size {h} x {w}')
+    if out is None:
+        out = torch.empty(1, 3, h, w, dtype=torch.float32, device=img_u8_hwc.device)
+    _chk(out, name='out')
+    if out.shape != (1, 3, h, w) or out.device != img_u8_hwc.device:
+        raise _lib.WesupHipError(f'image_resize_u8: out {tuple(out.shape)} on {out.device}, expected {(1, 3, h, w)}')
+    _lib.call('wesup_image_resize_u8', _p(img_u8_hwc), _p(out), H, W, h, w, _stream())
+    return out
+
+
+def plane_resize_acc(src, out, alpha=1.0, accumulate=False):
+    """out (H,W) = (accumulate ? out : 0) + alpha * bilinear_ac(src); src is an (h,w) fp32 plane, contiguous or a view with an
+    element stride such as ``pred[..., 1]`` of an (h,w,C) prediction (read in place)."""
+    _chk(out, name='out')
+    if not isinstance(src, torch.Tensor) or not src.is_cuda or src.dtype != torch.float32 or src.dim() != 2 or out.dim() != 2:
+        raise _lib.WesupHipError('plane_resize_acc: expected 2-D float32 CUDA/HIP planes')
+    h, w = src.shape
+    stride = src.stride(1) if w > 1 else (src.stride(0) if h > 1 else 1)      # (a size-1 dimension's stride means nothing)
+    if stride < 1 or (h > 1 and src.stride(0) != w * stride) or src.device != out.device:
+        raise _lib.WesupHipError(f'plane_resize_acc: src strides {src.stride()} for shape {tuple(src.shape)}')
+    H, W = out.shape
+    _lib.call('wesup_plane_resize_acc', _p(src), _p(out), h, w, H, W, stride, float(alpha), int(bool(accumulate)), _stream())
+    return out
+
+
+def pixel_gather_fwd(p0, bias, coarse=(), out=None):
+    """out (B,H,W,N) = ReLU(bias + p0 + sum_r bilinear_ac(coarse[r])): the first fc layer of the pixel head from its
+    per-resolution products p0 (B,H,W,N) and up to four coarse maps (B,h_r,w_r,N), each interpolated straight to (H,W).
+    out=None works in place on p0."""
+    _chk(p0, name='p0'); _chk(bias, name='bias')
+    B, H, W, N = p0.shape
+    if out is None:
+        out = p0
+    _chk(out, name='out')
+    if out.shape != p0.shape or bias.numel() != N or N % 4 or len(coarse) > 4:
+        raise _lib.WesupHipError(f'pixel_gather_fwd: p0 {tuple(p0.shape)}, out {tuple(out.shape)}, bias {bias.numel()}, {len(coarse)} levels')
+    levels = (_lib.CoarseMap * max(len(coarse), 1))()
+    for r, c in enumerate(coarse):
+        _chk(c, name=f'coarse[{r}]')
+        if c.dim() != 4 or c.shape[0] != B or c.shape[3] != N or c.device != p0.device:
+            raise _lib.WesupHipError(f'pixel_gather_fwd: coarse[{r}] {tuple(c.shape)} under p0 {tuple(p0.shape)}')
+        levels[r].p, levels[r].h, levels[r].w = c.data_ptr(), c.shape[1], c.shape[2]
+    _lib.call('wesup_pixel_gather_fwd', _p(p0), _p(bias), _p(out), levels, len(coarse), B, H, W, N, _stream())
+    return out
