@@ -498,6 +498,37 @@ typedef struct WesupCoarseMap { const float* p; int h, w; } WesupCoarseMap;
 int wesup_pixel_gather_fwd(const float* p0, const float* bias, float* out, const WesupCoarseMap* levels /* host */, int n_levels,
                            int B, int H, int W, int N, void* stream);
 
+/* ------------------------------------------------------------------ whole-slide evaluation: the DP2019 patch pipeline (csrc/slide.hip)
+ * test_dp2019_pipeline.py:18-71,158-172 cuts a slide into zero-padded p x p patches, runs infer.py (input_size) or pixel_infer.py
+ * (one scale) on each and pastes the predictions back.  The patch lattice of an (H, W) slide: n_h = ceil(H / p) rows of
+ * n_w = ceil(W / p) patches; patch k (row-major) has its corner at (k / n_w * p, k % n_w * p); texels beyond the slide are 0.
+ * p > H and p > W are fine (one padded patch).  Sizes: 1 <= H, W, p <= 2^30 and n_h * n_w < 2^31; H * W itself is not limited
+ * (every offset into the slide is 64-bit: a slide may exceed 2^31 bytes); a pass's tensors are indexed in 64 bit as well.
+ * All three entries: WESUP_ERR_INVALID without a launch for a null pointer, a non-positive size, count < 1, first < 0, a mode /
+ * align_corners outside {0, 1} or stride < 1; no workspace, no host sync.
+ *
+ * wesup_patch_gather_resize: img uint8 [H][W][3] -> out fp32 [count][3][h][w], the patches first .. first + count - 1, each
+ * (patch / 255.f) resized bilinearly from p x p to h x w (the same byte -> float expression as wesup_image_resize_u8).
+ * align_corners = 1: pixel_infer.py's resize, the coordinates of every other resampling kernel here -- a patch wholly inside
+ * the slide equals wesup_image_resize_u8 of it bit for bit.  align_corners = 0: infer.py's F.interpolate(mode='bilinear'),
+ * torch's src = max(scale * (dst + 0.5) - 0.5, 0).  The neighbour clamp is at the PATCH border and a texel beyond the slide
+ * reads as 0 (pad, then resize -- not a clamp to the slide's edge).  An index >= n_h * n_w repeats the last patch (the padding of
+ * a ragged final batch). */
+int wesup_patch_gather_resize(const uint8_t* img, float* out, int H, int W, int p, int h, int w, int align_corners, int first,
+                              int count, void* stream);
+/* pred fp32 [count][h][w], elements `stride` floats apart (2: class 1 of an (h, w, 2) prediction, read in place) -> out uint8
+ * [H][W]: every slide pixel inside one of the patches first .. first + count - 1 becomes 255 * rintf(v) (half to even), v = the
+ * patch's prediction resized to p x p.  mode 0 (infer.py): F.interpolate(mode='nearest'), source index min(floorf(dst * scale),
+ * in - 1), scale = (float)in / p.  mode 1 (pixel_infer.py, one scale): bilinear, align_corners -- wesup_plane_resize_acc's
+ * arithmetic at alpha = 1.  Lattice pixels beyond the slide (combine_single's crop) and patches past the end of the lattice are
+ * not written; nothing else of out is touched. */
+int wesup_patch_scatter_u8(const float* pred, uint8_t* out, int H, int W, int p, int h, int w, int stride, int mode, int first,
+                           int count, void* stream);
+/* S, G uint8 [n] -> out4 int64 [4] (8-byte aligned, zeroed here) = {#(s == g), #(s > 0 && g > 0), #(s > 0), #(g > 0)}, after
+ * x -> 255 - x on both maps with `negative` (compute_metrics(negative=True), test_dp2019_pipeline.py:100-111).  Integer counts,
+ * exact in any order; accuracy = eq / n and dice = 2 * inter / (sumG + sumS + 1e-7) are the host's, in float64. */
+int wesup_mask_scores(const uint8_t* S, const uint8_t* G, int64_t* out4, long n, int negative, void* stream);
+
 /* ------------------------------------------------------------------ entries by the names of SURVEY.md 8(b)
  * One call per ATen op of the reference for a binding that replaces them one by one; each is a thin entry over the
  * kernels above (csrc/named.hip).  Matrices are row-major with the channel / feature index contiguous (NHWC pixels). */

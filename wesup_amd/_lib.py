@@ -128,6 +128,10 @@ _SIGS = {
     'wesup_image_resize_u8': (c_int, 'pp' + 'iiii' + 'p'),
     'wesup_plane_resize_acc': (c_int, 'pp' + 'iiiii' + 'fi' + 'p'),
     'wesup_pixel_gather_fwd': (c_int, 'pppp' + 'iiiii' + 'p'),
+    # whole-slide evaluation: the DP2019 patch pipeline (csrc/slide.hip)
+    'wesup_patch_gather_resize': (c_int, 'pp' + 'iiiiiiii' + 'p'),
+    'wesup_patch_scatter_u8': (c_int, 'pp' + 'iiiiiiiii' + 'p'),
+    'wesup_mask_scores': (c_int, 'ppp' + 'li' + 'p'),
     # entries by the names of SURVEY.md 8(b) (csrc/named.hip)
     'wesup_sp_stats': (c_int, 'ppiiiipppp'),
     'wesup_conv1x1_workspace_bytes': (c_size_t, 'iii'),

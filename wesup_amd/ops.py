@@ -1499,3 +1499,81 @@ def pixel_gather_fwd(p0, bias, coarse=(), out=None):
         levels[r].p, levels[r].h, levels[r].w = c.data_ptr(), c.shape[1], c.shape[2]
     _lib.call('wesup_pixel_gather_fwd', _p(p0), _p(bias), _p(out), levels, len(coarse), B, H, W, N, _stream())
     return out
+
+
+# ---------------------------------------------------------------- whole-slide evaluation: the DP2019 patch pipeline (csrc/slide.hip)
+def _patch_lattice(H, W, p, first, count, name):
+    H, W, p, first, count = int(H), int(W), int(p), int(first), int(count)
+    if H < 1 or W < 1 or p < 1 or max(H, W, p) > 1 << 30:
+        raise _lib.WesupHipError(f'{name}: patch size {p} for a slide of {H} x {W}')
+    if first < 0 or count < 1:
+        raise _lib.WesupHipError(f'{name}: patches [{first}, {first} + {count})')
+    return H, W, p, first, count
+
+
+def patch_gather_resize(img_u8_hwc, p, h, w, first, count, align_corners=False, out=None):
+    """Network inputs for the patches of a slide on the device: img (H,W,3) uint8 -> (count,3,h,w) fp32, the zero-padded
+    ``p`` x ``p`` patches ``first .. first + count - 1`` of the ``ceil(H / p)`` x ``ceil(W / p)`` lattice (row-major), each
+    ``patch / 255.f`` resized bilinearly to (h, w): ``F.interpolate(mode='bilinear')`` of infer.py, or with ``align_corners`` the
+    resize of pixel_infer.py (ops.image_resize_u8 of the patch, bit for bit, where the patch lies inside the slide).  Indices
+    past the last patch repeat it (the padding of a ragged final batch).  ``out``: a buffer reused across passes."""
+    if not isinstance(img_u8_hwc, torch.Tensor) or img_u8_hwc.dim() != 3 or img_u8_hwc.shape[-1] != 3:
+        raise _lib.WesupHipError('patch_gather_resize: expected an (H,W,3) uint8 image')
+    _chk(img_u8_hwc, torch.uint8, 'img')
+    H, W, p, first, count = _patch_lattice(img_u8_hwc.shape[0], img_u8_hwc.shape[1], p, first, count, 'patch_gather_resize')
+    h, w = int(h), int(w)
+    if h < 1 or w < 1:
+        raise _lib.WesupHipError(f'patch_gather_resize: target size {h} x {w}')
+    if out is None:
+        out = torch.empty(count, 3, h, w, dtype=torch.float32, device=img_u8_hwc.device)
+    _chk(out, name='out')
+    if out.shape != (count, 3, h, w) or out.device != img_u8_hwc.device:
+        raise _lib.WesupHipError(f'patch_gather_resize: out {tuple(out.shape)} on {out.device}, expected {(count, 3, h, w)}')
+    tok = _tbegin('patch_gather_resize')
+    _lib.call('wesup_patch_gather_resize', _p(img_u8_hwc), _p(out), H, W, p, h, w, int(bool(align_corners)), first, count,
+              _stream())
+    _tend(tok, 12.0 * count * h * w)
+    return out
+
+
+def patch_scatter_u8(pred, out, p, first, mode=0):
+    """Paste patch predictions into the slide-size map: pred (count,h,w) fp32 -- contiguous, or a view with an element stride
+    such as ``probs[..., 1]`` of a (count,h,w,C) prediction, read in place -- for the patches ``first .. first + count - 1``;
+    out (H,W) uint8.  Every slide pixel inside those patches becomes ``255 * round(v)`` (half to even), ``v`` the prediction
+    resized to ``p`` x ``p``: ``mode`` 0 nearest (infer.py), 1 bilinear with align_corners (pixel_infer.py at one scale).  The
+    rest of ``out`` is left as it is; the lattice's padding beyond the slide is never written."""
+    _chk(out, torch.uint8, 'out')
+    if not isinstance(pred, torch.Tensor) or not pred.is_cuda or pred.dtype != torch.float32 or pred.dim() != 3 or out.dim() != 2:
+        raise _lib.WesupHipError('patch_scatter_u8: expected (count,h,w) float32 CUDA/HIP predictions and an (H,W) uint8 map')
+    if mode not in (0, 1):
+        raise _lib.WesupHipError(f'patch_scatter_u8: mode {mode}')
+    count, h, w = pred.shape
+    H, W, p, first, count = _patch_lattice(out.shape[0], out.shape[1], p, first, count, 'patch_scatter_u8')
+    if h < 1 or w < 1:
+        raise _lib.WesupHipError(f'patch_scatter_u8: pred {tuple(pred.shape)}')
+    stride = pred.stride(2) if w > 1 else (pred.stride(1) // w if h > 1 else (pred.stride(0) // (h * w) if count > 1 else 1))
+    if stride < 1 or (h > 1 and pred.stride(1) != w * stride) or (count > 1 and pred.stride(0) != h * w * stride) or \
+            pred.device != out.device:
+        raise _lib.WesupHipError(f'patch_scatter_u8: pred strides {pred.stride()} for shape {tuple(pred.shape)}')
+    tok = _tbegin('patch_scatter_u8')
+    _lib.call('wesup_patch_scatter_u8', _p(pred), _p(out), H, W, p, h, w, stride, int(mode), first, count, _stream())
+    _tend(tok, 4.0 * count * h * w + 1.0 * count * p * p)
+    return out
+
+
+def mask_scores(S, G, negative=False, out=None):
+    """The pixel counts behind overall accuracy and Dice of two uint8 maps of one shape: (4,) int64 on the device,
+    ``{#(s == g), #(s > 0 and g > 0), #(s > 0), #(g > 0)}``, after ``x -> 255 - x`` on both with ``negative``
+    (compute_metrics(negative=True) of the reference).  ``out``: a (4,) int64 buffer to reuse."""
+    _chk(S, torch.uint8, 'S'); _chk(G, torch.uint8, 'G')
+    if S.shape != G.shape or S.numel() < 1 or S.device != G.device:
+        raise _lib.WesupHipError(f'mask_scores: maps {tuple(S.shape)} and {tuple(G.shape)}')
+    if out is None:
+        out = torch.empty(4, dtype=torch.int64, device=S.device)
+    _chk(out, torch.int64, 'out')
+    if out.shape != (4,) or out.device != S.device:
+        raise _lib.WesupHipError(f'mask_scores: out {tuple(out.shape)} on {out.device}, expected (4,)')
+    tok = _tbegin('mask_scores')
+    _lib.call('wesup_mask_scores', _p(S), _p(G), _p(out), S.numel(), int(bool(negative)), _stream())
+    _tend(tok, 2.0 * S.numel())
+    return out
