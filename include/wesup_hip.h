@@ -529,6 +529,33 @@ int wesup_patch_scatter_u8(const float* pred, uint8_t* out, int H, int W, int p,
  * exact in any order; accuracy = eq / n and dice = 2 * inter / (sumG + sumS + 1e-7) are the host's, in float64. */
 int wesup_mask_scores(const uint8_t* S, const uint8_t* G, int64_t* out4, long n, int negative, void* stream);
 
+/* ------------------------------------------------------------------ weak-label preparation (csrc/prepare.hip)
+ * The integer label-map passes of wesup_amd/prepare.py (scripts/generate_points.py, generate_spl_masks.py and
+ * search_slic_params.py of the reference).  Label maps are int32, images at most 2^22 on a side.  All entries: WESUP_ERR_INVALID
+ * without a launch for a null pointer, a non-positive size, a table size outside its range or a shape whose sums the counters
+ * cannot hold; a label outside its table sets bit 0 of the image's status word and is skipped; results are exact integers in
+ * any order of the atomics.
+ *
+ * wesup_prepare_lds_entries: the largest table that a block keeps privately in LDS -- labels (L + 1) of wesup_label_stats for
+ * which = 0, ids (K) of wesup_sp_vote for which = 1; larger tables are added to in global memory. */
+int wesup_prepare_lds_entries(int which);
+/* labels [B][H][W] in [0, L] -> stats int64 [B][L + 1][3] (8-byte aligned, zeroed here) = {pixels, sum of the row indexes, sum of
+ * the column indexes} per label: the size and the centroid numerator of every region in one pass.  L < 2^26. */
+int wesup_label_stats(const int32_t* labels, int64_t* stats, int32_t* status, int B, int H, int W, int L, void* stream);
+/* labels [B][H][W] in [0, K), values uint8 [B][H][W]: every superpixel votes the mean of its values rounded half to even in
+ * integers (q, r = divmod(sum, count); q + 1 if 2r > count, q + (q & 1) if 2r == count, else q: numpy's mean().round(); 0 for an
+ * id without a pixel).  painted uint8 [B][H][W] (may be NULL) = the vote of each pixel's superpixel; agree int64 [B] (8-byte
+ * aligned, zeroed here) = pixels whose vote equals their value.  The counters are 32 bits wide: 255 * H * W < 2^32, K <= 2^26. */
+size_t wesup_sp_vote_workspace_bytes(int B, int H, int W, int K);
+int wesup_sp_vote(const int32_t* labels, const uint8_t* values, uint8_t* painted, int64_t* agree, int32_t* status, int B, int H,
+                  int W, int K, void* ws, size_t ws_bytes, void* stream);
+/* labels [H][W] in [0, K), points int32 [P][3] of (row, col, class) inside the image and the classes (status |= 2 otherwise: the
+ * caller wraps and checks) -> out uint8 [H][W][C]: out[h][w][c] = 1 iff a point of class c lies in the superpixel of (h, w).  A
+ * K x C flag table, then the paint; P = 0 (points may be NULL) gives all zeros.  C <= 256, K * C <= 2^26. */
+size_t wesup_spl_paint_workspace_bytes(int K, int C);
+int wesup_spl_paint(const int32_t* labels, const int32_t* points, uint8_t* out, int32_t* status, int H, int W, int K, int C, int P,
+                    void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------ entries by the names of SURVEY.md 8(b)
  * One call per ATen op of the reference for a binding that replaces them one by one; each is a thin entry over the
  * kernels above (csrc/named.hip).  Matrices are row-major with the channel / feature index contiguous (NHWC pixels). */

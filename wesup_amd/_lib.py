@@ -132,6 +132,13 @@ _SIGS = {
     'wesup_patch_gather_resize': (c_int, 'pp' + 'iiiiiiii' + 'p'),
     'wesup_patch_scatter_u8': (c_int, 'pp' + 'iiiiiiiii' + 'p'),
     'wesup_mask_scores': (c_int, 'ppp' + 'li' + 'p'),
+    # weak-label preparation (csrc/prepare.hip)
+    'wesup_prepare_lds_entries': (c_int, 'i'),
+    'wesup_label_stats': (c_int, 'ppp' + 'iiii' + 'p'),
+    'wesup_sp_vote_workspace_bytes': (c_size_t, 'iiii'),
+    'wesup_sp_vote': (c_int, 'ppppp' + 'iiii' + 'pzp'),
+    'wesup_spl_paint_workspace_bytes': (c_size_t, 'ii'),
+    'wesup_spl_paint': (c_int, 'pppp' + 'iiiii' + 'pzp'),
     # entries by the names of SURVEY.md 8(b) (csrc/named.hip)
     'wesup_sp_stats': (c_int, 'ppiiiipppp'),
     'wesup_conv1x1_workspace_bytes': (c_size_t, 'iii'),

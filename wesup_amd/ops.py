@@ -1577,3 +1577,82 @@ def mask_scores(S, G, negative=False, out=None):
     _lib.call('wesup_mask_scores', _p(S), _p(G), _p(out), S.numel(), int(bool(negative)), _stream())
     _tend(tok, 2.0 * S.numel())
     return out
+
+
+# ---------------------------------------------------------------- weak-label preparation (csrc/prepare.hip)
+LABEL_STATS_MAX_LABELS = 1 << 26     # labels 0 .. L with L below this
+SP_VOTE_MAX_PIXELS = ((1 << 32) - 1) // 255      # 32-bit sums of uint8 values
+
+
+def prepare_lds_entries():
+    """(labels of label_stats, ids of sp_vote) up to which a block keeps its table in LDS; above, the adds go to global memory."""
+    lib = _lib.load()
+    return lib.wesup_prepare_lds_entries(0), lib.wesup_prepare_lds_entries(1)
+
+
+def _labels3(labels, name):
+    _chk(labels, torch.int32, 'labels')
+    if labels.dim() not in (2, 3) or labels.numel() < 1:
+        raise _lib.WesupHipError(f'{name}: expected (H,W) or (B,H,W), got {tuple(labels.shape)}')
+    return (labels.unsqueeze(0), True) if labels.dim() == 2 else (labels, False)
+
+
+def label_stats(labels, L):
+    """labels (H,W) / (B,H,W) int32 in [0, L] -> (stats (B, L+1, 3) int64 = pixels, sum of row indexes, sum of column indexes per
+    label (the batch axis only for batched input); status (B,) int32, bit 0 set for a label outside [0, L])."""
+    lab, squeeze = _labels3(labels, 'label_stats')
+    B, H, W = lab.shape
+    L = int(L)
+    if L < 0 or L >= LABEL_STATS_MAX_LABELS:
+        raise _lib.WesupHipError(f'label_stats: {L} labels (below {LABEL_STATS_MAX_LABELS})')
+    stats = torch.empty(B, L + 1, 3, dtype=torch.int64, device=lab.device)
+    status = torch.empty(B, dtype=torch.int32, device=lab.device)
+    tok = _tbegin('label_stats')
+    _lib.call('wesup_label_stats', _p(lab), _p(stats), _p(status), B, H, W, L, _stream())
+    _tend(tok, 4.0 * lab.numel())
+    return (stats[0] if squeeze else stats), status
+
+
+def sp_vote(labels, values, K, paint=True):
+    """Every superpixel of labels (H,W) / (B,H,W) int32 in [0, K) votes the rounded mean (half to even) of its pixels of values
+    (uint8, same shape) -> (painted uint8 of the same shape or None without ``paint``; agree (B,) int64, the pixels whose painted
+    value equals their own; status (B,) int32, bit 0 set for a label outside [0, K))."""
+    lab, squeeze = _labels3(labels, 'sp_vote')
+    _chk(values, torch.uint8, 'values')
+    if values.shape != labels.shape or values.device != labels.device:
+        raise _lib.WesupHipError(f'sp_vote: labels {tuple(labels.shape)} and values {tuple(values.shape)}')
+    B, H, W = lab.shape
+    K = int(K)
+    if K < 1 or K > LABEL_STATS_MAX_LABELS or H * W > SP_VOTE_MAX_PIXELS:
+        raise _lib.WesupHipError(f'sp_vote: K = {K}, {H} x {W} pixels (K in [1, 2^26], at most {SP_VOTE_MAX_PIXELS} pixels)')
+    painted = torch.empty(B, H, W, dtype=torch.uint8, device=lab.device) if paint else None
+    agree = torch.empty(B, dtype=torch.int64, device=lab.device)
+    status = torch.empty(B, dtype=torch.int32, device=lab.device)
+    nb = _lib.load().wesup_sp_vote_workspace_bytes(B, H, W, K)
+    ws = workspace(nb, lab.device, 'prepare')
+    tok = _tbegin('sp_vote')
+    _lib.call('wesup_sp_vote', _p(lab), _p(values), _p(painted), _p(agree), _p(status), B, H, W, K, _p(ws), nb, _stream())
+    _tend(tok, 11.0 * lab.numel())
+    if paint and squeeze:
+        painted = painted[0]
+    return painted, agree, status
+
+
+def spl_paint(labels, points, K, n_classes=2):
+    """labels (H,W) int32 in [0, K), points (P,3) int32 rows of (row, col, class) inside the image and the classes -> (out (H,W,C)
+    uint8, 1 where a point of class c lies in the pixel's superpixel; status (1,) int32: bit 0 a label outside [0, K), bit 1 a
+    point outside the image or the classes)."""
+    _chk(labels, torch.int32, 'labels')
+    _chk(points, torch.int32, 'points')
+    if labels.dim() != 2 or labels.numel() < 1 or points.dim() != 2 or points.shape[1] != 3 or points.device != labels.device:
+        raise _lib.WesupHipError(f'spl_paint: labels {tuple(labels.shape)}, points {tuple(points.shape)}')
+    H, W = labels.shape
+    K, C, P = int(K), int(n_classes), points.shape[0]
+    if K < 1 or C < 1 or C > 256 or K * C > LABEL_STATS_MAX_LABELS:
+        raise _lib.WesupHipError(f'spl_paint: K = {K}, {C} classes')
+    out = torch.empty(H, W, C, dtype=torch.uint8, device=labels.device)
+    status = torch.empty(1, dtype=torch.int32, device=labels.device)
+    nb = _lib.load().wesup_spl_paint_workspace_bytes(K, C)
+    ws = workspace(nb, labels.device, 'prepare')
+    _lib.call('wesup_spl_paint', _p(labels), _p(points) if P else None, _p(out), _p(status), H, W, K, C, P, _p(ws), nb, _stream())
+    return out, status
