@@ -66,13 +66,17 @@ def oracle_pred(seed, H, W):
         return orc.pixel_inference(torch_weights(), image(seed, H, W))
 
 
-@pytest.fixture(scope='module')
-def model():
+def make_model():
     from wesup_amd.models.wesup import WESUPPixelInference
     m = WESUPPixelInference().to(dev())
     m.load_state_dict({k: torch.from_numpy(v) for k, v in weights().items()})
     m.eval()
     return m
+
+
+@pytest.fixture(scope='module')
+def model():
+    return make_model()
 
 
 def check_probabilities(case, out, ref):
@@ -138,6 +142,19 @@ def test_plane_resize_reads_class_one_in_place():
     ops.plane_resize_acc(pred[..., 1].contiguous(), packed, alpha=0.5)
     assert torch.equal(strided, packed)
     assert not torch.equal(strided, ops.plane_resize_acc(pred[..., 0], torch.empty_like(packed), alpha=0.5))
+
+
+def test_resizes_keep_their_recorded_bits():
+    """tests/golden/resize_bits.npz (tools/make_resize_golden.py): 19 x 23 -> 11 x 29, down on one axis and up on the other.  The
+    blends are written with their roundings (bilinear.hpp) and slide.hip's kernels are bit-equal to these: the bits are pinned."""
+    import os
+    from wesup_amd import ops
+    gold = np.load(os.path.join(os.path.dirname(__file__), 'golden', 'resize_bits.npz'))
+    image_out = ops.image_resize_u8(torch.from_numpy(gold['img']).to(dev()), *gold['image_out'].shape[2:])
+    assert torch.equal(image_out.cpu(), torch.from_numpy(gold['image_out']))
+    plane_out = torch.from_numpy(gold['base']).to(dev())
+    ops.plane_resize_acc(torch.from_numpy(gold['pred']).to(dev())[..., 1], plane_out, alpha=1 / 3, accumulate=True)
+    assert torch.equal(plane_out.cpu(), torch.from_numpy(gold['plane_out']))
 
 
 # ---------------------------------------------------------------- 2. the per-resolution gather
@@ -234,7 +251,36 @@ def test_forward_per_resolution_leaves_the_engine_alone(model):
     assert torch.equal(model(x), before)
 
 
-# ---------------------------------------------------------------- 4. the driver
+# ---------------------------------------------------------------- 4. backbone() is the conv chain of forward()
+@pytest.mark.parametrize('switches', [{}, {'conv_winograd': False}, {'plain': True}], ids=['default', 'direct', 'plain'])
+def test_backbone_taps_equal_forward_taps(switches):
+    """The thirteen taps of ``engine.backbone`` against those an evaluation ``engine.forward`` leaves, bit for bit: default
+    switches (Winograd layers, their pooling in the output transform), every layer in the direct form (max-pool launches), and
+    the plain walk.  70 x 50 pools to odd sizes (35 -> 17, 25 -> 12)."""
+    from wesup_amd import ops
+    m = make_model()
+    m._ensure_engine()
+    eng = m.engine
+    for name, value in switches.items():
+        assert hasattr(eng, name)
+        setattr(eng, name, value)
+    for B, H, W in ((2, 48, 80), (1, 70, 50)):
+        x = torch.cat([image(8 + i, H, W) for i in range(B)]).to(dev())
+        labels = torch.zeros(B, H, W, dtype=torch.int32, device=dev())        # one dummy superpixel per image (forward_batch)
+        meta = ops.sp_preprocess(labels, None, 1, n_sp_host=[1] * B)
+        with torch.no_grad():
+            eng.forward(x, meta, train=False, need_paint=False)
+            ys = eng.backbone(x)
+        taps = eng._last.y
+        assert len(ys) == len(taps) == 13
+        if 'conv_winograd' in switches:
+            assert not any(eng.route(B, H, W))
+        for l in range(13):
+            assert ys[l] is not taps[l] and ys[l].data_ptr() != taps[l].data_ptr()
+            assert torch.equal(ys[l], taps[l]), f'{switches} {(B, H, W)}: tap {l} differs'
+
+
+# ---------------------------------------------------------------- 5. the driver
 DRIVER_CASES = {'64x96': (64, 96, (0.5, 1.0), 0.72), '80x116': (80, 116, (0.4, 0.6), 0.46)}
 
 

@@ -16,6 +16,11 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline size_t align_up(size_t a, size_t b) { return (a + b - 1) / b * b; }
+// Blocks of a grid-stride kernel over `total` elements, one per thread up to max_blocks blocks; at least 1.
+static inline unsigned grid_stride_blocks(long total, int block, int max_blocks) {
+    const long nb = (total + block - 1) / block;
+    return (unsigned)(nb > max_blocks ? max_blocks : (nb < 1 ? 1 : nb));
+}
 
 // Exact n / d for n*d < 2^40 via one 64-bit multiply (n < 2^26 pixels, d < 2^12 here).
 struct FastDiv {

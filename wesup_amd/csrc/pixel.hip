@@ -1,7 +1,7 @@
 // Whole-image multi-scale pixel inference: the two resizes at the ends of a scale -- uint8 image down to the
 // network input, class-1 probability back up and into the mean over the scales -- and the gather that makes the first fc
 // layer's output from per-resolution products.  All three are memory movement with a few multiply-adds per element: no LDS,
-// no atomics, no workspace, deterministic.  Coordinates: lerp_of / ac_scale (bilinear.hpp), as every other resampling kernel.
+// no atomics, no workspace, deterministic.  Coordinates (lerp_of / ac_scale) and blends (blend_image, blend_plane): bilinear.hpp.
 #include "common.hpp"
 #include "bilinear.hpp"
 
@@ -9,10 +9,6 @@
 #define PX_MAX_BLOCKS 4096     // grid-stride above this (cdna_hip_programming.md, guideline 11)
 
 namespace {
-
-__device__ __forceinline__ float bilerp(const Lerp ly, const Lerp lx, float v00, float v01, float v10, float v11) {
-    return ly.l0 * (lx.l0 * v00 + lx.l1 * v01) + ly.l1 * (lx.l0 * v10 + lx.l1 * v11);
-}
 
 // out[c][y][x] = bilinear_ac(img[.][.][c] / 255.f)(y, x): to_tensor followed by F.interpolate.  One thread per output pixel and
 // all three planes (the 12 bytes of its four corners sit in two short runs); stores of neighbouring lanes are neighbours.
@@ -28,7 +24,7 @@ __global__ __launch_bounds__(PX_BLOCK) void px_image_resize_kernel(const uint8_t
         for (int c = 0; c < 3; ++c) {
             const float v00 = (float)r0[lx.i0 * 3 + c] / 255.f, v01 = (float)r0[lx.i1 * 3 + c] / 255.f;
             const float v10 = (float)r1[lx.i0 * 3 + c] / 255.f, v11 = (float)r1[lx.i1 * 3 + c] / 255.f;
-            out[c * total + idx] = bilerp(ly, lx, v00, v01, v10, v11);
+            out[c * total + idx] = blend_image(ly, lx, v00, v01, v10, v11);
         }
     }
 }
@@ -44,8 +40,8 @@ __global__ __launch_bounds__(PX_BLOCK) void px_plane_resize_kernel(const float* 
         const Lerp ly = lerp_of(Y, sh, h), lx = lerp_of(X, sw, w);
         const float* r0 = in + (long)ly.i0 * w * stride;
         const float* r1 = in + (long)ly.i1 * w * stride;
-        const float v = alpha * bilerp(ly, lx, r0[(long)lx.i0 * stride], r0[(long)lx.i1 * stride], r1[(long)lx.i0 * stride],
-                                       r1[(long)lx.i1 * stride]);
+        const float v = alpha * blend_plane(ly, lx, r0[(long)lx.i0 * stride], r0[(long)lx.i1 * stride], r1[(long)lx.i0 * stride],
+                                            r1[(long)lx.i1 * stride]);
         out[idx] = accumulate ? out[idx] + v : v;
     }
 }
@@ -69,10 +65,10 @@ WESUP_NO_PADDING(PixLevels, 4 * 8 + 4 * 4 * 4);
 namespace {
 
 __device__ __forceinline__ float4 fma_bilerp(float4 acc, const Lerp ly, const Lerp lx, float4 a0, float4 a1, float4 b0, float4 b1) {
-    acc.x += bilerp(ly, lx, a0.x, a1.x, b0.x, b1.x);
-    acc.y += bilerp(ly, lx, a0.y, a1.y, b0.y, b1.y);
-    acc.z += bilerp(ly, lx, a0.z, a1.z, b0.z, b1.z);
-    acc.w += bilerp(ly, lx, a0.w, a1.w, b0.w, b1.w);
+    acc.x += blend_image(ly, lx, a0.x, a1.x, b0.x, b1.x);
+    acc.y += blend_image(ly, lx, a0.y, a1.y, b0.y, b1.y);
+    acc.z += blend_image(ly, lx, a0.z, a1.z, b0.z, b1.z);
+    acc.w += blend_image(ly, lx, a0.w, a1.w, b0.w, b1.w);
     return acc;
 }
 
@@ -149,17 +145,12 @@ __global__ __launch_bounds__(PX_BLOCK) void px_gather_kernel(const float* p0, co
     }
 }
 
-inline unsigned px_blocks(long total) {
-    const long nb = (total + PX_BLOCK - 1) / PX_BLOCK;
-    return (unsigned)(nb > PX_MAX_BLOCKS ? PX_MAX_BLOCKS : nb);
-}
-
 }  // namespace
 
 extern "C" int wesup_image_resize_u8(const uint8_t* img, float* out, int H, int W, int h, int w, void* stream) {
     if (!img || !out || H <= 0 || W <= 0 || h <= 0 || w <= 0) return WESUP_ERR_INVALID;
-    WESUP_LAUNCH(px_image_resize_kernel, dim3(px_blocks((long)h * w)), dim3(PX_BLOCK), 0, (hipStream_t)stream, img, out, H, W, h, w,
-                 ac_scale(H, h), ac_scale(W, w));
+    WESUP_LAUNCH(px_image_resize_kernel, dim3(grid_stride_blocks((long)h * w, PX_BLOCK, PX_MAX_BLOCKS)), dim3(PX_BLOCK), 0,
+                 (hipStream_t)stream, img, out, H, W, h, w, ac_scale(H, h), ac_scale(W, w));
     WESUP_CHECK_LAUNCH();
     return WESUP_OK;
 }
@@ -167,8 +158,8 @@ extern "C" int wesup_image_resize_u8(const uint8_t* img, float* out, int H, int 
 extern "C" int wesup_plane_resize_acc(const float* in, float* out, int h, int w, int H, int W, int stride, float alpha,
                                       int accumulate, void* stream) {
     if (!in || !out || h <= 0 || w <= 0 || H <= 0 || W <= 0 || stride <= 0) return WESUP_ERR_INVALID;
-    WESUP_LAUNCH(px_plane_resize_kernel, dim3(px_blocks((long)H * W)), dim3(PX_BLOCK), 0, (hipStream_t)stream, in, out, h, w, H, W,
-                 stride, alpha, accumulate ? 1 : 0, ac_scale(h, H), ac_scale(w, W));
+    WESUP_LAUNCH(px_plane_resize_kernel, dim3(grid_stride_blocks((long)H * W, PX_BLOCK, PX_MAX_BLOCKS)), dim3(PX_BLOCK), 0,
+                 (hipStream_t)stream, in, out, h, w, H, W, stride, alpha, accumulate ? 1 : 0, ac_scale(h, H), ac_scale(w, W));
     WESUP_CHECK_LAUNCH();
     return WESUP_OK;
 }

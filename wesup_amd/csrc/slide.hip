@@ -13,22 +13,6 @@
 
 namespace {
 
-// The blends of pixel.hip's two resizes, with the roundings written out.  pixel.hip states both as
-//     ly.l0 * (lx.l0 * v00 + lx.l1 * v01) + ly.l1 * (lx.l0 * v10 + lx.l1 * v11)
-// and leaves the contraction into fused multiply-adds to the compiler, which picks another one in each kernel; the results here
-// are held to those kernels bit for bit (tests/test_slide_gpu.py), so each form is spelled with explicit fmaf and no contraction
-// beyond it.  px_image_resize_kernel: three fused steps.  px_plane_resize_kernel: the rows fused, the sum of the two rows not.
-__device__ __forceinline__ float blend_image(const Lerp ly, const Lerp lx, float v00, float v01, float v10, float v11) {
-#pragma clang fp contract(off)
-    const float a = __builtin_fmaf(lx.l0, v00, lx.l1 * v01), b = __builtin_fmaf(lx.l0, v10, lx.l1 * v11);
-    return __builtin_fmaf(ly.l0, a, ly.l1 * b);
-}
-__device__ __forceinline__ float blend_plane(const Lerp ly, const Lerp lx, float v00, float v01, float v10, float v11) {
-#pragma clang fp contract(off)
-    const float a = __builtin_fmaf(lx.l1, v01, lx.l0 * v00), b = __builtin_fmaf(lx.l1, v11, lx.l0 * v10);
-    return ly.l0 * a + ly.l1 * b;
-}
-
 // out[n][c][y][x] = bilinear(patch_k / 255.f)(y, x), k = min(first + n, last): one thread per output pixel and all three planes,
 // x fastest across lanes (the three plane stores of a wave are 256 contiguous bytes each).  The neighbour indices are clamped
 // at the PATCH border (lerp_of on p texels); a texel beyond the slide border reads as 0 -- pad, then resize.
@@ -161,11 +145,6 @@ __global__ __launch_bounds__(SD_BLOCK) void sd_scores_kernel(const uint8_t* __re
     }
 }
 
-inline unsigned sd_blocks(long total) {
-    const long b = (total + SD_BLOCK - 1) / SD_BLOCK;
-    return (unsigned)(b > SD_MAX_BLOCKS ? SD_MAX_BLOCKS : (b < 1 ? 1 : b));
-}
-
 // the lattice of an (H, W) slide under patch size p; false when a size is outside what the kernels index (see the header)
 inline bool sd_lattice(int H, int W, int p, int* n_w, int* last) {
     const int LIM = 1 << 30;
@@ -186,7 +165,7 @@ extern "C" int wesup_patch_gather_resize(const uint8_t* img, float* out, int H, 
         !sd_lattice(H, W, p, &n_w, &last) || (long)first + count > 0x7fffffffl)
         return WESUP_ERR_INVALID;
     hipStream_t st = (hipStream_t)stream;
-    const dim3 grid(sd_blocks((long)count * h * w)), block(SD_BLOCK);
+    const dim3 grid(grid_stride_blocks((long)count * h * w, SD_BLOCK, SD_MAX_BLOCKS)), block(SD_BLOCK);
     if (align_corners) {
         WESUP_LAUNCH(sd_gather_kernel<1>, grid, block, 0, st, img, out, H, W, n_w, last, p, h, w, first, count, ac_scale(p, h),
                      ac_scale(p, w));
@@ -205,7 +184,7 @@ extern "C" int wesup_patch_scatter_u8(const float* pred, uint8_t* out, int H, in
         !sd_lattice(H, W, p, &n_w, &last) || (long)first + count > 0x7fffffffl)
         return WESUP_ERR_INVALID;
     hipStream_t st = (hipStream_t)stream;
-    const dim3 grid(sd_blocks((long)count * p * p)), block(SD_BLOCK);
+    const dim3 grid(grid_stride_blocks((long)count * p * p, SD_BLOCK, SD_MAX_BLOCKS)), block(SD_BLOCK);
     if (mode == 0) {
         WESUP_LAUNCH(sd_scatter_kernel<0>, grid, block, 0, st, pred, out, H, W, n_w, last, p, h, w, stride, first, count,
                      hp_scale(h, p), hp_scale(w, p));
@@ -224,8 +203,8 @@ extern "C" int wesup_mask_scores(const uint8_t* S, const uint8_t* G, int64_t* ou
     const bool aligned = ((((uintptr_t)S) | ((uintptr_t)G)) & 15) == 0;
     const long nvec = aligned ? n / 16 : 0;
     const long work = nvec + (n - nvec * 16);
-    WESUP_LAUNCH(sd_scores_kernel, dim3(sd_blocks(work)), dim3(SD_BLOCK), 0, st, S, G, reinterpret_cast<unsigned long long*>(out4),
-                 n, nvec, negative ? 0xffffffffu : 0u);
+    WESUP_LAUNCH(sd_scores_kernel, dim3(grid_stride_blocks(work, SD_BLOCK, SD_MAX_BLOCKS)), dim3(SD_BLOCK), 0, st, S, G,
+                 reinterpret_cast<unsigned long long*>(out4), n, nvec, negative ? 0xffffffffu : 0u);
     WESUP_CHECK_LAUNCH();
     return WESUP_OK;
 }

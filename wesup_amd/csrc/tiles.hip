@@ -97,11 +97,6 @@ __global__ __launch_bounds__(TL_BLOCK) void tl_merge_kernel(const float* __restr
     }
 }
 
-inline unsigned tl_blocks(long total) {
-    const long b = (total + TL_BLOCK - 1) / TL_BLOCK;
-    return (unsigned)(b > TL_MAX_BLOCKS ? TL_MAX_BLOCKS : b);
-}
-
 }  // namespace
 
 extern "C" int wesup_window_gather(const uint8_t* img, const int32_t* tops, const int32_t* lefts, float* out, int H, int W,
@@ -111,11 +106,11 @@ extern "C" int wesup_window_gather(const uint8_t* img, const int32_t* tops, cons
         return WESUP_ERR_INVALID;
     hipStream_t st = (hipStream_t)stream;
     if (p % 4 == 0) {
-        WESUP_LAUNCH(tl_gather_kernel<4>, dim3(tl_blocks((long)count * p * (p / 4))), dim3(TL_BLOCK), 0, st, img, tops, lefts, out,
-                     H, W, n_h, n_w, p, first, count);
+        WESUP_LAUNCH(tl_gather_kernel<4>, dim3(grid_stride_blocks((long)count * p * (p / 4), TL_BLOCK, TL_MAX_BLOCKS)),
+                     dim3(TL_BLOCK), 0, st, img, tops, lefts, out, H, W, n_h, n_w, p, first, count);
     } else {
-        WESUP_LAUNCH(tl_gather_kernel<1>, dim3(tl_blocks((long)count * p * p)), dim3(TL_BLOCK), 0, st, img, tops, lefts, out, H, W,
-                     n_h, n_w, p, first, count);
+        WESUP_LAUNCH(tl_gather_kernel<1>, dim3(grid_stride_blocks((long)count * p * p, TL_BLOCK, TL_MAX_BLOCKS)), dim3(TL_BLOCK),
+                     0, st, img, tops, lefts, out, H, W, n_h, n_w, p, first, count);
     }
     WESUP_CHECK_LAUNCH();
     return WESUP_OK;
@@ -127,8 +122,8 @@ extern "C" int wesup_window_merge(const float* pred, const int32_t* tops, const 
         (long)n_h * n_w > 0x7fffffffl)
         return WESUP_ERR_INVALID;
     hipStream_t st = (hipStream_t)stream;
-    WESUP_LAUNCH(tl_merge_kernel, dim3(tl_blocks((long)H * W * C)), dim3(TL_BLOCK), 0, st, pred, tops, lefts, out, H, W, C, n_h,
-                 n_w, p, round_first ? 1 : 0);
+    WESUP_LAUNCH(tl_merge_kernel, dim3(grid_stride_blocks((long)H * W * C, TL_BLOCK, TL_MAX_BLOCKS)), dim3(TL_BLOCK), 0, st, pred,
+                 tops, lefts, out, H, W, C, n_h, n_w, p, round_first ? 1 : 0);
     WESUP_CHECK_LAUNCH();
     return WESUP_OK;
 }

@@ -263,18 +263,11 @@ class WesupEngine:
         return layer_plan.buffers(plan, b.groups, b.Kmax, self.D,
                                   lambda R, D: ops._lib.load().wesup_classifier_bwd_workspace_bytes(R, D))
 
-    def _get_bufs(self, B, H, W, Kmax, train):
-        """The buffer set of a shape, most recently used.  A new one is a bare record here -- its grouping and empty slots; _fit
-        creates the tensors -- so that what it will cost is known (its plan's table) before anything is allocated."""
-        key = (B, H, W, Kmax)
-        b = self._bufs.get(key)
-        if b is not None:
-            self._bufs.move_to_end(key)
-            return b
+    @staticmethod
+    def _empty_set(B, H, W, Kmax=0, groups=(), group_of=(None,) * 13):
+        """A buffer set of a shape with every slot empty (_hold fills them from a table); groups, group_of: layer_plan.groups_for."""
         b = _Bufs()
         b.shape, b.Kmax, b.dims = (B, H, W), Kmax, layer_plan.layer_dims(H, W)
-        # the matrix-form groups of this set (layer_plan.groups_for): a set keeps the grouping it was made with
-        groups, group_of = layer_plan.groups_for(B, H, W, Kmax, self._switches())
         b.group_of = list(group_of)
         b.groups = []
         for grp in groups:
@@ -286,6 +279,18 @@ class WesupEngine:
             setattr(b, name, [None] * 13)
         for name in ('x0', 'fm', 'sp_in', 'h1', 'h2', 'feats', 'sp_pred', 'pred', 'dfm', 'dV', 'dfeat', 'dh2', 'dh1', 'gsp', 'cls_part'):
             setattr(b, name, None)
+        return b
+
+    def _get_bufs(self, B, H, W, Kmax, train):
+        """The buffer set of a shape, most recently used.  A new one is a bare record here -- its grouping and empty slots; _fit
+        creates the tensors -- so that what it will cost is known (its plan's table) before anything is allocated."""
+        key = (B, H, W, Kmax)
+        b = self._bufs.get(key)
+        if b is not None:
+            self._bufs.move_to_end(key)
+            return b
+        # the matrix-form groups of this set (layer_plan.groups_for): a set keeps the grouping it was made with
+        b = self._empty_set(B, H, W, Kmax, *layer_plan.groups_for(B, H, W, Kmax, self._switches()))
         b.fm_valid = False
         b.s_valid = [False] * 13
         b.plans = {}                 # train -> (key, StepPlan): see _plan
@@ -310,15 +315,15 @@ class WesupEngine:
         return b
 
     def _fit(self, b, plan):
-        """Top set b up to what the walk under plan touches (its table): the one place a set's tensors are created, in front of
-        the walk's first launch.  Nothing is ever freed or shrunk -- a switch flipped on a live engine adds what the new plan
-        needs to what the set holds."""
+        """Top set b up to what the walk under plan touches (its table), in front of the walk's first launch.  Nothing is ever
+        freed or shrunk -- a switch flipped on a live engine adds what the new plan needs to what the set holds."""
         if b.fitted.get(plan.train) is not plan:
             self._hold(b, self._table(b, plan))
             b.fitted[plan.train] = plan
 
     def _hold(self, b, table):
-        """Create what set b does not hold of table (Buf records) with that shape."""
+        """Create what set b does not hold of table (Buf records) with that shape: the one place a set's tensors are created --
+        forward()'s and backward()'s through _fit, feature_maps()'s and backbone()'s with the entries they need."""
         for e in table:
             if e.name.startswith('g.'):
                 slots, k = vars(b.groups[e.layer]), e.name[2:]
@@ -508,13 +513,14 @@ class WesupEngine:
         """The tensor layer l's conv (forward and weight gradient) reads, by the plan's name for it."""
         return b.x0 if L.src == 'x0' else getattr(b, L.src)[l - 1]
 
-    def _side_2d(self, b, l, fm2d):
+    @staticmethod
+    def _side_2d(b, l):
         """Layer l's side output as a (pixels, C/2) matrix: its own buffer, or (unfused, full resolution) its slice of fm."""
         s_l = b.s[l]
         co = CONV_CH[l][1]
-        return fm2d[:, SIDE_OFF[l]:SIDE_OFF[l] + co // 2] if s_l is None else s_l.view(-1, co // 2)
+        return b.fm.view(-1, FM_CHANNELS)[:, SIDE_OFF[l]:SIDE_OFF[l] + co // 2] if s_l is None else s_l.view(-1, co // 2)
 
-    def _side_fwd(self, b, meta, l, L, fm2d):
+    def _side_fwd(self, b, meta, l, L):
         """Side branch of layer l: 1x1 conv on the pre-ReLU tap, then either the fused upsample+scatter-mean straight into the
         superpixel feature slice, or upsample into fm's channel slice (commuted: the pooling first, the 1x1 conv on its rows)."""
         B, H, W = b.shape
@@ -537,7 +543,7 @@ class WesupEngine:
                 T.end(tok, 2.0 * B * Kmax * co * (co // 2))
             elif not L.side_in_conv:
                 tok = T.begin('side_fwd')
-                ops.gemm_nt(b.y[l].view(B * h * w, co), ws, p[f'side_conv{off}.bias'], out=self._side_2d(b, l, fm2d))
+                ops.gemm_nt(b.y[l].view(B * h * w, co), ws, p[f'side_conv{off}.bias'], out=self._side_2d(b, l))
                 T.end(tok, 2.0 * B * h * w * co * (co // 2))
             if L.commuted or ('side_fwd_deep' in self._diag_skip and grp is not None):
                 pass
@@ -556,35 +562,18 @@ class WesupEngine:
                 ops.upsample_fwd(s_l, b.fm, off)
                 T.end(tok, 4.0 * B * H * W * (co // 2))
 
-    def forward(self, img, meta, train=True, need_paint=True, head=True):
-        """img (B,3,H,W) fp32 on the GPU, meta = ops.sp_preprocess(...).  Returns (feats, sp_pred, pred)
-        shaped (B,Kmax,D), (B,Kmax,2), (B,H,W); buffers are reused by the next call of the same shape."""
-        B, _, H, W = img.shape
-        Kmax = meta.Kmax
-        assert (meta.B, meta.H, meta.W) == (B, H, W)
+    def _check_device(self):
         if torch.cuda.current_device() != self.device.index:     # every launch goes to the CURRENT device's current stream
             raise RuntimeError(f'the model lives on {self.device} but the current device is cuda:{torch.cuda.current_device()}: '
                                'one process per GPU (torch.cuda.set_device) -- launches would go to the wrong device')
-        b = self._get_bufs(B, H, W, Kmax, train)
-        self._last = b
-        self._last_shape = (B, H, W)
-        plan = self._plan(b, train, self._route_of(B, H, W))
-        self._fit(b, plan)
-        pk = self._pack_weights(train, plan.route)
-        p = self.p
-        T = self.timer
-        ops.pack_input(img, b.x0)
-        if b.groups:
-            with self._OnSide(self):     # the side stream is idle until conv1_1 is done
-                tok = T.begin('interp_matrix')
-                for g in b.groups:
-                    ops.sp_interp_matrix(meta, g.h, g.w, out=g.Wm)
-                ops.transpose_batched([(g.Wm[i], g.WmT[i]) for g in b.groups for i in range(B)])
-                T.end(tok, 0.0)
-        fused = self.fuse_pool_fwd
+
+    def _conv_chain(self, b, plan, pk, side_fwd=None):
+        """The thirteen convolutions of a walk under plan, from the packed image b.x0 to the taps b.y (and the pooled / ReLU'd
+        copies, kept transforms, sign bits and pooling codes the plan asks for), on the weights pk.  side_fwd(l, L) queues the side
+        branch of layer l behind its conv -- or, deferred, behind the next layer's input transform; None: there is none."""
+        p, T = self.p, self.timer
+        B = b.shape[0]
         pending_side = None              # the side-branch work of the previous layer, when it is queued behind this layer's transform
-        b.fm_valid = not fused
-        fm2d = None if fused else b.fm.view(B * H * W, FM_CHANNELS)
         for l, L in enumerate(plan.layers):
             if l == 0 and pk.ready0:
                 ops.sync_wait(self.SLOT_W0)
@@ -592,7 +581,6 @@ class WesupEngine:
                 ops.sync_wait(self.SLOT_W)
             ci, co, h, w, m = L.ci, L.co, L.h, L.w, L.m
             idx = CONV_IDX[l]
-            b.s_valid[l] = not L.commuted
             x = self._input_of(b, l, L)
             yr = b.yr[l] if L.write_yr else None
             bits_out = b.mbits[l - 1] if L.write_bits else None
@@ -612,8 +600,7 @@ class WesupEngine:
                     pending_side = None
                 side = None
                 if L.side_in_conv:       # the side conv of the widest layers in the conv's epilogue, where the output tile sits in LDS anyway
-                    side = (p[f'side_conv{SIDE_OFF[l]}.weight'].view(co // 2, co), p[f'side_conv{SIDE_OFF[l]}.bias'],
-                            self._side_2d(b, l, fm2d))
+                    side = (p[f'side_conv{SIDE_OFF[l]}.weight'].view(co // 2, co), p[f'side_conv{SIDE_OFF[l]}.bias'], self._side_2d(b, l))
                 tok = T.begin('conv3x3_fwd')
                 ops.conv3x3_fwd(x, pk.wf[l], p[f'backbone.{idx}.bias'], co, relu_in=L.relu_in, out=b.y[l], out_relu=yr, side=side)
                 T.end(tok, 2.0 * B * h * w * co * ((3 if l == 0 else ci) * 9 + (co // 2 if L.side_in_conv else 0)))
@@ -621,16 +608,45 @@ class WesupEngine:
             # l + 1 (both read y_l); deferred until that transform has been queued (ops: after_transform), it runs beside the
             # layer's products instead -- a memory-bound kernel next to an MFMA-bound one.
             # (the deep layers too: deferring only the memory-bound shallow ones measured 0.03 ms worse)
-            if L.defer_side:
-                pending_side = lambda l=l, L=L: self._side_fwd(b, meta, l, L, fm2d)
+            if side_fwd is None:
+                pass
+            elif L.defer_side:
+                pending_side = lambda l=l, L=L: side_fwd(l, L)
             else:
-                self._side_fwd(b, meta, l, L, fm2d)
+                side_fwd(l, L)
             if L.pool and not m:
                 ops.maxpool2_fwd(b.y[l], b.yp[l], relu=plan.relu_stored)
         self._join_side()
+
+    def forward(self, img, meta, train=True, need_paint=True, head=True):
+        """img (B,3,H,W) fp32 on the GPU, meta = ops.sp_preprocess(...).  Returns (feats, sp_pred, pred)
+        shaped (B,Kmax,D), (B,Kmax,2), (B,H,W); buffers are reused by the next call of the same shape."""
+        B, _, H, W = img.shape
+        Kmax = meta.Kmax
+        assert (meta.B, meta.H, meta.W) == (B, H, W)
+        self._check_device()
+        b = self._get_bufs(B, H, W, Kmax, train)
+        self._last = b
+        self._last_shape = (B, H, W)
+        plan = self._plan(b, train, self._route_of(B, H, W))
+        self._fit(b, plan)
+        pk = self._pack_weights(train, plan.route)
+        p = self.p
+        T = self.timer
+        ops.pack_input(img, b.x0)
+        if b.groups:
+            with self._OnSide(self):     # the side stream is idle until conv1_1 is done
+                tok = T.begin('interp_matrix')
+                for g in b.groups:
+                    ops.sp_interp_matrix(meta, g.h, g.w, out=g.Wm)
+                ops.transpose_batched([(g.Wm[i], g.WmT[i]) for g in b.groups for i in range(B)])
+                T.end(tok, 0.0)
+        b.fm_valid = not self.fuse_pool_fwd
+        b.s_valid = [not L.commuted for L in plan.layers]
+        self._conv_chain(b, plan, pk, lambda l, L: self._side_fwd(b, meta, l, L))
         if train:
             self._pack_weights_bwd(pk)
-        if not fused:
+        if not self.fuse_pool_fwd:
             tok = T.begin('sp_pool_fwd')
             ops.sp_pool_fwd(b.fm, meta, out=b.sp_in)
             T.end(tok, 4.0 * B * (FM_CHANNELS * H * W + H * W + Kmax * FM_CHANNELS))
@@ -681,55 +697,32 @@ class WesupEngine:
     def backbone(self, img):
         """The thirteen convolutions of an evaluation walk and nothing else: img (B,3,H,W) fp32 on the GPU -> the pre-ReLU taps
         y[0..12], (B,h_l,w_l,co_l) NHWC.  No superpixel description, and none of the side-branch, interpolation-matrix,
-        scatter-mean, fc, classifier or paint launches of forward().  The convolutions take the forms forward(train=False) gives
-        them (same routing, same plan fields).  The taps live in a small cache of their own, keyed by shape and reused by the next
+        scatter-mean, fc, classifier or paint launches of forward().  The convolutions are forward(train=False)'s: the same
+        _conv_chain under the same routing and plan fields, without a side branch (tests/test_pixel_resolution_gpu.py holds the
+        taps of the two bit for bit).  The taps live in a small cache of their own, keyed by shape and reused by the next
         call of that shape: the buffer sets, plans and context of forward() / backward() are not touched."""
         B, _, H, W = img.shape
-        if torch.cuda.current_device() != self.device.index:
-            raise RuntimeError(f'the model lives on {self.device} but the current device is cuda:{torch.cuda.current_device()}: '
-                               'one process per GPU (torch.cuda.set_device) -- launches would go to the wrong device')
+        self._check_device()
         route = self._route_of(B, H, W)
         key = (self._switches(), route, ops.winograd_fused_min_blocks())
         cache = self._backbone_sets
         b = cache.get((B, H, W))
         if b is None or b.key != key:
-            b = _Bufs()
+            b = self._empty_set(B, H, W)
             b.key = key
-            # no layer is grouped and none is trained: only the forward fields of the plan are read here
-            b.plan = layer_plan.build((B, H, W), (None,) * 13, route, key[0], frozenset(), frozenset(), False,
-                                      ops.winograd_fused_supported, ops.winograd_bias_rows)
-            new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=self.device)
-            b.x0 = new(B, H, W, 4)
-            b.y = [new(B, L.h, L.w, L.co) for L in b.plan.layers]
-            b.yp = [new(B, L.h // 2, L.w // 2, L.co) if L.pool else None for L in b.plan.layers]
-            b.yr = [new(B, L.h, L.w, L.co) if L.write_yr else None for L in b.plan.layers]
+            # no layer is grouped, none is trained and none has a side branch (so no side conv in a conv's epilogue either): only
+            # the forward fields of the plan are read, and of its table the image and the three outputs of the convs
+            b.plan = layer_plan.build((B, H, W), b.group_of, route, key[0]._replace(fuse_side_fwd=False), frozenset(), frozenset(),
+                                      False, ops.winograd_fused_supported, ops.winograd_bias_rows)
+            self._hold(b, [e for e in self._table(b, b.plan) if e.name in ('x0', 'y', 'yp', 'yr')])
             cache.pop((B, H, W), None)
             while len(cache) >= self.MAX_BACKBONE_SHAPES:
                 cache.popitem(last=False)
             cache[(B, H, W)] = b
         cache.move_to_end((B, H, W))
-        plan = b.plan
         pk = self._pack_weights(False, route)
-        p, T = self.p, self.timer
         ops.pack_input(img, b.x0)
-        for l, L in enumerate(plan.layers):
-            if l == 0 and pk.ready0:
-                ops.sync_wait(self.SLOT_W0)
-            if l == 1 and pk.ready:
-                ops.sync_wait(self.SLOT_W)
-            x = self._input_of(b, l, L)
-            yr = b.yr[l] if L.write_yr else None
-            bias = p[f'backbone.{CONV_IDX[l]}.bias']
-            if L.m:
-                ops.conv3x3_fwd_winograd(x, pk.uf[l], bias, relu_in=L.relu_in, out=b.y[l], out_relu=yr, ws_tag='wino_main', timer=T,
-                                         out_pool=b.yp[l] if L.pool else None, pool_relu=plan.relu_stored, m=L.m)
-            else:
-                tok = T.begin('conv3x3_fwd')
-                ops.conv3x3_fwd(x, pk.wf[l], bias, L.co, relu_in=L.relu_in, out=b.y[l], out_relu=yr)
-                T.end(tok, 2.0 * B * L.h * L.w * L.co * (3 if l == 0 else L.ci) * 9)
-                if L.pool:
-                    ops.maxpool2_fwd(b.y[l], b.yp[l], relu=plan.relu_stored)
-        self._join_side()
+        self._conv_chain(b, b.plan, pk)
         return b.y
 
     # ------------------------------------------------------------------ backward

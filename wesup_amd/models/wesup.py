@@ -429,28 +429,15 @@ class WESUPPixelInference(WESUP):
     @torch.no_grad()
     def forward(self, x):
         """x (1,3,H,W) -> (H,W,C) class probabilities (models/wesup.py:382-400)."""
-        self._ensure_engine()
         if x.size(0) != 1:
             raise ValueError('pixel inference takes one image (models/wesup.py:386)')
-        x = x.contiguous().float()
-        H, W = x.size(2), x.size(3)
-        labels = torch.zeros(1, H, W, dtype=torch.int32, device=x.device)        # one dummy superpixel
-        meta = ops.sp_preprocess(labels, None, 1, n_sp_host=[1])
-        self.engine.forward(x, meta, train=False, need_paint=False)
-        fm = self.engine.feature_maps().view(H * W, FM_CHANNELS)                  # (HW, 2112), pixel-major
-        self.fm_size = (H, W)
-        p = self.engine.p
-        h1 = ops.gemm_nt(fm, p['fc_layers.0.weight'], p['fc_layers.0.bias'], flags=ops.RELU_OUT)
-        h2 = ops.gemm_nt(h1, p['fc_layers.2.weight'], p['fc_layers.2.bias'], flags=ops.RELU_OUT)
-        feats = ops.gemm_nt(h2, p['fc_layers.4.weight'], p['fc_layers.4.bias'], flags=ops.RELU_OUT)
-        pred = ops.classifier_fwd(feats, p['classifier.0.weight'], p['classifier.0.bias'])
-        return pred.view(H, W, -1)
+        return self.forward_batch(x)[0]
 
     @torch.no_grad()
     def forward_batch(self, x):
-        """x (B,3,h,w) -> (B,h,w,C) class probabilities: ``forward`` for several windows of one size in one pass (the
-        windows of infer_tile.pixel_predict_array_batched).  One backbone pass at batch B, then the same three GEMMs and the
-        classifier on the (B*h*w, 2112) view of the feature maps.
+        """x (B,3,h,w) -> (B,h,w,C) class probabilities: several windows of one size in one pass (the windows of
+        infer_tile.pixel_predict_array_batched; ``forward`` is this at B = 1).  One backbone pass at batch B, then the three fc
+        GEMMs and the classifier on the (B*h*w, 2112) view of the feature maps.
 
         Memory: the pixel-major feature maps, the two hidden layers and the head's output are roughly
         ``B * h * w * (2112 + 2 * 1024 + 34) * 4`` bytes on top of the engine's buffer set -- about 3.6 GB per 464 x 464
