@@ -462,6 +462,21 @@ int wesup_directed_hausdorff_sq(const int32_t* pairs, const int32_t* start_x, co
                                 const int32_t* bstart_y, const int32_t* bpix_y, int32_t* d2, int P, int H, int W, int LX, int LY,
                                 void* stream);
 
+/* ------------------------------------------------------------------ painted object comparisons (csrc/paint.hip)
+ * wesup_object_match: tables [B][nS + 1][nG + 1] as wesup_contingency writes them (nS, nG: the maxima of the batch), nS_dev /
+ * nG_dev [B]: each image's own object counts (wesup_cc_label's n_labels); cells outside an image's own counts are not read.
+ * match [B][nS + 1]: for a row p in 1..nS_dev[b] the column g >= 1 with 2 * table[p][g] > area[g] (area[g] = the sum of column g
+ * over the image's rows) of the largest area, the lowest g among equal areas, or max(nS_dev[b], nG_dev[b]) + p when there is
+ * none; 0 for row 0 and the rows past nS_dev[b]  (reference scripts/paint_masks.py:50-70). */
+size_t wesup_object_match_workspace_bytes(int B, int nG);
+int wesup_object_match(const int32_t* table, const int32_t* nS_dev, const int32_t* nG_dev, int32_t* match, int B, int nS, int nG,
+                       void* ws, size_t ws_bytes, void* stream);
+/* out [B][HW][3] uint8 = the low three bytes (R, G, B in this order) of lut[b][labels[b][pixel]], lut [B][n_lut] one 32-bit word
+ * per label; a label outside [0, n_lut) is never used as an index: its pixel is black and status[b] |= 1 (status is zeroed
+ * here). */
+int wesup_label_paint(const int32_t* labels, const int32_t* lut, uint8_t* out, int32_t* status, int B, int HW, int n_lut,
+                      void* stream);
+
 /* ------------------------------------------------------------------ window inference on large images (csrc/tiles.hip)
  * The device ends of infer_tile.py: cutting an image into the network's input windows and merging the per-window predictions.
  * The window lattice is tops[n_h] x lefts[n_w] (int32, device memory, sorted, first 0, last size - p: infer_tile.window_grid);

@@ -121,6 +121,10 @@ _SIGS = {
     'wesup_label_sort_workspace_bytes': (c_size_t, 'iiii'),
     'wesup_label_sort': (c_int, 'pppppp' + 'iiii' + 'pzp'),
     'wesup_directed_hausdorff_sq': (c_int, 'ppppppp' + 'iiiii' + 'p'),
+    # painted object comparisons (csrc/paint.hip)
+    'wesup_object_match_workspace_bytes': (c_size_t, 'ii'),
+    'wesup_object_match': (c_int, 'pppp' + 'iii' + 'pzp'),
+    'wesup_label_paint': (c_int, 'pppp' + 'iii' + 'p'),
     # window inference on large images (csrc/tiles.hip)
     'wesup_window_gather': (c_int, 'pppp' + 'iiiiiii' + 'p'),
     'wesup_window_merge': (c_int, 'pppp' + 'iiiiiii' + 'p'),

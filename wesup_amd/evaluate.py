@@ -1,8 +1,9 @@
-"""GlaS evaluation: small-region post-processing of predicted masks, the challenge metrics over a directory of
-predictions, and the test-set driver (reference scripts/evaluate_glas.py:29-98 and test_glas.py:13-61;
-SURVEY.md 8(f) row 4).
+"""GlaS, CRAG and LUSC evaluation: small-region post-processing of predicted masks, the challenge metrics over a directory
+of predictions, and the test-set driver (reference scripts/evaluate_glas.py:29-98, scripts/evaluate_crag.py,
+scripts/evaluate_pdl1.py and test_glas.py:13-61).
 
   python -m wesup_amd.evaluate PRED_ROOT --gt-root ~/data/GLAS_all        # post-process + score testA / testB
+  python -m wesup_amd.evaluate PRED_ROOT --dataset crag [--gt-dir DIR]    # a flat directory, 5000-pixel rule (also: lusc)
   python -m wesup_amd.evaluate --test -c CKPT --scales 0.6,0.55,0.5,0.45,0.4 --data-root ~/data/GLAS_all
 
 Evaluation-time code on the CPU by default, as in the reference (numpy / scipy; the training step does not touch it).
@@ -17,6 +18,8 @@ import numpy as np
 from .utils import metrics as M
 
 MIN_REGION = 2000        # pixels (scripts/evaluate_glas.py:33,39)
+MIN_REGION_FLAT = 5000   # CRAG and LUSC (scripts/evaluate_crag.py:33,39, scripts/evaluate_pdl1.py:30,36)
+FLAT_GT_DIRS = {'crag': '~/data/CRAG/test/masks', 'lusc': 'LUSC/test/masks'}   # evaluate_crag.py:65 (its author's home), evaluate_pdl1.py:73
 
 
 def remove_small_regions(pred, min_size=MIN_REGION, device=None):
@@ -76,15 +79,10 @@ def score(predictions, gts, binarize_gt=False, device=None):
     return rows, means
 
 
-def evaluate_split(pred_dir, gt_dir, new_pred_dir=None, csv_path=None, min_size=MIN_REGION, log=print, device=None):
-    """One test split: read predictions (0/255 images) and ground-truth object maps in sorted order, post-process,
-    optionally save the new predictions and the per-image csv (columns of scripts/evaluate_glas.py:62-66)."""
+def _evaluate_paths(pred_paths, gt_paths, new_pred_dir, csv_path, min_size, log, device):
+    """Post-process the predictions (0/255 images), optionally save them, score them against the ground truth as read, log the
+    five means and optionally write the per-image csv -> (rows, means, post-processed predictions)."""
     from PIL import Image
-    exts = ('*.bmp', '*.png')
-    pred_paths = sorted(p for e in exts for p in Path(pred_dir).glob(e))
-    gt_paths = sorted(p for e in exts for p in Path(gt_dir).glob(e))
-    if len(pred_paths) != len(gt_paths):
-        raise ValueError(f'{len(pred_paths)} predictions in {pred_dir} but {len(gt_paths)} masks in {gt_dir}')
     predictions = [remove_small_regions(_read_mask(p) / 255, min_size, device) for p in pred_paths]
     gts = [_read_mask(p) for p in gt_paths]
     if new_pred_dir is not None:
@@ -101,7 +99,35 @@ def evaluate_split(pred_dir, gt_dir, new_pred_dir=None, csv_path=None, min_size=
             out.writerow(['', 'detection_f1', 'object_dice', 'object_hausdorff'])
             for path, r in zip(pred_paths, rows):
                 out.writerow([path.name, r['detection_f1'], r['object_dice'], r['object_hausdorff']])
-    return rows, means
+    return rows, means, predictions
+
+
+def evaluate_split(pred_dir, gt_dir, new_pred_dir=None, csv_path=None, min_size=MIN_REGION, log=print, device=None):
+    """One test split: read predictions (0/255 images) and ground-truth object maps in sorted order, post-process,
+    optionally save the new predictions and the per-image csv (columns of scripts/evaluate_glas.py:62-66)."""
+    exts = ('*.bmp', '*.png')
+    pred_paths = sorted(p for e in exts for p in Path(pred_dir).glob(e))
+    gt_paths = sorted(p for e in exts for p in Path(gt_dir).glob(e))
+    if len(pred_paths) != len(gt_paths):
+        raise ValueError(f'{len(pred_paths)} predictions in {pred_dir} but {len(gt_paths)} masks in {gt_dir}')
+    return _evaluate_paths(pred_paths, gt_paths, new_pred_dir, csv_path, min_size, log, device)[:2]
+
+
+def evaluate_flat(pred_root, gt_dir, min_size=MIN_REGION_FLAT, log=print, device=None, csv_path=None):
+    """scripts/evaluate_crag.py and scripts/evaluate_pdl1.py (one script but for the ground-truth directory): the ``*.png``
+    of ``pred_root`` against the ``*.png`` of ``gt_dir``, both sorted, the ground truth used as read; small regions and holes
+    below ``min_size`` = 5000 pixels are removed, the post-processed maps go to ``<pred_root>-new/`` and the five means are
+    logged in the reference's wording and order -> (rows, means, post-processed maps).
+
+    The one deliberate difference: the scoring is ``score``'s, whose Hausdorff term is ``nan`` for an image with an empty map and
+    whose means are ``nanmean`` -- the reference's ``np.mean`` of an ``inf`` there says nothing about the other images.  With every
+    map non-empty the numbers are the reference's."""
+    pred_root, gt_dir = Path(pred_root).expanduser(), Path(gt_dir).expanduser()
+    pred_paths, gt_paths = sorted(pred_root.glob('*.png')), sorted(gt_dir.glob('*.png'))
+    if len(pred_paths) != len(gt_paths):
+        raise ValueError(f'{len(pred_paths)} predictions in {pred_root} but {len(gt_paths)} masks in {gt_dir}')
+    new_root = pred_root.parent / (pred_root.name + '-new')
+    return _evaluate_paths(pred_paths, gt_paths, new_root, csv_path, min_size, log, device)
 
 
 def evaluate_glas(pred_root, gt_root='~/data/GLAS_all', min_size=MIN_REGION, log=print, device=None):
@@ -142,7 +168,11 @@ def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     ap.add_argument('pred_root', nargs='?')
     ap.add_argument('--gt-root', default='~/data/GLAS_all')
-    ap.add_argument('--min-size', type=int, default=MIN_REGION)
+    ap.add_argument('--dataset', choices=('glas', 'crag', 'lusc'), default='glas',
+                    help='glas: testA / testB under PRED_ROOT; crag, lusc: a flat directory of predictions')
+    ap.add_argument('--gt-dir', help='ground-truth masks of --dataset crag / lusc (default: ' +
+                                     ', '.join(f'{k}: {v}' for k, v in FLAT_GT_DIRS.items()) + ')')
+    ap.add_argument('--min-size', type=int, help=f'default: {MIN_REGION} for glas, {MIN_REGION_FLAT} for crag and lusc')
     ap.add_argument('--test', action='store_true', help='run the test-set driver (test_glas.py) instead of scoring')
     ap.add_argument('-m', '--model', default='wesup')
     ap.add_argument('-c', '--checkpoint')
@@ -155,8 +185,12 @@ def main(argv=None):
     if a.test:
         size = [int(s) for s in a.input_size.split(',')] if a.input_size else None
         test(a.checkpoint, a.model, size, tuple(float(s) for s in a.scales.split(',')), a.device, a.data_root)
+    elif a.dataset == 'glas':
+        evaluate_glas(a.pred_root, a.gt_root, MIN_REGION if a.min_size is None else a.min_size,
+                      device=a.device if a.gpu_scoring else None)
     else:
-        evaluate_glas(a.pred_root, a.gt_root, a.min_size, device=a.device if a.gpu_scoring else None)
+        evaluate_flat(a.pred_root, a.gt_dir or FLAT_GT_DIRS[a.dataset], MIN_REGION_FLAT if a.min_size is None else a.min_size,
+                      device=a.device if a.gpu_scoring else None)
 
 
 if __name__ == '__main__':

@@ -1358,6 +1358,52 @@ def directed_hausdorff_sq(pairs, X, Y):
     return d2
 
 
+# ---------------------------------------------------------------- painted object comparisons (csrc/paint.hip)
+LABEL_PAINT_MAX_LUT = 1 << 26        # entries of a colour table
+
+
+def object_match(table, nS_dev, nG_dev):
+    """table (nS+1, nG+1) / (B, nS+1, nG+1) int32 as ``contingency`` writes it, nS_dev / nG_dev (B,) int32 device tensors with
+    each image's own object counts (``cc_label``'s n_labels; cells outside them are not read) -> (B, nS+1) int32: the
+    ground-truth object every predicted object takes its colour from (paint.match_objects_from_table), 0 for row 0 and the rows
+    past an image's own count.  The batch axis only for batched input."""
+    _chk(table, torch.int32, 'table'); _chk(nS_dev, torch.int32, 'nS_dev'); _chk(nG_dev, torch.int32, 'nG_dev')
+    if table.dim() not in (2, 3) or table.shape[-1] < 1 or table.shape[-2] < 1:
+        raise _lib.WesupHipError(f'object_match: table {tuple(table.shape)}')
+    B = 1 if table.dim() == 2 else table.shape[0]
+    nS, nG = table.shape[-2] - 1, table.shape[-1] - 1
+    if B < 1 or (nS + 1) * (nG + 1) > CONTINGENCY_MAX_CELLS:
+        raise _lib.WesupHipError(f'object_match: {B} tables of {nS + 1} x {nG + 1} cells')
+    if tuple(nS_dev.shape) != (B,) or tuple(nG_dev.shape) != (B,) or nS_dev.device != table.device or nG_dev.device != table.device:
+        raise _lib.WesupHipError(f'object_match: counts {tuple(nS_dev.shape)} and {tuple(nG_dev.shape)} for {B} tables (one device)')
+    match = torch.empty(B, nS + 1, dtype=torch.int32, device=table.device)
+    nb = _lib.load().wesup_object_match_workspace_bytes(B, nG)
+    ws = workspace(nb, table.device, 'regions')
+    _lib.call('wesup_object_match', _p(table), _p(nS_dev), _p(nG_dev), _p(match), B, nS, nG, _p(ws), nb, _stream())
+    return match[0] if table.dim() == 2 else match
+
+
+def label_paint(labels, lut):
+    """labels (H,W) / (B,H,W) int32, lut (n_lut,) / (B, n_lut) int32 with one colour per label packed R | G << 8 | B << 16 ->
+    ((..., H, W, 3) uint8 interleaved RGB, status (B,) int32).  A label outside [0, n_lut) paints black and sets bit 0 of its
+    image's status; it is never used as an index."""
+    _chk(labels, torch.int32, 'labels'); _chk(lut, torch.int32, 'lut')
+    if labels.dim() not in (2, 3) or lut.dim() != labels.dim() - 1:
+        raise _lib.WesupHipError(f'label_paint: labels {tuple(labels.shape)}, lut {tuple(lut.shape)}')
+    single = labels.dim() == 2
+    B = 1 if single else labels.shape[0]
+    H, W = labels.shape[-2:]
+    n_lut = lut.shape[-1]
+    if B < 1 or H * W < 1 or n_lut < 1 or n_lut > LABEL_PAINT_MAX_LUT or (not single and lut.shape[0] != B):
+        raise _lib.WesupHipError(f'label_paint: labels {tuple(labels.shape)}, lut {tuple(lut.shape)}')
+    if lut.device != labels.device:
+        raise _lib.WesupHipError('label_paint: labels and lut on different devices')
+    out = torch.empty(B, H, W, 3, dtype=torch.uint8, device=labels.device)
+    status = torch.empty(B, dtype=torch.int32, device=labels.device)
+    _lib.call('wesup_label_paint', _p(labels), _p(lut), _p(out), _p(status), B, H * W, n_lut, _stream())
+    return (out[0] if single else out), status
+
+
 # ---------------------------------------------------------------- window inference on large images (csrc/tiles.hip)
 _lattice_cache = {}    # (device, axis positions) -> int32 device tensor: an image size meets the same few lattices again and again
 
