@@ -220,6 +220,17 @@ int wesup_winograd_gemm_output_transform_gather(const float* V, long plane_elems
 long wesup_winograd_bias_rows(int B, int H, int W, int C);
 int wesup_winograd_dual_transform(const float* dy, float* V, float* dM, float* bias_part, int B, int H, int W, int C,
                                   void* stream);
+/* The same for the gradient of a layer in front of a 2x2 max-pool, without that gradient in memory:
+ * dy(b,h,w,c) = side(b,h,w,c) + (code(b,h/2,w/2,c) picks this position of the window ? dP(b,h/2,w/2,c) : 0), formed while
+ * loading.  dP (B,H/2,W/2,C): the input gradient of the layer above at pooled resolution; code (B,H/2,W/2,C/4) uint16: the
+ * forward's pooling decisions (wesup_winograd_gemm_output_transform_ex's pool_code); H, W even.  side: the side-branch
+ * gradient, dense (B,H,W,C) with new_row NULL, or rows [B][Kmax][C] (divided by their areas already) gathered per pixel by
+ * new_row [B][H*W], as wesup_conv3x3_dgrad_winograd_gather takes them.  V, dM and bias_part equal wesup_winograd_dual_transform
+ * of the tensor the unpooling epilogues (wesup_conv3x3_dgrad_winograd_unpool / _gather) would have written, bit for bit.
+ * side, dP and the label map each below 4 GiB (WESUP_ERR_INVALID otherwise: the kernel's offsets are 32-bit). */
+int wesup_winograd_dual_transform_unpool(const float* side, const int32_t* new_row, int Kmax, const float* dP,
+                                         const unsigned short* code, float* V, float* dM, float* bias_part, int B, int H, int W,
+                                         int C, void* stream);
 int wesup_conv3x3_wgrad_winograd_pre(const float* v_pre, const float* dm_pre, const float* bias_part, int bias_rows,
                                      float* dw_kcrs, float* db, int B, int H, int W, int Ci, int Cout,
                                      void* ws, size_t ws_bytes, void* stream);

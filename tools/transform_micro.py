@@ -43,4 +43,18 @@ for l, div, ci, co in layers:
     by_du = 4.0 * (B * h * w * co + 2 * 36 * T * co)
     tot_in += mult[l] * t_in; tot_dual += mult[l] * t_du
     print(f'layer {l:2d} {h:4d}x{w:<4d} {ci:3d}->{co:3d}: input transform {t_in * 1e3:7.1f} us {by_in / t_in / 1e9:5.2f} TB/s   dual transform {t_du * 1e3:7.1f} us {by_du / t_du / 1e9:5.2f} TB/s')
+    if l in (1, 3):      # the pooled layers whose gradient the step never writes: winograd_dual_transform_unpool (gather / dense side)
+        dp = torch.randn(B, h // 2, w // 2, co, device=d)
+        k = torch.randint(0, 5, (B, h // 2, w // 2, co // 4), device=d)
+        code = (k | (k << 3) | (k << 6) | (k << 9)).to(torch.int16)
+        if l == 1:       # superpixels as 20 x 20 cells, rows of one superpixel each
+            Kmax = (h // 20) * (w // 20)
+            yy, xx = torch.meshgrid(torch.arange(h, device=d) // 20, torch.arange(w, device=d) // 20, indexing='ij')
+            new_row = (yy * (w // 20) + xx).to(torch.int32).view(1, h * w).repeat(B, 1).contiguous()
+            side, by_side = torch.randn(B, Kmax, co, device=d), 4.0 * B * (h * w + Kmax * co)
+        else:
+            new_row, side, by_side = None, dy, 4.0 * B * h * w * co
+        t_up = timed(lambda: ops.winograd_dual_transform_unpool(side, dp, code, dV, dM, bp, new_row=new_row))
+        by_up = by_side + 4.0 * dp.numel() + 2.0 * code.numel() + 4.0 * 2 * 36 * T * co
+        print(f'         {"gathered" if l == 1 else "dense"} side + unpooled dP on load: {t_up * 1e3:7.1f} us {by_up / t_up / 1e9:5.2f} TB/s')
 print(f'# per step (12 layers): input transforms {tot_in:.3f} ms, dual transforms {tot_dual:.3f} ms')

@@ -442,25 +442,11 @@ __device__ __forceinline__ bool wino4_decode(const WinoGeom& g, WinoTile& o) {
 // thread = (tile, 4 channels): 36 float4 loads (patch rows 4i-1 .. 4i+4), B^T d B, 36 float4 stores
 // bits (optional, [B][H][W][C/4] bytes): bit j of a byte = x[..., 4 cq + j] > 0 for the 4x4 pixels the tile owns (its
 // patch without the halo) -- the ReLU decisions of the layer below, kept for its backward (16x smaller than the mask tensor).
+// ... on the patch d (rows 4i-1 .. 4i+4, zeros outside the image) once it is in registers
 template <bool KEEP_CORE = false>
-__device__ __forceinline__ void wino4_input_body(const float* __restrict__ x, float* __restrict__ V, const WinoGeom& g,
-                                                 const WinoTile& q, int relu, unsigned char* __restrict__ bits,
-                                                 float4 (*core)[4] = nullptr) {
-    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-    // All 36 loads first, nothing between them: with the sign-bit stores in the same loop every load was followed by its own
-    // s_waitcnt (36 serial round trips per thread -- unnoticed alone, where other waves cover them, and the reason this kernel
-    // doubled its time beside the other streams' kernels).
-    float4 d[6][6];
-#pragma unroll
-    for (int c = 0; c < 6; ++c) {
-        const int w = 4 * q.j - 1 + c;
-#pragma unroll
-        for (int r = 0; r < 6; ++r) {
-            const int h = 4 * q.i - 1 + r;
-            const bool in = (unsigned)h < (unsigned)g.H && (unsigned)w < (unsigned)g.W;
-            d[r][c] = in ? ld4(x + (((long)q.b * g.H + h) * g.W + w) * g.C + 4 * q.cq) : z;
-        }
-    }
+__device__ __forceinline__ void wino4_input_patch(const float4 (&d)[6][6], float* __restrict__ V, const WinoGeom& g,
+                                                  const WinoTile& q, int relu, unsigned char* __restrict__ bits,
+                                                  float4 (*core)[4] = nullptr) {
     if constexpr (KEEP_CORE) {           // the tile's own 4x4 values for the caller (the dual transform's second half)
 #pragma unroll
         for (int r = 0; r < 4; ++r)
@@ -510,6 +496,27 @@ __device__ __forceinline__ void wino4_input_body(const float* __restrict__ x, fl
 #pragma unroll
         for (int c = 0; c < 6; ++c) st4s(out + (6 * r + c) * ps, o[c], g.nt);
     }
+}
+template <bool KEEP_CORE = false>
+__device__ __forceinline__ void wino4_input_body(const float* __restrict__ x, float* __restrict__ V, const WinoGeom& g,
+                                                 const WinoTile& q, int relu, unsigned char* __restrict__ bits,
+                                                 float4 (*core)[4] = nullptr) {
+    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+    // All 36 loads first, nothing between them: with the sign-bit stores in the same loop every load was followed by its own
+    // s_waitcnt (36 serial round trips per thread -- unnoticed alone, where other waves cover them, and the reason this kernel
+    // doubled its time beside the other streams' kernels).
+    float4 d[6][6];
+#pragma unroll
+    for (int c = 0; c < 6; ++c) {
+        const int w = 4 * q.j - 1 + c;
+#pragma unroll
+        for (int r = 0; r < 6; ++r) {
+            const int h = 4 * q.i - 1 + r;
+            const bool in = (unsigned)h < (unsigned)g.H && (unsigned)w < (unsigned)g.W;
+            d[r][c] = in ? ld4(x + (((long)q.b * g.H + h) * g.W + w) * g.C + 4 * q.cq) : z;
+        }
+    }
+    wino4_input_patch<KEEP_CORE>(d, V, g, q, relu, bits, core);
 }
 __global__ __launch_bounds__(256) void wino4_input_transform_kernel(const float* __restrict__ x, float* __restrict__ V,
                                                                     const WinoGeom g, int relu, unsigned char* __restrict__ bits) {
@@ -592,6 +599,119 @@ __global__ __launch_bounds__(256) void wino4_dual_transform_kernel(const float* 
         float4 core[4][4];           // dy is read once: the 16 values both transforms share stay in registers
         wino4_input_body<true>(dy, V, g, q, 0, nullptr, core);
         tot = wino4_outgrad_body<true>(dy, dM, g, q, core);
+    }
+    if (!colsum_part) return;            // uniform
+    wino4_block_colsum(tot, g, colsum_part, sh);
+}
+
+// The dual transform of a gradient that is never materialised: dY of a layer in front of a 2x2 max-pool is its side-branch
+// gradient plus the max-pool backward of dP, the input gradient of the layer above at pooled resolution -- what that layer's
+// unpooling epilogue (wino_unpool_add / wino_unpool_gather, winograd.hpp) wrote into the 4x larger tensor for this kernel to
+// read back.  Here a thread forms its 36 values from dP (16 windows: pooled rows 2i-1 .. 2i+2), their codes and the side
+// gradient: dense (B,H,W,C), or (GATHER) the row of its superpixel per pixel, as the gather epilogue reads it.  Same arithmetic
+// on the same values: side + picked, one add; the dense form leaves a position no channel of the quad picks untouched, as the
+// accumulating epilogue does.  H, W even.  Loads in levels, each issued whole before its first use (wino4_input_body): the
+// dense form has one (codes, dP, side values), the gather form two (codes, dP and label-map entries, then the rows); pixels
+// outside the image are clamped and predicated.
+template <bool GATHER>
+__device__ __forceinline__ void wino4_unpool_patch(float4 (&d)[6][6], const float* __restrict__ side,
+                                                   const float* __restrict__ dP, const unsigned short* __restrict__ code,
+                                                   const WinoGather& ga, const WinoGeom& g, const WinoTile& q,
+                                                   float4 (*park)[256]) {
+    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+    const int Hp = g.H >> 1, Wp = g.W >> 1, Q = g.C >> 2;
+    int ph[4], pw[4], hh[6], ww[6];      // pooled rows / columns 2i-1 .. 2i+2: patch rows (0), (1,2), (3,4), (5); patch rows / columns
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+        ph[p] = q.b * Hp + min(max(2 * q.i - 1 + p, 0), Hp - 1);
+        pw[p] = min(max(2 * q.j - 1 + p, 0), Wp - 1);
+    }
+#pragma unroll
+    for (int r = 0; r < 6; ++r) {
+        hh[r] = min(max(4 * q.i - 1 + r, 0), g.H - 1);
+        ww[r] = min(max(4 * q.j - 1 + r, 0), g.W - 1);
+    }
+    // Every address is a uniform base + an unsigned 32-bit byte offset (the entry checks that each tensor is below 4 GiB): one
+    // register per load in flight instead of a 64-bit pair -- with 64-bit addresses the compiler cut the loads into some
+    // twenty groups with a wait behind each.  Level 1: codes, dP and (GATHER) the label-map entries, none of which depends on
+    // another; level 2 (GATHER): the 36 rows.
+    unsigned cd[4][4], srow[6][6];
+    float4 dp[4][4];
+#pragma unroll
+    for (int pr = 0; pr < 4; ++pr)
+#pragma unroll
+        for (int pc = 0; pc < 4; ++pc)
+            cd[pr][pc] = *(const unsigned short*)((const char*)code + ((unsigned)(ph[pr] * Wp + pw[pc]) * Q + q.cq) * 2u);
+#pragma unroll
+    for (int r = 0; r < 6; ++r)
+#pragma unroll
+        for (int c = 0; c < 6; ++c) {
+            const unsigned pix = (unsigned)(q.b * g.H + hh[r]) * g.W + ww[c];
+            if constexpr (GATHER) srow[r][c] = *(const unsigned*)((const char*)ga.row + pix * 4u);
+            else srow[r][c] = pix;
+        }
+#pragma unroll
+    for (int pr = 0; pr < 4; ++pr)
+#pragma unroll
+        for (int pc = 0; pc < 4; ++pc)
+            dp[pr][pc] = *(const float4*)((const char*)dP + ((unsigned)(ph[pr] * Wp + pw[pc]) * g.C + 4 * q.cq) * 4u);
+    if constexpr (GATHER) {
+        // The rows wait for the label map, so level 1 is complete before level 2 can be issued: dP spends that second round trip
+        // in LDS (each thread its own 16 slots, consecutive threads consecutive quads: no conflicts, no barrier), and the rows
+        // are loaded without 64 registers of dP beside them.  (gfx950, this compiler: level 1 is one run of 68 loads; the
+        // kernel still sits at the 256-register limit of two waves per SIMD and spills 3 VGPRs)
+#pragma unroll
+        for (int pr = 0; pr < 4; ++pr)
+#pragma unroll
+            for (int pc = 0; pc < 4; ++pc) park[4 * pr + pc][threadIdx.x] = dp[pr][pc];
+    }
+    const float* sbase = GATHER ? ga.src : side;
+#pragma unroll
+    for (int r = 0; r < 6; ++r)
+#pragma unroll
+        for (int c = 0; c < 6; ++c) {
+            const unsigned row = GATHER ? q.b * ga.Kmax + srow[r][c] : srow[r][c];
+            d[r][c] = *(const float4*)((const char*)sbase + (row * g.C + 4 * q.cq) * 4u);
+        }
+#pragma unroll
+    for (int pr = 0; pr < 4; ++pr) {
+#pragma unroll
+        for (int pc = 0; pc < 4; ++pc) {      // window by window: rows 2 pr - 1, 2 pr and columns 2 pc - 1, 2 pc of the patch
+            const WinoPicks pk = wino_code_picks(cd[pr][pc]);
+            const float4 v = GATHER ? park[4 * pr + pc][threadIdx.x] : dp[pr][pc];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {     // position k of the window
+                const int r = 2 * pr - 1 + (k >> 1), c = 2 * pc - 1 + (k & 1);
+                if (r < 0 || r > 5 || c < 0 || c > 5) continue;
+                const int h = 4 * q.i - 1 + r, w = 4 * q.j - 1 + c;
+                const bool in = (unsigned)h < (unsigned)g.H && (unsigned)w < (unsigned)g.W;
+                float4 o = d[r][c];
+                if (GATHER || pk.kx == k || pk.ky == k || pk.kz == k || pk.kw == k) {
+                    o.x += pk.kx == k ? v.x : 0.f; o.y += pk.ky == k ? v.y : 0.f;
+                    o.z += pk.kz == k ? v.z : 0.f; o.w += pk.kw == k ? v.w : 0.f;
+                }
+                d[r][c] = in ? o : z;
+            }
+        }
+    }
+}
+template <bool GATHER>
+__global__ __launch_bounds__(256, 2) void wino4_dual_transform_unpool_kernel(const float* __restrict__ side,
+                                                                          const float* __restrict__ dP,
+                                                                          const unsigned short* __restrict__ code,
+                                                                          const WinoGather ga, float* __restrict__ V,
+                                                                          float* __restrict__ dM, const WinoGeom g,
+                                                                          float* __restrict__ colsum_part) {
+    __shared__ float4 sh[256];
+    __shared__ float4 park[GATHER ? 16 : 1][256];        // (GATHER: 64 KB, two blocks per CU)
+    WinoTile q;
+    const bool active = wino4_decode(g, q);
+    float4 tot = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (active) {
+        float4 d[6][6], core[4][4];
+        wino4_unpool_patch<GATHER>(d, side, dP, code, ga, g, q, park);
+        wino4_input_patch<true>(d, V, g, q, 0, nullptr, core);
+        tot = wino4_outgrad_body<true>(nullptr, dM, g, q, core);
     }
     if (!colsum_part) return;            // uniform
     wino4_block_colsum(tot, g, colsum_part, sh);
@@ -945,6 +1065,34 @@ extern "C" int wesup_winograd_dual_transform(const float* dy, float* V, float* d
     g.nt = wino_nt_stores(2 * 4.0 * 36 * g.T * C);      // (two transformed tensors per launch)
     const dim3 grid((unsigned)wino_transform_blocks(B, H, W, C, 4));
     WESUP_LAUNCH(wino4_dual_transform_kernel, grid, dim3(256), 0, (hipStream_t)stream, dy, V, dM, g, bias_part);
+    WESUP_CHECK_LAUNCH();
+    return WESUP_OK;
+}
+// wesup_winograd_dual_transform of dy = side + maxpool2_bwd(dP) without that tensor: dP (B,H/2,W/2,C) the gradient at pooled
+// resolution, code (B,H/2,W/2,C/4) the forward's pooling decisions (wino_code_picks), H and W even.  side: dense (B,H,W,C), or
+// (new_row given) rows [B][Kmax][C] gathered per pixel by new_row [B][H*W], divided by their areas already.
+extern "C" int wesup_winograd_dual_transform_unpool(const float* side, const int32_t* new_row, int Kmax, const float* dP,
+                                                    const unsigned short* code, float* V, float* dM, float* bias_part, int B,
+                                                    int H, int W, int C, void* stream) {
+    if (!side || !dP || !code || !V || !dM || !wino_shape_ok(B, H, W, C, C, 4) || (H & 1) || (W & 1) || (new_row && Kmax <= 0) ||
+        (((uintptr_t)side | (uintptr_t)dP | (uintptr_t)V | (uintptr_t)dM | (uintptr_t)bias_part) & 15) || ((uintptr_t)code & 1) ||
+        ((uintptr_t)new_row & 3) || (bias_part && !wino4_block_colsum_ok(C)))
+        return WESUP_ERR_INVALID;
+    // The kernel's byte offsets are 32-bit: the side gradient (rows or dense) below 4 GiB, and dP, whose B * H/2 * W/2 * C * 4 bytes
+    // are B * H * W * C; the codes (1/8 of dP's bytes) and the label map (B * H * W * 4 <= dP's bytes for C >= 4) are smaller.
+    if ((long)B * (new_row ? Kmax : H * W) * C * 4 >= (1l << 32) || (long)B * H * W * C >= (1l << 32)) return WESUP_ERR_INVALID;
+    WinoGeom g = wino_geom(B, H, W, C, 4);
+    g.nt = wino_nt_stores(2 * 4.0 * 36 * g.T * C);      // (two transformed tensors per launch)
+    const dim3 grid((unsigned)wino_transform_blocks(B, H, W, C, 4));
+    if (new_row) {
+        const WinoGather ga = {side, new_row, nullptr, Kmax, 0, (long)H * W};
+        WESUP_LAUNCH(wino4_dual_transform_unpool_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, side, dP, code, ga, V, dM, g,
+                     bias_part);
+    } else {
+        const WinoGather ga = {nullptr, nullptr, nullptr, 0, 0, 0};
+        WESUP_LAUNCH(wino4_dual_transform_unpool_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, side, dP, code, ga, V, dM, g,
+                     bias_part);
+    }
     WESUP_CHECK_LAUNCH();
     return WESUP_OK;
 }

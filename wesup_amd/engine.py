@@ -176,6 +176,9 @@ class WesupEngine:
     fuse_unpool = property(lambda self: not self.plain)
     matrix_pool = True          # coarse layers: upsample + scatter-mean (and backward) as GEMMs with the interpolation-pooling matrix
     fuse_side_fwd = True        # side conv of a direct-form layer with <= 128 output channels inside its conv epilogue (where not commuted)
+    # 1: the gradient of a pooled layer whose transform is the dual one is never written -- the input gradient of the layer above
+    # stays at pooled resolution and the transform unpools it while loading (layer_plan: dp_on_load); 0: the unpooling epilogues
+    unpool_on_load = 1
 
     # ------------------------------------------------------------------ streams
     # Ordering edges between the three streams go through the library's event pool (ops.sync_record / sync_wait: slots of a
@@ -367,7 +370,7 @@ class WesupEngine:
     def _switches(self):
         return layer_plan.Switches(self.fuse_pool_bwd, self.fuse_pool_fwd, self.two_streams, self.wgrad_winograd, self.conv_winograd,
                                    self.plain, self.matrix_pool, self.fuse_side_fwd, self.WINOGRAD_MIN_CI, self.WINOGRAD_MIN_CO,
-                                   self.WINOGRAD_TILE)
+                                   self.WINOGRAD_TILE, int(self.unpool_on_load))
 
     def _route_of(self, B, H, W):
         """route(B, H, W) as a tuple, remembered per (routing rule, shape): thirteen calls of the rule per walk otherwise."""
@@ -938,6 +941,17 @@ class WesupEngine:
         # kernels instead of sitting on the critical path.
         main = torch.cuda.current_stream()
         wg = self._wg() if self.two_streams else None
+
+        def dP(l):
+            """Layer l's input gradient at pooled resolution where plan.dp_on_load keeps it (None: the epilogue unpools it)."""
+            at = plan.dp_on_load[l]
+            if at is None:
+                return None
+            hp, wp = b.dims[l]
+            n = B * hp * wp * CONV_CH[l][0]
+            store = b.G[l - 1].view(-1) if at[0] == 'G' else b.dV
+            return store[at[1]:at[1] + n].view(B, hp, wp, CONV_CH[l][0])
+
         for l in range(12, lowest - 1, -1):
             L = Ls[l]
             ci, co, h, w = L.ci, L.co, L.h, L.w
@@ -954,10 +968,20 @@ class WesupEngine:
             if L.dual:      # one pass over G_l for both consumers (F(4x4) input gradient and weight gradient)
                 Tl = ops.winograd_tiles(B, h, w, 4)
                 v_dy = b.dV[:36 * Tl * co].view(36, Tl, co)
+                dp = dP(l + 1) if l < 12 else None
                 tok = T.begin('winograd_transform')
-                if 'dual' not in self._diag_skip:
+                if 'dual' in self._diag_skip:
+                    pass
+                elif dp is None:
                     ops.winograd_dual_transform(b.G[l], v_dy, b.dM[l], b.bpart[l])
-                T.end(tok, 4.0 * (B * h * w + 2 * 36 * Tl) * co)
+                elif Ls[l + 1].dgrad == 'gather':     # G_l = gathered side gradient + unpooled dP, formed while loading
+                    ops.winograd_dual_transform_unpool(b.dybar[l], dp, b.pcode[l], v_dy, b.dM[l], b.bpart[l], new_row=meta.new_row)
+                else:                                 # G_l (the side gradient) + unpooled dP
+                    ops.winograd_dual_transform_unpool(b.G[l], dp, b.pcode[l], v_dy, b.dM[l], b.bpart[l])
+                # bytes in: G_l; with dP also dP and its codes (2 bytes per 4 values: 1.125 x dP's own 4 bytes per value), and a
+                # label map in place of G_l where the side gradient is gathered
+                n_in = B * h * w * (1 if dp is not None and Ls[l + 1].dgrad == 'gather' else co) + (0 if dp is None else 1.125 * dp.numel())
+                T.end(tok, 4.0 * (n_in + 2 * 36 * Tl * co))
 
             def wgrad(ws_tag):
                 tok = T.begin('conv3x3_wgrad')
@@ -995,7 +1019,10 @@ class WesupEngine:
                 pooled = Ls[l - 1].pool
                 mbits = b.mbits[l - 1] if L.write_bits else None
                 pcode = b.pcode[l - 1] if Ls[l - 1].write_codes else None
-                if L.dgrad == 'gather':
+                dp_out = dP(l)
+                if dp_out is not None:      # plain, at pooled resolution: the dual transform of layer l - 1 unpools it while loading
+                    ops.conv3x3_dgrad_winograd(b.G[l], pk.ud[l], out=dp_out, ws_tag='wino_main', timer=T, m=4, v_pre=v_dy)
+                elif L.dgrad == 'gather':
                     ops.conv3x3_dgrad_winograd_gather(b.G[l], pk.ud[l], b.dybar[l - 1], meta.new_row, None, out=b.G[l - 1],
                                                       mask_src=None if pooled else b.y[l - 1],
                                                       unpool_src=b.y[l - 1] if pooled else None, ws_tag='wino_main', timer=T,

@@ -23,10 +23,11 @@ FM_CHANNELS = 2112
 DEEP_SIDE_WGRAD_AT = 2
 WGRAD_EARLY_LAYERS = 1
 
-# The engine's six boolean switches, its two class-level ones, and the three class attributes of the weight-gradient routing.
+# The engine's six boolean switches, its two class-level ones, the three class attributes of the weight-gradient routing, and
+# its class-level int unpool_on_load.
 Switches = namedtuple('Switches', 'fuse_pool_bwd fuse_pool_fwd two_streams wgrad_winograd conv_winograd plain matrix_pool '
-                                  'fuse_side_fwd wgrad_min_ci wgrad_min_co wgrad_tile',
-                      defaults=(True, True, True, True, True, False, True, True, 128, 256, 4))
+                                  'fuse_side_fwd wgrad_min_ci wgrad_min_co wgrad_tile unpool_on_load',
+                      defaults=(True, True, True, True, True, False, True, True, 128, 256, 4, 1))
 
 Group = namedtuple('Group', 'layers h w off C')      # the layers of one coarse resolution: side outputs side by side, one matrix
 
@@ -61,6 +62,12 @@ StepPlan = namedtuple('StepPlan', [
     'late_at', 'late_side',   # the grouped layers' side-conv weight gradients are queued when the chain reaches late_at
     'shallow_first',  # the shallow layers' side gradients go to the head of the weight-gradient stream
     'fm', 'dfm',      # the (B,H,W,2112) feature map / its gradient are materialised (the unfused switches)
+    # Per layer l, None or where its input gradient stays at pooled resolution (dP) for the dual transform of the pooled layer
+    # l - 1 to unpool while loading (ops.winograd_dual_transform_unpool) instead of the 'gather' / 'unpool' epilogue scattering
+    # it into G[l - 1]: ('G', 0) the head quarter of G[l - 1]'s own storage ('gather': nothing else writes that tensor), or
+    # ('dV', first element) the tail of the shared dV buffer ('unpool': G[l - 1] holds the side gradient).  Storage the set
+    # holds anyway: no row of the layer table and no buffer changes with it.
+    'dp_on_load',
 ])
 
 # One buffer of a set: b.<name> (layer None), b.<name>[layer], or b.groups[layer].<name[2:]> for the 'g.' names (layer = the group's
@@ -72,6 +79,11 @@ ITEMSIZE = {'float32': 4, 'int16': 2, 'uint8': 1}
 def tiles(B, H, W, m):
     """Tiles of the F(m x m, 3x3) domain of a (B,H,W) map (ops.winograd_tiles)."""
     return B * ((H + m - 1) // m) * ((W + m - 1) // m)
+
+
+def dv_elems(B, dims):
+    """Elements of the shared dV buffer: V' = B^T dY B of one layer at a time, the largest of them."""
+    return max(36 * tiles(B, *dims[l], 4) * CONV_CH[l][1] for l in range(1, 13))
 
 
 def layer_dims(H, W):
@@ -217,11 +229,31 @@ def build(shape, group_of, route, switches, diag_skip, frozen, train, fused_supp
                 else:
                     r['dgrad'] = 'direct'
                 r['pool_bwd'] = bool(POOL_AFTER[l - 1] and not unpooled)
+    dp_on_load = [None] * 13
+    if train and fancy and sw.unpool_on_load and 'dual' not in diag_skip:      # (--diag-skip dual takes the transform out, nothing else)
+        dv = dv_elems(B, dims)
+        for l in range(lowest + 1, 13):
+            hu, wu = dims[l - 1]
+            # the transform of G[l - 1] is the dual one, the forward left the pooling's codes, every pre-pool pixel sits in a window
+            if not (POOL_AFTER[l - 1] and bwd[l - 1]['dual'] and fwd[l - 1]['write_codes'] and hu % 2 == 0 and wu % 2 == 0):
+                continue
+            if 4 * B * hu * wu * CONV_CH[l - 1][1] >= 1 << 32:       # (the kernel's 32-bit byte offsets)
+                continue
+            if bwd[l]['dgrad'] == 'gather':
+                dp_on_load[l] = ('G', 0)
+            elif bwd[l]['dgrad'] == 'unpool':
+                # dP in the tail of dV: behind v_dy(l), which the input gradient reads while it writes dP, and behind
+                # v_dy(l - 1), which the transform writes while it reads dP
+                n = B * (hu // 2) * (wu // 2) * CONV_CH[l - 1][1]
+                v_l = 36 * tiles(B, *dims[l], 4) * CONV_CH[l][1]
+                v_below = 36 * tiles(B, hu, wu, 4) * CONV_CH[l - 1][1]
+                if max(v_l, v_below) + n <= dv:
+                    dp_on_load[l] = ('dV', dv - n)
     return StepPlan(shape=tuple(shape), route=tuple(route), train=bool(train),
                     layers=tuple(LayerPlan(**f, **r) for f, r in zip(fwd, bwd)),
                     lowest=lowest, relu_stored=relu_stored, runs=tuple(tuple(r) for r in runs), late_at=late_at,
                     late_side=late_side, shallow_first=bool(train and sw.two_streams and sw.fuse_pool_bwd),
-                    fm=not sw.fuse_pool_fwd, dfm=bool(train and not sw.fuse_pool_bwd))
+                    fm=not sw.fuse_pool_fwd, dfm=bool(train and not sw.fuse_pool_bwd), dp_on_load=tuple(dp_on_load))
 
 
 def buffers(plan, groups, Kmax, D, cls_part_bytes):
@@ -291,7 +323,7 @@ def buffers(plan, groups, Kmax, D, cls_part_bytes):
     for l in (l for run in plan.runs for l in run):
         add('dybar', l, (B, Kmax, Ls[l].co))
     if any(L.dual for L in Ls):       # one V' = B^T dY B for all layers, the largest of them
-        add('dV', None, (max(36 * tiles(B, L.h, L.w, 4) * L.co for L in Ls[1:]),))
+        add('dV', None, (dv_elems(B, [(L.h, L.w) for L in Ls]),))
     if plan.dfm:
         add('dfm', None, (B, H, W, FM_CHANNELS))
     add('dfeat', None, (R, D))

@@ -722,6 +722,32 @@ def winograd_dual_transform(dy, V, dM, bias_part=None):
     return V, dM
 
 
+def winograd_dual_transform_unpool(side, dp, code, V, dM, bias_part=None, new_row=None):
+    """winograd_dual_transform of dy = side + maxpool2_bwd(dp), with dy never written: dp (B,H/2,W/2,C) the gradient at pooled
+    resolution, code (B,H/2,W/2,C/4) int16 the forward's pooling decisions (conv3x3_fwd_winograd(pool_code_out=...)), H and W
+    even.  side: the side-branch gradient, dense (B,H,W,C), or with new_row (B,H*W) int32 the rows (B,Kmax,C) it gathers per
+    pixel (divided by their areas already: scale_rows_by_area).  Bit for bit what the dual transform makes of the tensor
+    conv3x3_dgrad_winograd_unpool / conv3x3_dgrad_winograd_gather(unpool_code=...) leave."""
+    _chk(side, name='side'); _chk(dp, name='dp'); _chk(V, name='V'); _chk(dM, name='dM')
+    B, Hp, Wp, C = dp.shape
+    H, W = 2 * Hp, 2 * Wp
+    T = winograd_tiles(B, H, W, 4)
+    assert V.shape == (36, T, C) == dM.shape
+    assert code.dtype == torch.int16 and code.shape == (B, Hp, Wp, C // 4) and code.is_contiguous()
+    Kmax = 0
+    if new_row is not None:
+        _chk(new_row, torch.int32, 'new_row')
+        Kmax = side.shape[1]
+        assert side.shape == (B, Kmax, C) and new_row.shape == (B, H * W)
+    else:
+        assert side.shape == (B, H, W, C)
+    if bias_part is not None:
+        _chk(bias_part, name='bias_part'); assert bias_part.shape == (winograd_bias_rows(B, H, W, C), C) and bias_part.shape[0] > 0
+    _lib.call('wesup_winograd_dual_transform_unpool', _p(side), _p(new_row), Kmax, _p(dp), _p(code), _p(V), _p(dM), _p(bias_part),
+              B, H, W, C, _stream())
+    return V, dM
+
+
 def conv3x3_wgrad_winograd_pre(v_pre, dm_pre, bias_part, B, H, W, dw, db=None, ws_tag='default'):
     """The F(4x4) weight gradient from operands that exist: v_pre (36,tiles,Ci) kept by the forward, dm_pre (36,tiles,Cout) and
     bias_part from winograd_dual_transform.  dw (Cout,Ci,3,3); db (Cout) needs bias_part."""
