@@ -29,6 +29,9 @@ extern "C" {
 #define WESUP_ERR_LAUNCH (-2)    /* hipLaunch failed */
 #define WESUP_ERR_WORKSPACE (-3) /* workspace too small */
 
+/* classes of the C-way head (the *_c entries, wesup_paint_argmax, wesup_seg_confusion): 2 <= C <= WESUP_MAX_CLASSES */
+#define WESUP_MAX_CLASSES 16
+
 /* flags for wesup_gemm_nt */
 #define WESUP_RELU_IN 1    /* A := max(A, 0) while loading */
 #define WESUP_RELU_OUT 2   /* C := max(C, 0) */
@@ -419,6 +422,40 @@ int wesup_head_bwd(const float* feat, const float* Wc, const float* pred, const 
                    const int32_t* n_l, const float* dloss, float eps, float prop_weight, float* terms, float* dpred,
                    float* dfeat, int B, int Kmax, int D, int C, void* ws, size_t ws_bytes, void* stream);
 int wesup_classifier_bwd_finish(const void* ws, size_t ws_bytes, float* dWc, float* dbc, int R, int D, void* stream);
+/* ------------------------------------------------------------------ the C-way head, 2 <= C <= WESUP_MAX_CLASSES
+ * New entries beside the two-class ones above, which keep their kernels: the two-class step's launch list and bits do not move.
+ * Outside the range of C every entry returns WESUP_ERR_INVALID.  Called with C = 2 each reproduces its two-class entry bit for bit.
+ * wesup_classifier_fwd_c: pred (R, C) = softmax(feat (R, D) . Wc (C, D)^T + bc): logits by fmaf in ascending k, the maximum
+ *   subtracted, exponentials summed in ascending class order, one reciprocal.  A streaming kernel (pixel inference runs it with
+ *   R = B*H*W): Wc / bc in LDS once per block, rows as float4 where D % 4 == 0, logits in registers; D <= 512.
+ * wesup_classifier_bwd_c: dz_c = p_c (dp_c - sum_j dp_j p_j); dfeat = (sum_c dz_c Wc[c][k] + dfeat_extra) where feat > 0, else 0;
+ *   dWc (C, D), dbc (C) from per-64-row partial sums added in fixed order (no float atomics).  Class sums: the first product,
+ *   then fmaf in ascending class order.
+ * wesup_head_fwd_c = wesup_classifier_fwd_c + wesup_propagate in one launch; wesup_head_bwd_c = wesup_loss_fwd (terms only) +
+ *   wesup_loss_bwd + the first kernel of wesup_classifier_bwd_c in one launch (Kmax % 64 == 0), wesup_classifier_bwd_c_finish
+ *   adds the partial sums it left in ws up.  Bit-identical to the separate entries at the same C. */
+int wesup_classifier_fwd_c(const float* feat, const float* Wc, const float* bc, float* pred, int R, int D, int C, void* stream);
+size_t wesup_classifier_bwd_c_workspace_bytes(int R, int D, int C);
+int wesup_classifier_bwd_c(const float* feat, const float* Wc, const float* pred, const float* dpred,
+                           const float* dfeat_extra, float* dfeat, float* dWc, float* dbc, int R, int D, int C,
+                           void* ws, size_t ws_bytes, void* stream);
+int wesup_head_fwd_c(const float* feat, const float* Wc, const float* bc, float* pred, const float* sp_labels,
+                     const int32_t* n_sp, const int32_t* n_l, float threshold, int enable, float* y_all, int32_t* src_idx,
+                     float* max_sim, int B, int Kmax, int D, int C, void* stream);
+int wesup_head_bwd_c(const float* feat, const float* Wc, const float* pred, const float* y_all, const int32_t* n_sp,
+                     const int32_t* n_l, const float* dloss, float eps, float prop_weight, float* terms, float* dpred,
+                     float* dfeat, int B, int Kmax, int D, int C, void* ws, size_t ws_bytes, void* stream);
+int wesup_classifier_bwd_c_finish(const void* ws, size_t ws_bytes, float* dWc, float* dbc, int R, int D, int C, void* stream);
+/* class-map paint-back: pred[b][p] = (float) argmax_c sp_pred[b][new_row[p]][c], the first maximum (ties go to the lowest class).
+ * The argmax is taken once per superpixel row into ws (B * Kmax floats), then gathered per pixel. */
+size_t wesup_paint_argmax_workspace_bytes(int B, int Kmax);
+int wesup_paint_argmax(const float* sp_pred, const int32_t* new_row, float* pred, int B, int HW, int Kmax, int C,
+                       void* ws, size_t ws_bytes, void* stream);
+/* conf (B, C, C) int32: pixels per (ground-truth class = first maximum over the mask's C planes, predicted class = pred as a
+ * class index).  conf and status[0] are zeroed by the entry; a predicted value outside [0, C) (or NaN) sets status[0] and is
+ * not counted.  Integer adds in LDS per block, then integer adds to the table: the result does not depend on the order. */
+int wesup_seg_confusion(const float* pred, const uint8_t* mask, int32_t* conf, int32_t* status, int B, int HW, int C,
+                        void* stream);
 /* generic _cross_entropy (models/wesup.py:66-96) on (n, C): out2[4] = {sum(-y log clamp(yhat) [* class_weights[c]]),
  * #rows with sum(y) > 0, loss = sum/#rows (0 if no row is labelled), 0}; class_weights (C,) or NULL (models/wesup.py:93-94) */
 int wesup_cross_entropy_fwd(const float* y_hat, const float* y_true, const float* class_weights, float eps, float* out2,

@@ -106,6 +106,16 @@ _SIGS = {
     'wesup_head_fwd': (c_int, 'pppppppfipppiiiip'),
     'wesup_head_bwd': (c_int, 'pppppppffpppiiiipzp'),
     'wesup_classifier_bwd_finish': (c_int, 'pzppiip'),
+    # the C-way head, 2 <= C <= WESUP_MAX_CLASSES (csrc/loss.hip)
+    'wesup_classifier_fwd_c': (c_int, 'ppppiiip'),
+    'wesup_classifier_bwd_c_workspace_bytes': (c_size_t, 'iii'),
+    'wesup_classifier_bwd_c': (c_int, 'ppppppppiiipzp'),
+    'wesup_head_fwd_c': (c_int, 'pppppppfipppiiiip'),
+    'wesup_head_bwd_c': (c_int, 'pppppppffpppiiiipzp'),
+    'wesup_classifier_bwd_c_finish': (c_int, 'pzppiiip'),
+    'wesup_paint_argmax_workspace_bytes': (c_size_t, 'ii'),
+    'wesup_paint_argmax': (c_int, 'pppiiiipzp'),
+    'wesup_seg_confusion': (c_int, 'ppppiiip'),
     'wesup_cross_entropy_fwd': (c_int, 'pppfpiip'),
     'wesup_cross_entropy_bwd': (c_int, 'pppppfpiip'),
     'wesup_sgd_step': (c_int, 'pppzffffip'),
@@ -181,6 +191,7 @@ _SIGS = {
 _T = {'p': c_void_p, 'i': c_int, 'f': c_float, 'z': c_size_t, 'l': ctypes.c_long}
 
 EXPORTS = sorted(_SIGS)
+MAX_CLASSES = 16         # WESUP_MAX_CLASSES
 ABI_VERSION = 6          # include/wesup_hip.h; a stale libwesup_hip.so with other signatures must not be called
 
 _lib = None

@@ -130,6 +130,188 @@ extern "C" int wesup_classifier_bwd(const float* feat, const float* Wc, const fl
     return WESUP_OK;
 }
 
+// ------------------------------------------------------------------ classifier Linear(D,C) + Softmax(dim=1), 2 <= C <= WESUP_MAX_CLASSES
+// The two-class kernels above stay as they are (the step's launch list and bits at C = 2 do not move); these are reached for a
+// classifier of more than two classes, and reproduce the two-class entries bit for bit when called with C = 2.
+// One row: logits by fmaf in ascending k, the maximum subtracted, the exponentials summed in ascending class order, one
+// reciprocal.  The logits live in registers: z[] is indexed by unrolled constants only, CMAX >= C bounds it at compile time.
+// W: [C][D] and bias [C], in LDS (classifier_fwd_c_kernel) or global memory (prop_body's tail) -- the arithmetic is the same.
+template <int CMAX, bool VEC4>
+__device__ __forceinline__ void cls_row(const float* __restrict__ f, const float* W, const float* bias, float* __restrict__ out,
+                                        int D, int C, bool st4_ok = false) {
+    float z[CMAX];
+#pragma unroll
+    for (int c = 0; c < CMAX; ++c) z[c] = (c < C) ? bias[c] : 0.f;
+    if constexpr (VEC4) {
+        for (int k = 0; k < D; k += 4) {
+            const float4 v = ld4(f + k);
+#pragma unroll
+            for (int c = 0; c < CMAX; ++c)
+                if (c < C) {
+                    const float4 w = ld4(W + c * D + k);
+                    z[c] = fmaf(v.x, w.x, z[c]);
+                    z[c] = fmaf(v.y, w.y, z[c]);
+                    z[c] = fmaf(v.z, w.z, z[c]);
+                    z[c] = fmaf(v.w, w.w, z[c]);
+                }
+        }
+    } else {
+        for (int k = 0; k < D; ++k) {
+            const float v = f[k];
+#pragma unroll
+            for (int c = 0; c < CMAX; ++c)
+                if (c < C) z[c] = fmaf(v, W[c * D + k], z[c]);
+        }
+    }
+    float m = z[0];
+#pragma unroll
+    for (int c = 1; c < CMAX; ++c)
+        if (c < C) m = fmaxf(m, z[c]);
+    z[0] = expf(z[0] - m);
+    float s = z[0];
+#pragma unroll
+    for (int c = 1; c < CMAX; ++c)
+        if (c < C) {
+            z[c] = expf(z[c] - m);
+            s += z[c];
+        }
+    const float inv = 1.f / s;
+    if (CMAX >= 4 && st4_ok) {                      // (C % 4 == 0, out 16-byte aligned)
+#pragma unroll
+        for (int c = 0; c + 3 < CMAX; c += 4)
+            if (c < C) st4(out + c, make_float4(z[c] * inv, z[c + 1] * inv, z[c + 2] * inv, z[c + 3] * inv));
+    } else {
+#pragma unroll
+        for (int c = 0; c < CMAX; ++c)
+            if (c < C) out[c] = z[c] * inv;
+    }
+}
+// Streaming form (pixel inference runs it with R = B*H*W): Wc and bc staged in LDS once per block (every lane reads the same
+// address: a broadcast), a thread per row, rows read as float4 where D % 4 == 0, at most 2048 blocks that stride over the rows.
+template <int CMAX, bool VEC4>
+__global__ __launch_bounds__(256) void classifier_fwd_c_kernel(const float* __restrict__ feat, const float* __restrict__ Wc,
+                                                               const float* __restrict__ bc, float* __restrict__ pred, int R,
+                                                               int D, int C, int st4_ok) {
+    extern __shared__ __align__(16) float shw[];                  // [C][D] | [C]
+    for (int e = threadIdx.x; e < C * D; e += 256) shw[e] = Wc[e];
+    if (threadIdx.x < C) shw[C * D + threadIdx.x] = bc[threadIdx.x];
+    __syncthreads();
+    for (long r = (long)blockIdx.x * 256 + threadIdx.x; r < R; r += (long)gridDim.x * 256)
+        cls_row<CMAX, VEC4>(feat + r * D, shw, shw + C * D, pred + r * C, D, C, st4_ok != 0);
+}
+#define CLS_C_MAX_D 512                             // (C * D + C floats of LDS: 32 KB at C = 16)
+static inline bool cls_c_range(int C) { return C >= 2 && C <= WESUP_MAX_CLASSES; }
+template <int CMAX>
+static int classifier_fwd_c_launch(const float* feat, const float* Wc, const float* bc, float* pred, int R, int D, int C,
+                                   hipStream_t st) {
+    const bool vec = (D % 4 == 0) && (((uintptr_t)feat & 15) == 0);
+    const int st4_ok = (C % 4 == 0) && (((uintptr_t)pred & 15) == 0);
+    const int blocks = min(ceil_div(R, 256), 2048);
+    const size_t lds = (size_t)(C * D + C) * sizeof(float);
+    if (vec)
+        WESUP_LAUNCH((classifier_fwd_c_kernel<CMAX, true>), dim3(blocks), dim3(256), lds, st, feat, Wc, bc, pred, R, D, C, st4_ok);
+    else
+        WESUP_LAUNCH((classifier_fwd_c_kernel<CMAX, false>), dim3(blocks), dim3(256), lds, st, feat, Wc, bc, pred, R, D, C, st4_ok);
+    WESUP_CHECK_LAUNCH();
+    return WESUP_OK;
+}
+extern "C" int wesup_classifier_fwd_c(const float* feat, const float* Wc, const float* bc, float* pred, int R, int D, int C,
+                                      void* stream) {
+    if (!feat || !Wc || !bc || !pred || R <= 0 || D <= 0 || D > CLS_C_MAX_D || !cls_c_range(C)) return WESUP_ERR_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    if (C <= 2) return classifier_fwd_c_launch<2>(feat, Wc, bc, pred, R, D, C, st);
+    if (C <= 4) return classifier_fwd_c_launch<4>(feat, Wc, bc, pred, R, D, C, st);
+    if (C <= 8) return classifier_fwd_c_launch<8>(feat, Wc, bc, pred, R, D, C, st);
+    return classifier_fwd_c_launch<WESUP_MAX_CLASSES>(feat, Wc, bc, pred, R, D, C, st);
+}
+
+// backward, C classes: dz_c = p_c (dp_c - sum_j dp_j p_j); dfeat = (sum_c dz_c Wc[c][k] + extra) masked by feat > 0; partial
+// dWc / dbc per 64 rows, reduced in fixed order.  The class sums are written as cls_dz / cls_dfeat write theirs: the first
+// product, then fmaf in ascending class order -- the unfused kernel, the fused one (head_bwd_c_kernel) and, at C = 2, the
+// two-class kernels agree bit for bit.  No per-thread array: a row's dpred waits in its LDS row of dz.
+__device__ __forceinline__ void cls_dz_row(const float* __restrict__ p, float* dzrow, int C) {
+    float s = dzrow[0] * p[0];
+    for (int c = 1; c < C; ++c) s = fmaf(dzrow[c], p[c], s);
+    for (int c = 0; c < C; ++c) dzrow[c] = p[c] * (dzrow[c] - s);
+}
+// dfeat of the block's rows and the block's partial sums, from dz[CLS_ROWS][WESUP_MAX_CLASSES] in LDS (behind a __syncthreads)
+__device__ __forceinline__ void cls_bwd_c_tail(const float* __restrict__ feat, const float* __restrict__ Wc,
+                                               const float* __restrict__ extra, float* __restrict__ dfeat,
+                                               float* __restrict__ pout, const float (*dz)[WESUP_MAX_CLASSES], long r0, long R,
+                                               int D, int C) {
+    const int tid = threadIdx.x;
+    for (int e = tid; e < CLS_ROWS * D; e += 256) {
+        const int rr = e / D, k = e - rr * D;
+        const long r = r0 + rr;
+        if (r < R) {
+            float g = dz[rr][0] * Wc[k];
+            for (int c = 1; c < C; ++c) g = fmaf(dz[rr][c], Wc[c * D + k], g);
+            if (extra) g += extra[r * D + k];
+            dfeat[r * D + k] = feat[r * D + k] > 0.f ? g : 0.f;
+        }
+    }
+    for (int e = tid; e < C * D + C; e += 256) {
+        float s = 0.f;
+        if (e < C * D) {
+            const int c = e / D, k = e - c * D;
+            for (int rr = 0; rr < CLS_ROWS; ++rr) {
+                const long r = r0 + rr;
+                if (r < R) s = fmaf(dz[rr][c], feat[r * D + k], s);
+            }
+        } else {
+            const int c = e - C * D;
+            for (int rr = 0; rr < CLS_ROWS; ++rr) s += dz[rr][c];
+        }
+        pout[e] = s;
+    }
+}
+__global__ __launch_bounds__(256) void classifier_bwd_c_kernel(const float* __restrict__ feat, const float* __restrict__ Wc,
+                                                               const float* __restrict__ pred, const float* __restrict__ dpred,
+                                                               const float* __restrict__ extra, float* __restrict__ dfeat,
+                                                               float* __restrict__ part, int R, int D, int C) {
+    __shared__ float dz[CLS_ROWS][WESUP_MAX_CLASSES];
+    const long r0 = (long)blockIdx.x * CLS_ROWS;
+    const int tid = threadIdx.x;
+    if (tid < CLS_ROWS) {
+        const long r = r0 + tid;
+        if (r < R) {
+            for (int c = 0; c < C; ++c) dz[tid][c] = dpred[r * C + c];
+            cls_dz_row(pred + r * C, dz[tid], C);
+        } else {
+            for (int c = 0; c < C; ++c) dz[tid][c] = 0.f;
+        }
+    }
+    __syncthreads();
+    cls_bwd_c_tail(feat, Wc, extra, dfeat, part + (long)blockIdx.x * (C * D + C), dz, r0, R, D, C);
+}
+__global__ void classifier_bwd_c_reduce(const float* __restrict__ part, float* __restrict__ dWc, float* __restrict__ dbc,
+                                        int nblk, int D, int C) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= C * D + C) return;
+    float s = 0.f;
+    for (int b = 0; b < nblk; ++b) s += part[(long)b * (C * D + C) + e];
+    if (e < C * D) dWc[e] = s;
+    else dbc[e - C * D] = s;
+}
+extern "C" size_t wesup_classifier_bwd_c_workspace_bytes(int R, int D, int C) {
+    if (R <= 0 || D <= 0 || !cls_c_range(C)) return 0;
+    return (size_t)ceil_div(R, CLS_ROWS) * (C * D + C) * sizeof(float);
+}
+extern "C" int wesup_classifier_bwd_c(const float* feat, const float* Wc, const float* pred, const float* dpred,
+                                      const float* dfeat_extra, float* dfeat, float* dWc, float* dbc, int R, int D, int C,
+                                      void* ws, size_t ws_bytes, void* stream) {
+    if (!feat || !Wc || !pred || !dpred || !dfeat || !dWc || !dbc || !ws || R <= 0 || D <= 0 || !cls_c_range(C))
+        return WESUP_ERR_INVALID;
+    if (ws_bytes < wesup_classifier_bwd_c_workspace_bytes(R, D, C)) return WESUP_ERR_WORKSPACE;
+    const int nblk = ceil_div(R, CLS_ROWS);
+    hipStream_t st = (hipStream_t)stream;
+    WESUP_LAUNCH(classifier_bwd_c_kernel, dim3(nblk), dim3(256), 0, st, feat, Wc, pred, dpred, dfeat_extra, dfeat, (float*)ws, R,
+                 D, C);
+    WESUP_LAUNCH(classifier_bwd_c_reduce, dim3(ceil_div(C * D + C, 64)), dim3(64), 0, st, (const float*)ws, dWc, dbc, nblk, D, C);
+    WESUP_CHECK_LAUNCH();
+    return WESUP_OK;
+}
+
 // ------------------------------------------------------------------ label propagation (models/wesup.py:99-139)
 // One launch: a block owns PROP_ROWS consecutive rows of an image.  It first writes what every row has whatever happens next --
 // y_all = the row's own labels (labelled rows) or zeros, src_idx = -1, max_sim = 0 (a launch of its own until round 5) -- and
@@ -139,13 +321,15 @@ extern "C" int wesup_classifier_bwd(const float* feat, const float* Wc, const fl
 // torch.max(dim=1) does; propagate iff W > threshold (strict).
 #define PROP_TILE 256
 #define PROP_ROWS 16
-__global__ __launch_bounds__(256) void prop_kernel(const float* __restrict__ feat, const float* __restrict__ sp_labels,
-                                                   const int32_t* __restrict__ n_sp, const int32_t* __restrict__ n_l,
-                                                   float thr, int enable, float* __restrict__ y_all, int32_t* __restrict__ src_idx,
-                                                   float* __restrict__ max_sim, int Kmax, int D, int C,
-                                                   const float* __restrict__ Wc, const float* __restrict__ bc,
-                                                   float* __restrict__ pred) {
-    extern __shared__ float sh[];
+// (the body of prop_kernel and of prop_c_kernel, its form for a classifier of more than two classes: GENERIC only chooses the
+// classifier tail, everything else is the same code)
+template <bool GENERIC>
+__device__ __forceinline__ void prop_body(float* sh, const float* __restrict__ feat, const float* __restrict__ sp_labels,
+                                          const int32_t* __restrict__ n_sp, const int32_t* __restrict__ n_l,
+                                          float thr, int enable, float* __restrict__ y_all, int32_t* __restrict__ src_idx,
+                                          float* __restrict__ max_sim, int Kmax, int D, int C,
+                                          const float* __restrict__ Wc, const float* __restrict__ bc,
+                                          float* __restrict__ pred) {
     float* fl = sh;                               // [PROP_TILE][D+1]
     float* fi = sh + PROP_TILE * (D + 1);         // [PROP_ROWS][D]
     const int b = blockIdx.y;
@@ -162,7 +346,13 @@ __global__ __launch_bounds__(256) void prop_kernel(const float* __restrict__ fea
     }
     // wesup_head_fwd: the classifier + softmax of this block's rows rides along (classifier_fwd_kernel's arithmetic, row by row:
     // a launch of its own on the chain between the fc layers and the loss otherwise)
-    if (pred && tid < PROP_ROWS && i_blk + tid < Kmax) {
+    if constexpr (GENERIC) {
+        // wesup_head_fwd_c: classifier_fwd_c_kernel's arithmetic (cls_row), C columns per row
+        if (pred && tid < PROP_ROWS && i_blk + tid < Kmax) {
+            const long r = (long)b * Kmax + i_blk + tid;
+            cls_row<WESUP_MAX_CLASSES, false>(feat + r * D, Wc, bc, pred + r * C, D, C);
+        }
+    } else if (pred && tid < PROP_ROWS && i_blk + tid < Kmax) {
         const long r = (long)b * Kmax + i_blk + tid;
         float z0 = bc[0], z1 = bc[1];
         const float* f = feat + r * D;
@@ -242,6 +432,24 @@ __global__ __launch_bounds__(256) void prop_kernel(const float* __restrict__ fea
                     y_all[((long)b * Kmax + i) * C + c] = sp_labels[((long)b * Kmax + j) * C + c];
         }
     }
+}
+__global__ __launch_bounds__(256) void prop_kernel(const float* __restrict__ feat, const float* __restrict__ sp_labels,
+                                                   const int32_t* __restrict__ n_sp, const int32_t* __restrict__ n_l,
+                                                   float thr, int enable, float* __restrict__ y_all, int32_t* __restrict__ src_idx,
+                                                   float* __restrict__ max_sim, int Kmax, int D, int C,
+                                                   const float* __restrict__ Wc, const float* __restrict__ bc,
+                                                   float* __restrict__ pred) {
+    extern __shared__ float sh[];
+    prop_body<false>(sh, feat, sp_labels, n_sp, n_l, thr, enable, y_all, src_idx, max_sim, Kmax, D, C, Wc, bc, pred);
+}
+__global__ __launch_bounds__(256) void prop_c_kernel(const float* __restrict__ feat, const float* __restrict__ sp_labels,
+                                                     const int32_t* __restrict__ n_sp, const int32_t* __restrict__ n_l,
+                                                     float thr, int enable, float* __restrict__ y_all, int32_t* __restrict__ src_idx,
+                                                     float* __restrict__ max_sim, int Kmax, int D, int C,
+                                                     const float* __restrict__ Wc, const float* __restrict__ bc,
+                                                     float* __restrict__ pred) {
+    extern __shared__ float sh[];
+    prop_body<true>(sh, feat, sp_labels, n_sp, n_l, thr, enable, y_all, src_idx, max_sim, Kmax, D, C, Wc, bc, pred);
 }
 extern "C" int wesup_propagate(const float* feat, const float* sp_labels, const int32_t* n_sp, const int32_t* n_l,
                                float threshold, int enable, float* y_all, int32_t* src_idx, float* max_sim, int B,
@@ -480,6 +688,104 @@ extern "C" int wesup_classifier_bwd_finish(const void* ws, size_t ws_bytes, floa
     return WESUP_OK;
 }
 
+// The C-class forms of the two fused head launches (2 <= C <= WESUP_MAX_CLASSES), bit-identical to the separate entries at the
+// same C.  wesup_head_fwd_c = wesup_classifier_fwd_c + wesup_propagate (prop_c_kernel: prop_kernel with cls_row as its tail).
+extern "C" int wesup_head_fwd_c(const float* feat, const float* Wc, const float* bc, float* pred, const float* sp_labels,
+                                const int32_t* n_sp, const int32_t* n_l, float threshold, int enable, float* y_all,
+                                int32_t* src_idx, float* max_sim, int B, int Kmax, int D, int C, void* stream) {
+    if (!feat || !Wc || !bc || !pred || !sp_labels || !n_sp || !n_l || !y_all || !src_idx || !max_sim || B <= 0 || Kmax <= 0 ||
+        D <= 0 || D > 256 || !cls_c_range(C))
+        return WESUP_ERR_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t lds = ((size_t)PROP_TILE * (D + 1) + (size_t)PROP_ROWS * D) * sizeof(float);
+    WESUP_LAUNCH(prop_c_kernel, dim3(ceil_div(Kmax, PROP_ROWS), B), dim3(256), lds, st, feat, sp_labels, n_sp, n_l, threshold,
+                 enable, y_all, src_idx, max_sim, Kmax, D, C, Wc, bc, pred);
+    WESUP_CHECK_LAUNCH();
+    return WESUP_OK;
+}
+// wesup_head_bwd_c = wesup_loss_fwd (terms only) + wesup_loss_bwd + the first kernel of wesup_classifier_bwd_c: head_bwd_kernel
+// with C columns per row (its comment above holds word for word).
+__global__ __launch_bounds__(256) void head_bwd_c_kernel(const float* __restrict__ feat, const float* __restrict__ Wc,
+                                                         const float* __restrict__ pred, const float* __restrict__ y_all,
+                                                         const int32_t* __restrict__ n_sp, const int32_t* __restrict__ n_l,
+                                                         const float* __restrict__ dloss, float eps, float prop_weight,
+                                                         float* __restrict__ terms, float* __restrict__ dpred,
+                                                         float* __restrict__ dfeat, float* __restrict__ part, int B, int Kmax,
+                                                         int D, int C) {
+    __shared__ float sh[256];
+    __shared__ float dz[CLS_ROWS][WESUP_MAX_CLASSES];
+    const int tid = threadIdx.x;
+    const long r0 = (long)blockIdx.x * CLS_ROWS;          // first row (of B * Kmax) of this block
+    const int b = (int)(r0 / Kmax), i0 = (int)(r0 - (long)b * Kmax);
+    const int ns = n_sp[b], nl = n_l[b];
+    float sup = 0.f, supc = 0.f, pro = 0.f, proc = 0.f, plab = 0.f;
+    for (int r = tid; r < ns; r += 256) {
+        float ys;
+        const float ce = ce_row(pred + ((long)b * Kmax + r) * C, y_all + ((long)b * Kmax + r) * C, C, eps, &ys);
+        if (r < nl) {
+            sup += ce;
+            supc += (ys > 0.f) ? 1.f : 0.f;
+        } else {
+            pro += ce;
+            proc += (ys > 0.f) ? 1.f : 0.f;
+            plab += ys;
+        }
+    }
+    sup = block_sum256(sup, sh);
+    supc = block_sum256(supc, sh);
+    pro = block_sum256(pro, sh);
+    proc = block_sum256(proc, sh);
+    plab = block_sum256(plab, sh);
+    if (tid == 0 && i0 == 0) {
+        float l = (supc > 0.f) ? sup / supc : 0.f;
+        if (nl < ns && proc > 0.f) l += prop_weight * (pro / proc);
+        float* t = terms + (long)b * 8;
+        t[0] = sup; t[1] = supc; t[2] = pro; t[3] = proc; t[4] = plab; t[5] = l; t[6] = 0.f; t[7] = 0.f;
+    }
+    // dpred of the block's rows (loss_bwd_kernel's expression), then dz
+    if (tid < CLS_ROWS) {
+        const int r = i0 + tid;                           // row inside the image (< Kmax)
+        const long gr = r0 + tid;
+        float coef = 0.f;
+        if (r < ns) {
+            if (r < nl) coef = (supc > 0.f) ? 1.f / supc : 0.f;
+            else coef = (nl < ns && proc > 0.f) ? prop_weight / proc : 0.f;
+        }
+        for (int c = 0; c < C; ++c) {
+            const float p = pred[gr * C + c];
+            float g = 0.f;
+            if (r < ns && p >= eps && p <= 1.f - eps) g = dloss[0] * (1.f / (float)B) * coef * (-y_all[gr * C + c] / p);
+            dpred[gr * C + c] = g;
+            dz[tid][c] = g;
+        }
+        cls_dz_row(pred + gr * C, dz[tid], C);
+    }
+    __syncthreads();
+    cls_bwd_c_tail(feat, Wc, nullptr, dfeat, part + (long)blockIdx.x * (C * D + C), dz, r0, (long)B * Kmax, D, C);
+}
+extern "C" int wesup_head_bwd_c(const float* feat, const float* Wc, const float* pred, const float* y_all, const int32_t* n_sp,
+                                const int32_t* n_l, const float* dloss, float eps, float prop_weight, float* terms, float* dpred,
+                                float* dfeat, int B, int Kmax, int D, int C, void* ws, size_t ws_bytes, void* stream) {
+    if (!feat || !Wc || !pred || !y_all || !n_sp || !n_l || !dloss || !terms || !dpred || !dfeat || !ws || B <= 0 || Kmax <= 0 ||
+        (Kmax % CLS_ROWS) || D <= 0 || !cls_c_range(C))
+        return WESUP_ERR_INVALID;
+    const int R = B * Kmax;
+    if (ws_bytes < wesup_classifier_bwd_c_workspace_bytes(R, D, C)) return WESUP_ERR_WORKSPACE;
+    WESUP_LAUNCH(head_bwd_c_kernel, dim3(R / CLS_ROWS), dim3(256), 0, (hipStream_t)stream, feat, Wc, pred, y_all, n_sp, n_l,
+                 dloss, eps, prop_weight, terms, dpred, dfeat, (float*)ws, B, Kmax, D, C);
+    WESUP_CHECK_LAUNCH();
+    return WESUP_OK;
+}
+extern "C" int wesup_classifier_bwd_c_finish(const void* ws, size_t ws_bytes, float* dWc, float* dbc, int R, int D, int C,
+                                             void* stream) {
+    if (!ws || !dWc || !dbc || R <= 0 || D <= 0 || !cls_c_range(C)) return WESUP_ERR_INVALID;
+    if (ws_bytes < wesup_classifier_bwd_c_workspace_bytes(R, D, C)) return WESUP_ERR_WORKSPACE;
+    WESUP_LAUNCH(classifier_bwd_c_reduce, dim3(ceil_div(C * D + C, 64)), dim3(64), 0, (hipStream_t)stream, (const float*)ws, dWc,
+                 dbc, ceil_div(R, CLS_ROWS), D, C);
+    WESUP_CHECK_LAUNCH();
+    return WESUP_OK;
+}
+
 // generic _cross_entropy on (n, C)
 __global__ __launch_bounds__(256) void ce_fwd_kernel(const float* __restrict__ y_hat, const float* __restrict__ y_true,
                                                      const float* __restrict__ cw, float eps, float* __restrict__ out2,
@@ -622,6 +928,79 @@ extern "C" int wesup_seg_metrics(const float* pred, const uint8_t* mask, float* 
     hipStream_t st = (hipStream_t)stream;
     WESUP_LAUNCH(seg_metrics_kernel, dim3(SEG_BLOCKS, B), dim3(256), 0, st, pred, mask, (float*)ws, HW, C);
     WESUP_LAUNCH(seg_metrics_reduce, dim3(ceil_div(B * 4, 64)), dim3(64), 0, st, (const float*)ws, out4, B);
+    WESUP_CHECK_LAUNCH();
+    return WESUP_OK;
+}
+
+// ------------------------------------------------------------------ class maps and their confusion table (more than two classes)
+// paint: the index of a superpixel's largest probability (the first maximum: ties go to the lowest class), once per superpixel
+// row into ws, then one gather per pixel -- C is not scanned per pixel.
+__global__ void row_argmax_kernel(const float* __restrict__ sp_pred, float* __restrict__ cls, long rows, int C) {
+    const long r = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= rows) return;
+    const float* p = sp_pred + r * C;
+    float best = p[0];
+    int bi = 0;
+    for (int c = 1; c < C; ++c) {
+        const float v = p[c];
+        if (v > best) { best = v; bi = c; }
+    }
+    cls[r] = (float)bi;
+}
+__global__ void paint_rows_kernel(const float* __restrict__ cls, const int32_t* __restrict__ new_row, float* __restrict__ pred,
+                                  long HW, int Kmax, long total) {
+    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= total) return;
+    const long b = idx / HW;
+    pred[idx] = cls[b * Kmax + new_row[idx]];
+}
+extern "C" size_t wesup_paint_argmax_workspace_bytes(int B, int Kmax) {
+    return (B > 0 && Kmax > 0) ? (size_t)B * Kmax * sizeof(float) : 0;
+}
+extern "C" int wesup_paint_argmax(const float* sp_pred, const int32_t* new_row, float* pred, int B, int HW, int Kmax, int C,
+                                  void* ws, size_t ws_bytes, void* stream) {
+    if (!sp_pred || !new_row || !pred || !ws || B <= 0 || HW <= 0 || Kmax <= 0 || !cls_c_range(C)) return WESUP_ERR_INVALID;
+    if (ws_bytes < wesup_paint_argmax_workspace_bytes(B, Kmax)) return WESUP_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const long rows = (long)B * Kmax, total = (long)B * HW;
+    WESUP_LAUNCH(row_argmax_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, sp_pred, (float*)ws, rows, C);
+    WESUP_LAUNCH(paint_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const float*)ws, new_row, pred,
+                 (long)HW, Kmax, total);
+    WESUP_CHECK_LAUNCH();
+    return WESUP_OK;
+}
+// conf[b][g][p]: pixels of image b with ground-truth class g (the first maximum over the mask's C planes, as seg_metrics_kernel)
+// and predicted class p.  Integer counts: a block adds its pixels up in LDS, then adds its table to the image's -- integer sums
+// do not depend on the order.  The entry zeroes conf and status itself.  A predicted value outside [0, C) sets status.
+__global__ __launch_bounds__(256) void seg_confusion_kernel(const float* __restrict__ pred, const uint8_t* __restrict__ mask,
+                                                            int32_t* __restrict__ conf, int32_t* __restrict__ status, int HW,
+                                                            int C) {
+    __shared__ int32_t tab[WESUP_MAX_CLASSES * WESUP_MAX_CLASSES];
+    const int b = blockIdx.y;
+    if (threadIdx.x < C * C) tab[threadIdx.x] = 0;
+    __syncthreads();
+    for (int p = blockIdx.x * 256 + threadIdx.x; p < HW; p += SEG_BLOCKS * 256) {
+        const float P = rintf(pred[(long)b * HW + p]);
+        int gi = 0;
+        uint8_t best = mask[((long)b * C) * HW + p];
+        for (int c = 1; c < C; ++c) {
+            const uint8_t v = mask[((long)b * C + c) * HW + p];
+            if (v > best) { best = v; gi = c; }
+        }
+        if (P >= 0.f && P < (float)C) atomicAdd(&tab[gi * C + (int)P], 1);
+        else atomicOr(status, 1);                 // (a NaN lands here too)
+    }
+    __syncthreads();
+    if (threadIdx.x < C * C && tab[threadIdx.x] != 0) atomicAdd(&conf[(long)b * C * C + threadIdx.x], tab[threadIdx.x]);
+}
+extern "C" int wesup_seg_confusion(const float* pred, const uint8_t* mask, int32_t* conf, int32_t* status, int B, int HW, int C,
+                                   void* stream) {
+    if (!pred || !mask || !conf || !status || B <= 0 || HW <= 0 || !cls_c_range(C)) return WESUP_ERR_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    int rc = wesup_fill_words_(conf, 0u, (size_t)B * C * C, st);
+    if (rc == WESUP_OK) rc = wesup_fill_words_(status, 0u, 1, st);
+    if (rc != WESUP_OK) return rc;
+    WESUP_LAUNCH(seg_confusion_kernel, dim3(SEG_BLOCKS, B), dim3(256), 0, st, pred, mask, conf, status, HW, C);
     WESUP_CHECK_LAUNCH();
     return WESUP_OK;
 }

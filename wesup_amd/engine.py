@@ -263,8 +263,8 @@ class WesupEngine:
 
     def _table(self, b, plan):
         """layer_plan.buffers of set b under plan: every buffer that walk touches."""
-        return layer_plan.buffers(plan, b.groups, b.Kmax, self.D,
-                                  lambda R, D: ops._lib.load().wesup_classifier_bwd_workspace_bytes(R, D))
+        C = self.n_classes
+        return layer_plan.buffers(plan, b.groups, b.Kmax, self.D, lambda R, D: ops.classifier_bwd_bytes(R, D, C), C=C)
 
     @staticmethod
     def _empty_set(B, H, W, Kmax=0, groups=(), group_of=(None,) * 13):
@@ -367,6 +367,12 @@ class WesupEngine:
     # ------------------------------------------------------------------ the plan
     BENCH_SHAPE = (4, 480, 480)      # what a weight prefetch in front of the very first forward packs for
 
+    @property
+    def n_classes(self):
+        """Classes of the head, read from the classifier's weight (2: the two-class kernels; more: the *_c entries)."""
+        w = self.p.get('classifier.0.weight')
+        return 2 if w is None else int(w.shape[0])
+
     def _switches(self):
         return layer_plan.Switches(self.fuse_pool_bwd, self.fuse_pool_fwd, self.two_streams, self.wgrad_winograd, self.conv_winograd,
                                    self.plain, self.matrix_pool, self.fuse_side_fwd, self.WINOGRAD_MIN_CI, self.WINOGRAD_MIN_CO,
@@ -386,7 +392,7 @@ class WesupEngine:
         """Everything layer_plan.build reads besides the grouping a buffer set was made with: a changed key is a new plan (and a
         new recording of the step runner)."""
         return (self._switches(), self._route_of(B, H, W) if route is None else route, ops.winograd_fused_min_blocks(),
-                frozenset(self.frozen), frozenset(self._diag_skip), bool(train))
+                frozenset(self.frozen), frozenset(self._diag_skip), bool(train), self.n_classes)
 
     def _plan(self, b, train, route=None):
         """The plan of buffer set b for a training / evaluation walk, rebuilt when its key changes (tests flip switches on a live
@@ -623,7 +629,8 @@ class WesupEngine:
 
     def forward(self, img, meta, train=True, need_paint=True, head=True):
         """img (B,3,H,W) fp32 on the GPU, meta = ops.sp_preprocess(...).  Returns (feats, sp_pred, pred)
-        shaped (B,Kmax,D), (B,Kmax,2), (B,H,W); buffers are reused by the next call of the same shape."""
+        shaped (B,Kmax,D), (B,Kmax,C), (B,H,W); buffers are reused by the next call of the same shape.  pred: the class-1
+        probability for two classes, the class map (argmax, as floats) for more."""
         B, _, H, W = img.shape
         Kmax = meta.Kmax
         assert (meta.B, meta.H, meta.W) == (B, H, W)
@@ -663,9 +670,9 @@ class WesupEngine:
         # paints behind it; sp_pred is then not yet filled when this returns
         if head:
             ops.classifier_fwd(b.feats, p['classifier.0.weight'], p['classifier.0.bias'], b.sp_pred)
-        sp_pred3 = b.sp_pred.view(B, Kmax, 2)
+        sp_pred3 = b.sp_pred.view(B, Kmax, self.n_classes)
         if need_paint and head:
-            ops.paint_fwd(sp_pred3, meta, 1, out=b.pred)
+            ops.paint(sp_pred3, meta, out=b.pred)
         self.ctx = (b, pk, meta, B, H, W, Kmax) if train else None
         return b.feats.view(B, Kmax, self.D), sp_pred3, b.pred
 
@@ -741,7 +748,7 @@ class WesupEngine:
         self.ctx = None
 
     def backward(self, dfeat_extra, dpred, head_done=False):
-        """dpred (B,Kmax,2) [and optional dfeat_extra (B,Kmax,D)]: gradients of the loss w.r.t. sp_pred /
+        """dpred (B,Kmax,C) [and optional dfeat_extra (B,Kmax,D)]: gradients of the loss w.r.t. sp_pred /
         sp_features.  Writes every parameter gradient into self.g (overwrites)."""
         assert self.ctx is not None, 'backward without a training-mode forward'
         b, pk, meta, B, H, W, Kmax = self.ctx
@@ -768,7 +775,7 @@ class WesupEngine:
         # head_done: ops.head_bwd (loss + its gradient + the classifier's backward in one launch, the step runner) has written
         # b.dfeat and left the partial sums of the classifier's weight gradient in its workspace; they are added up off the chain
         if not head_done:
-            ops.classifier_bwd(b.feats, p['classifier.0.weight'], b.sp_pred, dpred.reshape(R, 2),
+            ops.classifier_bwd(b.feats, p['classifier.0.weight'], b.sp_pred, dpred.reshape(R, self.n_classes),
                                None if dfeat_extra is None else dfeat_extra.reshape(R, D),
                                b.dfeat, g['classifier.0.weight'], g['classifier.0.bias'])
         else:

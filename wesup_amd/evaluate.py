@@ -152,6 +152,8 @@ def test(ckpt_path, model_type='wesup', input_size=None, scales=(0.5,), device='
     from .models import initialize_trainer
     ckpt_path = Path(ckpt_path)
     trainer = initialize_trainer(model_type, device=device)
+    from .models import require_two_class_checkpoint
+    require_two_class_checkpoint(ckpt_path, 'GlaS evaluation')
     trainer.load_checkpoint(ckpt_path)
     record_dir = ckpt_path.parent.parent
     results_dir = record_dir / ('results' if input_size is not None else f'results-{len(scales)}scale')

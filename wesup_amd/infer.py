@@ -41,10 +41,20 @@ def _cross(size=9):
     return selem
 
 
+def n_classes_of(trainer):
+    """Classes of the trainer's model (2 when neither the model nor the trainer's kwargs say)."""
+    C = getattr(getattr(trainer, 'model', None), 'n_classes', None)
+    return int(C or (getattr(trainer, 'kwargs', None) or {}).get('n_classes') or 2)
+
+
 def predict(trainer, dataset, input_size=None, scales=(0.5,), device='cuda', device_post=False):
-    """Predict every image of ``dataset`` (raw items of utils.data.SegmentationDataset).  Returns a list of (H,W) masks.
+    """Predict every image of ``dataset`` (raw items of utils.data.SegmentationDataset).  Returns a list of (H,W) masks --
+    class-index maps for a model of more than two classes, which single-scale and fixed-size inference handle unchanged.
     ``device_post``: the opening of a multi-scale prediction runs on the device too (ops.binary_opening: scipy's conventions
     bit for bit) and the mask is copied to the host once, after it."""
+    if n_classes_of(trainer) > 2 and input_size is None and len(scales) > 1:
+        raise ValueError('multi-scale inference averages the rounded maps of the scales and rounds again: undefined for class '
+                         f'indices ({n_classes_of(trainer)} classes) -- use one scale or a fixed input size')
     from scipy import ndimage
     predictions = []
     for i in range(len(dataset)):
@@ -82,12 +92,13 @@ def predict(trainer, dataset, input_size=None, scales=(0.5,), device='cuda', dev
     return predictions
 
 
-def save_predictions(predictions, dataset, output_dir='predictions'):
+def save_predictions(predictions, dataset, output_dir='predictions', n_classes=2):
+    """One PNG per image: {0, 255} for two classes, the class indices themselves for more."""
     from PIL import Image
     output_dir = Path(output_dir)
     output_dir.mkdir(parents=True, exist_ok=True)
     for pred, img_path in zip(predictions, dataset.img_paths):
-        Image.fromarray(pred.astype('uint8') * 255).save(output_dir / f'{img_path.stem}.png')
+        Image.fromarray(pred.astype('uint8') * (255 if n_classes == 2 else 1)).save(output_dir / f'{img_path.stem}.png')
 
 
 def evaluate_predictions(predictions, dataset, device=None):
@@ -114,10 +125,10 @@ def evaluate_predictions(predictions, dataset, device=None):
 
 def infer(trainer, data_dir, output_dir=None, input_size=None, scales=(0.5,), device='cuda', device_post=False):
     trainer.model.eval()
-    dataset = SegmentationDataset(data_dir, train=False)
+    dataset = SegmentationDataset(data_dir, train=False, n_classes=n_classes_of(trainer))
     predictions = predict(trainer, dataset, input_size=input_size, scales=scales, device=device, device_post=device_post)
     if output_dir is not None:
-        save_predictions(predictions, dataset, output_dir)
+        save_predictions(predictions, dataset, output_dir, n_classes=n_classes_of(trainer))
     return predictions
 
 
@@ -135,7 +146,9 @@ def main(argv=None):
     output_dir = a.output_dir
     if output_dir is None and a.checkpoint is not None:
         output_dir = Path(a.checkpoint).parent.parent / 'results'
-    trainer = initialize_trainer(a.model_type, device=a.device)
+    from .models import checkpoint_n_classes
+    C = checkpoint_n_classes(a.checkpoint) if a.checkpoint is not None else 2
+    trainer = initialize_trainer(a.model_type, device=a.device, n_classes=C)
     if a.checkpoint is not None:
         trainer.load_checkpoint(a.checkpoint)
     infer(trainer, a.data_dir, output_dir, input_size=a.input_size, scales=tuple(a.scales), device=a.device,

@@ -226,6 +226,8 @@ def _load_pixel_model(checkpoint, device):
     from .models.wesup import WESUPPixelInference
     model = WESUPPixelInference().to(device)
     if checkpoint is not None:
+        from .models import require_two_class_checkpoint
+        require_two_class_checkpoint(checkpoint, 'tile / pixel inference')
         model.load_state_dict(torch.load(checkpoint, map_location=device)['model_state_dict'])
     return model
 
@@ -252,6 +254,8 @@ def main(argv=None):
         return
     trainer = initialize_trainer(a.model_type, device=a.device)
     if a.checkpoint is not None:
+        from .models import require_two_class_checkpoint
+        require_two_class_checkpoint(a.checkpoint, 'tile inference')
         trainer.load_checkpoint(a.checkpoint)
     infer(trainer, a.data_dir, a.patch_size, output_dir, device=a.device, batch=a.batch)
 

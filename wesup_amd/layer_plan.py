@@ -256,11 +256,12 @@ def build(shape, group_of, route, switches, diag_skip, frozen, train, fused_supp
                     fm=not sw.fuse_pool_fwd, dfm=bool(train and not sw.fuse_pool_bwd), dp_on_load=tuple(dp_on_load))
 
 
-def buffers(plan, groups, Kmax, D, cls_part_bytes):
+def buffers(plan, groups, Kmax, D, cls_part_bytes, C=2):
     """Every buffer the walk under ``plan`` reads or writes, as Buf records: what a set of that shape holds once it has been fitted
     to the plan (engine._fit), and so what it costs (``nbytes``).  groups: the set's Group records (groups_for); cls_part_bytes: the
     size of the classifier's partial-sum block, a number or a callable (rows, D) -> bytes (what ops.head_bwd_partials asks the
-    library for)."""
+    library for).  C: classes of the classifier -- the width of sp_pred, and (through cls_part_bytes, which the engine forms for its
+    C) of the partial-sum block; the loss gradient dpred (B, Kmax, C) is the step runner's, not the set's."""
     B, H, W = plan.shape[:3]
     R, Ls = B * Kmax, plan.layers
     out = []
@@ -303,7 +304,7 @@ def buffers(plan, groups, Kmax, D, cls_part_bytes):
     add('h1', None, (R, 1024))
     add('h2', None, (R, 1024))
     add('feats', None, (R, D))
-    add('sp_pred', None, (R, 2))
+    add('sp_pred', None, (R, C))
     add('pred', None, (B, H, W))
     if not plan.train:
         return tuple(out)

@@ -1,5 +1,5 @@
 """Factory of the reference (models/__init__.py:9-19)."""
-from .wesup import WESUP, WESUPConfig, WESUPTrainer
+from .wesup import WESUP, WESUPConfig, WESUPTrainer, checkpoint_n_classes, require_two_class_checkpoint
 
 
 def initialize_trainer(model_type, **kwargs):

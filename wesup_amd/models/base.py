@@ -186,6 +186,8 @@ class BaseTrainer(ABC):
         metrics = dict()
         seg = None
         fast, names = self._fast_metrics()
+        # (more than two classes: the general path scores on the host, evaluate(); the step runner counts a confusion table)
+        fast = fast and int(self.kwargs.get('n_classes') or 2) == 2
         pixel_mask = target[0] if isinstance(target, (tuple, list)) else None
         has_gt = pixel_mask is not None and torch.is_tensor(pixel_mask) and not is_empty_tensor(pixel_mask)
 
@@ -415,7 +417,11 @@ class BaseTrainer(ABC):
         if target is None:
             return dict()
         metrics = defaultdict(list)
+        # more than two classes: accuracy / dice by their confusion-table definitions (utils/metrics.py); two: as ever
+        C = int(self.kwargs.get('n_classes') or 2)
+        multi = {'accuracy': M.accuracy_multiclass, 'dice': M.dice_multiclass} if C > 2 else {}
         for P, G in zip(pred, target):
             for func in self.metric_funcs:
-                metrics[func.__name__].append(func(P, G))
+                name = func.__name__
+                metrics[name].append(multi[name](P, G, C) if name in multi else func(P, G))
         return {k: np.mean(v) for k, v in metrics.items()}

@@ -246,6 +246,24 @@ def load_backbone_weights(backbone, path):
     backbone.load_state_dict(picked)
 
 
+def checkpoint_n_classes(checkpoint):
+    """Classes of the model a checkpoint holds (a path, a loaded checkpoint dict or a state_dict): rows of classifier.0.weight."""
+    if not isinstance(checkpoint, dict):
+        checkpoint = torch.load(checkpoint, map_location='cpu')
+    sd = checkpoint.get('model_state_dict', checkpoint)
+    return int(sd['classifier.0.weight'].shape[0])
+
+
+def require_two_class_checkpoint(checkpoint, what):
+    """The tools that read the class-1 probability (pixel_infer, infer_tile, slide, evaluate) are two-class: a checkpoint of a
+    model with more classes is refused, not read through column 1."""
+    if checkpoint is not None:
+        C = checkpoint_n_classes(checkpoint)
+        if C != 2:
+            raise ValueError(f'{what} is two-class (it reads the class-1 probability): the checkpoint holds a {C}-class model; '
+                             'wesup_amd.infer writes class-index maps for it')
+
+
 def _vgg16_features():
     """torchvision VGG16 cfg "D" layer list (models/wesup.py:199); random init unless ``backbone_weights`` names a
     file with the ImageNet weights the reference downloads (no network here)."""
@@ -277,7 +295,7 @@ class _WesupFn(torch.autograd.Function):
     def backward(ctx, dfeat, dpred, _dpaint):
         model = ctx.model
         if dpred is None:
-            dpred = torch.zeros(model.engine.ctx[3], model.engine.ctx[6], 2, device=model.engine.device)
+            dpred = torch.zeros(model.engine.ctx[3], model.engine.ctx[6], model.engine.n_classes, device=model.engine.device)
         model.engine.backward(None if dfeat is None else dfeat.contiguous(), dpred.contiguous())
         model._publish_grads()
         return None, None, None, None
@@ -309,9 +327,13 @@ class WESUP(nn.Module):
             nn.Linear(self.fm_channels_sum, 1024), nn.ReLU(),
             nn.Linear(1024, 1024), nn.ReLU(),
             nn.Linear(1024, D), nn.ReLU())
-        # `n_classes` is a named parameter, so kwargs never holds it: the classifier is always
-        # 2-way in the reference (models/wesup.py:230).
-        self.classifier = nn.Sequential(nn.Linear(D, self.kwargs.get('n_classes', 2)), nn.Softmax(dim=1))
+        # In the reference `n_classes` is a named parameter, so kwargs never holds it and its classifier is always 2-way
+        # (models/wesup.py:230).  The one deliberate departure from that quirk: the classifier here is
+        # Linear(D, n_classes).  The default is 2, and state_dict keys and their order are the same for every class count.
+        if not 2 <= int(n_classes) <= 16:
+            raise ValueError(f'n_classes must be in [2, 16] (WESUP_MAX_CLASSES), got {n_classes}')
+        self.n_classes = int(n_classes)
+        self.classifier = nn.Sequential(nn.Linear(D, self.n_classes), nn.Softmax(dim=1))
         self.fm_size = None
         self.sp_features = None
         self.sp_pred = None
@@ -394,7 +416,9 @@ class WESUP(nn.Module):
 
     def forward(self, x):
         """x = (img (B,3,H,W), sp_maps) with sp_maps a dense (N,H,W) tensor as in the reference (B = 1)
-        or a SuperpixelMaps.  Returns the painted class-1 probability, (B,H,W)  (models/wesup.py:263-304)."""
+        or a SuperpixelMaps.  Returns the painted class-1 probability, (B,H,W)  (models/wesup.py:263-304); with more than two
+        classes the painted class map (the argmax of each superpixel's prediction, as floats), so that ``postprocess``
+        (``round().long()``) holds for both.  ``self.sp_pred`` holds all C columns."""
         img, sp_maps = x
         self._ensure_engine()
         if isinstance(sp_maps, SuperpixelMaps):
@@ -412,7 +436,7 @@ class WESUP(nn.Module):
         self.engine.frozen = {n for n, p in self._named if not p.requires_grad}
         feats, sp_pred, pred = _WesupFn.apply(self._anchor, self, img, meta)
         self._last_meta = meta
-        self._padded = (feats, sp_pred)        # (B,Kmax,D), (B,Kmax,2): what the batched loss consumes
+        self._padded = (feats, sp_pred)        # (B,Kmax,D), (B,Kmax,C): what the batched loss consumes
         if meta.B == 1 and meta.n_sp_host is not None:
             n = meta.n_sp_host[0]
             self.sp_features, self.sp_pred = feats[0, :n], sp_pred[0, :n]
@@ -560,7 +584,8 @@ class WESUPTrainer(BaseTrainer):
         from ..utils.data import get_dataset
         return get_dataset(root_dir, train=train, proportion=proportion,
                            multiscale_range=self.kwargs.get('multiscale_range'),
-                           rescale_factor=self.kwargs.get('rescale_factor'))
+                           rescale_factor=self.kwargs.get('rescale_factor'),
+                           n_classes=int(self.kwargs.get('n_classes') or 2))
 
     def get_default_optimizer(self):
         from ..optim import FusedSGD

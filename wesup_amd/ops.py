@@ -1072,6 +1072,27 @@ def paint_fwd(sp_pred, meta, cls=1, out=None):
     return out
 
 
+def paint_argmax(sp_pred, meta, out=None):
+    """Class-map paint-back for more than two classes: out (B,H,W) f32 = the index of each pixel's superpixel's largest probability
+    (first maximum), wesup_paint_argmax."""
+    _chk(sp_pred, name='sp_pred')
+    B, Kmax, C = sp_pred.shape
+    assert B == meta.B and Kmax == meta.Kmax
+    if out is None:
+        out = torch.empty(B, meta.H, meta.W, dtype=torch.float32, device=sp_pred.device)
+    nb = _lib.load().wesup_paint_argmax_workspace_bytes(B, Kmax)
+    ws = workspace(nb, sp_pred.device, 'argmax')
+    tok = _tbegin('paint')
+    _lib.call('wesup_paint_argmax', _p(sp_pred), _p(meta.new_row), _p(out), B, meta.H * meta.W, Kmax, C, _p(ws), nb, _stream())
+    _tend(tok, 8.0 * B * meta.H * meta.W + 4.0 * B * Kmax * (C + 2))
+    return out
+
+
+def paint(sp_pred, meta, out=None):
+    """What the model's forward returns per pixel: the class-1 probability for two classes, the class map (as floats) for more."""
+    return paint_fwd(sp_pred, meta, 1, out=out) if sp_pred.shape[2] == 2 else paint_argmax(sp_pred, meta, out=out)
+
+
 # ---------------------------------------------------------------- SLIC
 def slic(img, n_segments, compactness=40.0, max_iter=10, enforce_connectivity=True, min_size_factor=0.5):
     """GPU SLIC: img (B,3,H,W) RGB in [0,1] -> (labels (B,H,W) int32 with contiguous ids, n_labels (B,) int32)."""
@@ -1088,30 +1109,65 @@ def slic(img, n_segments, compactness=40.0, max_iter=10, enforce_connectivity=Tr
 
 
 # ---------------------------------------------------------------- head / loss / optimiser
+MAX_CLASSES = _lib.MAX_CLASSES       # WESUP_MAX_CLASSES: the *_c entries take 2 <= C <= MAX_CLASSES
+
+
 def classifier_fwd(feat, Wc, bc, out=None):
+    """softmax(feat . Wc^T + bc): (R, D) -> (R, C), C = Wc.shape[0].  Two classes: wesup_classifier_fwd, more: wesup_classifier_fwd_c."""
     _chk(feat, name='feat'); _chk(Wc, name='Wc'); _chk(bc, name='bc')
     R, D = feat.shape
-    assert Wc.shape == (2, D) and bc.numel() == 2
+    C = Wc.shape[0]
+    assert Wc.shape == (C, D) and bc.numel() == C
     if out is None:
-        out = torch.empty(R, 2, dtype=torch.float32, device=feat.device)
-    _lib.call('wesup_classifier_fwd', _p(feat), _p(Wc), _p(bc), _p(out), R, D, _stream())
+        out = torch.empty(R, C, dtype=torch.float32, device=feat.device)
+    assert out.numel() == R * C
+    if C == 2:
+        _lib.call('wesup_classifier_fwd', _p(feat), _p(Wc), _p(bc), _p(out), R, D, _stream())
+    else:
+        _lib.call('wesup_classifier_fwd_c', _p(feat), _p(Wc), _p(bc), _p(out), R, D, C, _stream())
     return out
 
 
-def classifier_bwd(feat, Wc, pred, dpred, dfeat_extra=None, dfeat=None, dWc=None, dbc=None):
+def classifier_fwd_c(feat, Wc, bc, out=None):
+    """wesup_classifier_fwd_c for any 2 <= C <= MAX_CLASSES (classifier_fwd calls it for C > 2)."""
+    _chk(feat, name='feat'); _chk(Wc, name='Wc'); _chk(bc, name='bc')
+    R, D = feat.shape
+    C = Wc.shape[0]
+    assert Wc.shape == (C, D) and bc.numel() == C
+    if out is None:
+        out = torch.empty(R, C, dtype=torch.float32, device=feat.device)
+    _lib.call('wesup_classifier_fwd_c', _p(feat), _p(Wc), _p(bc), _p(out), R, D, C, _stream())
+    return out
+
+
+def classifier_bwd_bytes(R, D, C=2):
+    """Bytes of the classifier's per-64-row partial sums of dWc / dbc."""
+    lib = _lib.load()
+    return lib.wesup_classifier_bwd_workspace_bytes(R, D) if C == 2 else lib.wesup_classifier_bwd_c_workspace_bytes(R, D, C)
+
+
+def classifier_bwd(feat, Wc, pred, dpred, dfeat_extra=None, dfeat=None, dWc=None, dbc=None, generic=False):
+    """Backward of classifier_fwd; C = Wc.shape[0].  generic: wesup_classifier_bwd_c also for two classes."""
     _chk(feat, name='feat'); _chk(pred, name='pred'); _chk(dpred, name='dpred')
     R, D = feat.shape
-    assert pred.shape == (R, 2) and dpred.shape == (R, 2)
+    C = Wc.shape[0]
+    assert pred.shape == (R, C) and dpred.shape == (R, C)
     if dfeat_extra is not None:
         _chk(dfeat_extra, name='dfeat_extra'); assert dfeat_extra.shape == (R, D)
     dev = feat.device
     dfeat = torch.empty(R, D, dtype=torch.float32, device=dev) if dfeat is None else dfeat
-    dWc = torch.empty(2, D, dtype=torch.float32, device=dev) if dWc is None else dWc
-    dbc = torch.empty(2, dtype=torch.float32, device=dev) if dbc is None else dbc
-    nb = _lib.load().wesup_classifier_bwd_workspace_bytes(R, D)
-    ws = workspace(nb, dev, 'cls')
-    _lib.call('wesup_classifier_bwd', _p(feat), _p(Wc), _p(pred), _p(dpred), _p(dfeat_extra), _p(dfeat), _p(dWc), _p(dbc),
-              R, D, _p(ws), nb, _stream())
+    dWc = torch.empty(C, D, dtype=torch.float32, device=dev) if dWc is None else dWc
+    dbc = torch.empty(C, dtype=torch.float32, device=dev) if dbc is None else dbc
+    if C == 2 and not generic:
+        nb = _lib.load().wesup_classifier_bwd_workspace_bytes(R, D)
+        ws = workspace(nb, dev, 'cls')
+        _lib.call('wesup_classifier_bwd', _p(feat), _p(Wc), _p(pred), _p(dpred), _p(dfeat_extra), _p(dfeat), _p(dWc), _p(dbc),
+                  R, D, _p(ws), nb, _stream())
+    else:
+        nb = _lib.load().wesup_classifier_bwd_c_workspace_bytes(R, D, C)
+        ws = workspace(nb, dev, 'cls')
+        _lib.call('wesup_classifier_bwd_c', _p(feat), _p(Wc), _p(pred), _p(dpred), _p(dfeat_extra), _p(dfeat), _p(dWc), _p(dbc),
+                  R, D, C, _p(ws), nb, _stream())
     return dfeat, dWc, dbc
 
 
@@ -1161,15 +1217,18 @@ def loss_bwd(pred, y_all, meta, terms, dloss, eps, prop_weight, out=None):
 
 
 def head_fwd(feat, Wc, bc, pred, meta, threshold, enable=True, out=None):
-    """classifier_fwd + propagate in one launch (wesup_head_fwd): feat (B,Kmax,D) -> pred (B*Kmax,2) and (y_all, src_idx, max_sim)."""
+    """classifier_fwd + propagate in one launch (wesup_head_fwd; wesup_head_fwd_c for more than two classes): feat (B,Kmax,D) ->
+    pred (B*Kmax,C) and (y_all, src_idx, max_sim)."""
     _chk(feat, name='feat'); _chk(Wc, name='Wc'); _chk(bc, name='bc'); _chk(pred, name='pred')
     B, Kmax, D = feat.shape
-    assert B == meta.B and Kmax == meta.Kmax and Wc.shape == (2, D) and bc.numel() == 2 and pred.numel() == B * Kmax * 2
+    C = Wc.shape[0]
+    assert B == meta.B and Kmax == meta.Kmax and Wc.shape == (C, D) and bc.numel() == C and pred.numel() == B * Kmax * C
+    assert C == meta.C, 'the classifier and the label masks disagree about the number of classes'
     y_all, src, sim = out
     assert y_all.shape == (B, Kmax, meta.C) and src.shape == (B, Kmax) == sim.shape and src.dtype == torch.int32
     tok = _tbegin('propagate')
-    _lib.call('wesup_head_fwd', _p(feat), _p(Wc), _p(bc), _p(pred), _p(meta.sp_labels), _p(meta.n_sp), _p(meta.n_l), float(threshold),
-              int(enable), _p(y_all), _p(src), _p(sim), B, Kmax, D, meta.C, _stream())
+    _lib.call('wesup_head_fwd' if C == 2 else 'wesup_head_fwd_c', _p(feat), _p(Wc), _p(bc), _p(pred), _p(meta.sp_labels), _p(meta.n_sp),
+              _p(meta.n_l), float(threshold), int(enable), _p(y_all), _p(src), _p(sim), B, Kmax, D, meta.C, _stream())
     _tend(tok, 4.0 * B * Kmax * (D + 2 * meta.C + 2))
     return y_all, src, sim
 
@@ -1178,33 +1237,43 @@ def head_bwd_supported(Kmax, C):
     return Kmax % 64 == 0 and C == 2
 
 
-def head_bwd_partials(R, D, device):
+def head_c_supported(Kmax, C):
+    """The fused head launches for more than two classes (wesup_head_fwd_c / wesup_head_bwd_c)."""
+    return Kmax % 64 == 0 and 2 < C <= MAX_CLASSES
+
+
+def head_bwd_partials(R, D, device, C=2):
     """The buffer wesup_head_bwd leaves the partial sums of dWc / dbc in and wesup_classifier_bwd_finish reads (on another stream,
     launches later): owned by the caller -- the engine keeps one per buffer set -- never a shared grow-only workspace, which another
     tag's growth may replace between the two calls."""
-    return torch.empty(max(int(_lib.load().wesup_classifier_bwd_workspace_bytes(R, D)), 256), dtype=torch.uint8, device=device)
+    return torch.empty(max(int(classifier_bwd_bytes(R, D, C)), 256), dtype=torch.uint8, device=device)
 
 
 def head_bwd(feat, Wc, pred, y_all, meta, dloss, eps, prop_weight, terms, dpred, dfeat, partials):
     """loss_fwd (terms) + loss_bwd (dpred) + the first kernel of classifier_bwd (dfeat, partial sums of dWc / dbc into ``partials``,
-    see head_bwd_partials) in one launch (wesup_head_bwd); classifier_bwd_finish adds the partial sums up."""
+    see head_bwd_partials) in one launch (wesup_head_bwd; wesup_head_bwd_c for more than two classes); classifier_bwd_finish adds
+    the partial sums up."""
     _chk(feat, name='feat'); _chk(pred, name='pred'); _chk(y_all, name='y_all'); _chk(dloss, name='dloss')
     _chk(partials, torch.uint8, 'partials')
     B, Kmax, C = y_all.shape
     R, D = feat.shape
     assert R == B * Kmax and pred.numel() == R * C and dpred.numel() == R * C and dfeat.shape == (R, D) and terms.shape == (B, 8)
-    assert head_bwd_supported(Kmax, C) and B == meta.B and Kmax == meta.Kmax
-    nb = _lib.load().wesup_classifier_bwd_workspace_bytes(R, D)
+    assert Wc.shape == (C, D) and (head_bwd_supported(Kmax, C) or head_c_supported(Kmax, C)) and B == meta.B and Kmax == meta.Kmax
+    nb = classifier_bwd_bytes(R, D, C)
     assert partials.numel() >= nb
-    _lib.call('wesup_head_bwd', _p(feat), _p(Wc), _p(pred), _p(y_all), _p(meta.n_sp), _p(meta.n_l), _p(dloss), float(eps),
-              float(prop_weight), _p(terms), _p(dpred), _p(dfeat), B, Kmax, D, C, _p(partials), nb, _stream())
+    _lib.call('wesup_head_bwd' if C == 2 else 'wesup_head_bwd_c', _p(feat), _p(Wc), _p(pred), _p(y_all), _p(meta.n_sp), _p(meta.n_l),
+              _p(dloss), float(eps), float(prop_weight), _p(terms), _p(dpred), _p(dfeat), B, Kmax, D, C, _p(partials), nb, _stream())
 
 
 def classifier_bwd_finish(partials, R, D, dWc, dbc):
     _chk(partials, torch.uint8, 'partials')
-    nb = _lib.load().wesup_classifier_bwd_workspace_bytes(R, D)
-    assert partials.numel() >= nb
-    _lib.call('wesup_classifier_bwd_finish', _p(partials), nb, _p(dWc), _p(dbc), R, D, _stream())
+    C = dWc.shape[0]
+    nb = classifier_bwd_bytes(R, D, C)
+    assert partials.numel() >= nb and dWc.shape == (C, D) and dbc.numel() == C
+    if C == 2:
+        _lib.call('wesup_classifier_bwd_finish', _p(partials), nb, _p(dWc), _p(dbc), R, D, _stream())
+    else:
+        _lib.call('wesup_classifier_bwd_c_finish', _p(partials), nb, _p(dWc), _p(dbc), R, D, C, _stream())
 
 
 def cross_entropy_fwd(y_hat, y_true, eps, class_weights=None):
@@ -1249,6 +1318,24 @@ def seg_metrics(pred, mask, out=None):
     ws = workspace(nb, pred.device, 'seg')
     _lib.call('wesup_seg_metrics', _p(pred), _p(mask), _p(out), B, H * W, C, _p(ws), nb, _stream())
     return out
+
+
+def seg_confusion(pred, mask, out=None, status=None):
+    """pred (B,H,W) f32 class indices, mask (B,C,H,W) uint8 -> (conf (B,C,C) int32, status (1,) int32): conf[b][g][p] = pixels of
+    ground-truth class g (first maximum over the mask's planes) predicted as p; status != 0: a predicted value outside [0, C).
+    Both are zeroed by the entry."""
+    _chk(pred, name='pred'); _chk(mask, torch.uint8, 'mask')
+    B, H, W = pred.shape
+    C = mask.shape[1]
+    assert mask.shape == (B, C, H, W)
+    if out is None:
+        out = torch.empty(B, C, C, dtype=torch.int32, device=pred.device)
+    if status is None:
+        status = torch.empty(1, dtype=torch.int32, device=pred.device)
+    _chk(out, torch.int32, 'conf'); _chk(status, torch.int32, 'status')
+    assert out.numel() == B * C * C and status.numel() == 1
+    _lib.call('wesup_seg_confusion', _p(pred), _p(mask), _p(out), _p(status), B, H * W, C, _stream())
+    return out, status
 
 
 # ---------------------------------------------------------------- mask post-processing and challenge scoring (csrc/regions.hip)

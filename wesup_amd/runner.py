@@ -90,12 +90,18 @@ class _State:
         self.gt = torch.empty(B, C, H, W, dtype=torch.uint8, device=dev) if has_gt else None
         self.meta = None
         # read-back block: loss | terms (B,8) | seg (B,4) | NaN flag of the other ranks as floats, then n_sp | n_l | status as
-        # int32 (the superpixel preprocessing writes them there): ONE copy brings the block to the host
-        self.n_f = 1 + 8 * B + 4 * B + 1
+        # int32 (the superpixel preprocessing writes them there): ONE copy brings the block to the host.  More than two classes:
+        # in the place of seg the confusion table (B,C,C) and its status word, int32 bit patterns (ops.seg_confusion)
+        self.n_seg = 4 * B if C == 2 else B * C * C + 1
+        self.n_f = 1 + 8 * B + self.n_seg + 1
         self.rb = torch.zeros(self.n_f + 3 * B, **f32)
         self.loss = self.rb[0:1]
         self.terms = self.rb[1:1 + 8 * B].view(B, 8)
-        self.seg = self.rb[1 + 8 * B:1 + 12 * B].view(B, 4)
+        if C == 2:
+            self.seg = self.rb[1 + 8 * B:1 + 12 * B].view(B, 4)
+        else:
+            seg = self.rb[1 + 8 * B:1 + 8 * B + self.n_seg].view(torch.int32)
+            self.conf, self.conf_status = seg[:B * C * C].view(B, C, C), seg[B * C * C:]
         self.rb_flag = self.rb[self.n_f - 1:self.n_f]
         self.rb_counts = self.rb[self.n_f:].view(torch.int32).view(3, B)
         self.host = torch.empty(self.n_f + 3 * B, dtype=torch.float32).pin_memory()
@@ -208,7 +214,7 @@ class StepRunner:
         has_gt = not is_empty_tensor(pixel_mask)
         names = [f.__name__ for f in (t.metric_funcs or [])]
         want_seg = has_gt and bool(names)
-        C = mask.shape[1] if mask is not None else (pixel_mask.shape[1] if has_gt else 2)
+        C = mask.shape[1] if mask is not None else (pixel_mask.shape[1] if has_gt else eng.n_classes)
         Kmax = t._kmax(counts, None, H, W)
         key = (B, H, W, C, Kmax, mask is not None, want_seg)
         st = self.states.pop(key, None)
@@ -363,18 +369,23 @@ class StepRunner:
             multi = red is not None and t.world_size > 1
             # One rank: the head of the step -- classifier, label propagation, loss, its gradient, the classifier's backward: six
             # launches on the chain between the fc layers' forward and backward -- in two (ops.head_fwd / head_bwd, bit-identical)
-            fuse = self.fuse_head and not multi and ops.head_bwd_supported(st.y_all.shape[1], st.y_all.shape[2])
+            # (more than two classes: the same walk over the *_c entries -- ops.head_fwd / head_bwd / paint dispatch on the class
+            # count --, with the confusion table where the two-class walk forms the four segmentation sums)
+            Kmax_, C_ = st.y_all.shape[1], st.y_all.shape[2]
+            if eng.n_classes != C_:
+                raise ValueError(f'the model has {eng.n_classes} classes, the masks of this batch have {C_}')
+            fuse = self.fuse_head and not multi and (ops.head_bwd_supported(Kmax_, C_) or ops.head_c_supported(Kmax_, C_))
             feats, sp_pred, pred = eng.forward(st.img, st.meta, train=True, need_paint=multi, head=not fuse)
             if want_seg and multi:
-                ops.seg_metrics(pred, st.gt, out=st.seg)
+                self._seg(st, pred)
             if fuse:
                 b, P = eng._last, eng.p
                 ops.head_fwd(feats, P['classifier.0.weight'], P['classifier.0.bias'], b.sp_pred, st.meta,
                              float(kw.get('propagate_threshold')), enable=bool(kw.get('enable_propagation')), out=(st.y_all, st.src, st.sim))
                 with eng.side_stream():                                   # (idle between the forward's last pooling and the backward)
-                    ops.paint_fwd(sp_pred, st.meta, 1, out=pred)          # (the pixel-wise prediction: metrics and callers only)
+                    ops.paint(sp_pred, st.meta, out=pred)                 # (the pixel-wise prediction: metrics and callers only)
                     if want_seg:
-                        ops.seg_metrics(pred, st.gt, out=st.seg)
+                        self._seg(st, pred)
                 ops.head_bwd(b.feats, P['classifier.0.weight'], b.sp_pred, st.y_all, st.meta, st.one, float(kw.get('epsilon')),
                              float(kw.get('propagate_weight')), st.terms, st.dpred, b.dfeat, b.cls_part)
                 st.rb_event = None
@@ -405,9 +416,9 @@ class StepRunner:
                     # between the last pooling of the forward and the first side-branch gradient), behind the loss.
                     st.rb_event = None
                     with eng.side_stream():
-                        ops.paint_fwd(sp_pred, st.meta, 1, out=pred)      # (the pixel-wise prediction: metrics and callers only)
+                        ops.paint(sp_pred, st.meta, out=pred)             # (the pixel-wise prediction: metrics and callers only)
                         if want_seg:
-                            ops.seg_metrics(pred, st.gt, out=st.seg)
+                            self._seg(st, pred)
                         _lib.call('wesup_copy_to_host', ctypes.c_void_p(st.host.data_ptr()), ops._p(st.rb), st.rb.numel() * 4, ops._stream())
                         ops.sync_record(RB_SLOT)
             if red is not None and red.profile:
@@ -455,6 +466,14 @@ class StepRunner:
         self._publish(st)
         return host
 
+    @staticmethod
+    def _seg(st, pred):
+        """The step's segmentation sums: accuracy / dice inputs for two classes, the confusion table for more."""
+        if st.y_all.shape[2] == 2:
+            ops.seg_metrics(pred, st.gt, out=st.seg)
+        else:
+            ops.seg_confusion(pred, st.gt, out=st.conf, status=st.conf_status)
+
     def _replay(self, st, metrics):
         plan = st.plan
         lib = _lib.load()
@@ -494,8 +513,14 @@ class StepRunner:
             for b in range(B):
                 s32 = np.float32(s32 + t32[b, 5])
             loss = float(np.float32(s32 / np.float32(B)))
-        host = {'loss': loss, 'terms': f[1:1 + 8 * B].reshape(B, 8), 'seg': f[1 + 8 * B:1 + 12 * B].reshape(B, 4),
+        host = {'loss': loss, 'terms': f[1:1 + 8 * B].reshape(B, 8),
                 'n_sp': cnt[0].astype(np.float64), 'n_l': cnt[1].astype(np.float64)}
+        C = st.y_all.shape[2]
+        if C == 2:
+            host['seg'] = f[1 + 8 * B:1 + 12 * B].reshape(B, 4)
+        else:
+            seg = raw[1 + 8 * B:1 + 8 * B + st.n_seg].view(np.int32)
+            host['conf'], host['conf_status'] = seg[:B * C * C].reshape(B, C, C).astype(np.int64), int(seg[B * C * C])
         nan_anywhere = f[st.n_f - 1] if st.rb_event is not None else 0.0
         if math.isnan(host['loss']) or nan_anywhere > 0:
             raise ValueError('Loss is nan!')
@@ -516,7 +541,14 @@ class StepRunner:
         t._metrics_from_terms(host, metrics)
         metrics['loss'] = host['loss']
         ev = {}
-        if want_seg:
+        if want_seg and 'conf' in host:
+            if host['conf_status']:
+                raise ValueError('the painted class map holds a value outside [0, n_classes)')
+            if 'accuracy' in names:
+                ev['accuracy'] = M.accuracy_from_confusion(host['conf'])
+            if 'dice' in names:
+                ev['dice'] = M.dice_from_confusion(host['conf'])
+        elif want_seg:
             if 'accuracy' in names:
                 ev['accuracy'] = M.accuracy_from_sums(host['seg'], H * W)
             if 'dice' in names:

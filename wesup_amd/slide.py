@@ -237,6 +237,8 @@ def main(data_root, checkpoint, model_type='wesup', pixel=False, patch_size=PATC
         else:
             from .models import initialize_trainer
             trainer = initialize_trainer(model_type, device=device)
+            from .models import require_two_class_checkpoint
+            require_two_class_checkpoint(checkpoint, 'whole-slide evaluation')
             trainer.load_checkpoint(checkpoint)
             trainer.model.eval()
         for path in sorted((data_root / 'images').glob('*.jpg')):

@@ -27,9 +27,9 @@ NO_CLASS = 255
 
 
 class SyntheticGlasDataset(torch.utils.data.Dataset):
-    def __init__(self, H=480, W=480, g=24, n=16, seed=0, frac=0.2, with_points=True):
+    def __init__(self, H=480, W=480, g=24, n=16, seed=0, frac=0.2, with_points=True, n_classes=2):
         self.H, self.W, self.g, self.n, self.seed, self.frac = H, W, g, n, seed, frac
-        self.with_points = with_points
+        self.with_points, self.n_classes = with_points, int(n_classes)
 
     def __len__(self):
         return self.n
@@ -42,10 +42,10 @@ class SyntheticGlasDataset(torch.utils.data.Dataset):
         s = self.seed * 100003 + i
         img = torch.from_numpy(synth.synth_image(s, self.H, self.W))
         seg = torch.from_numpy(synth.voronoi_labels(s, self.H, self.W, self.g))
-        pix = torch.from_numpy(synth.pixel_mask(s, self.H, self.W)).long()
+        pix = torch.from_numpy(synth.pixel_mask(s, self.H, self.W, self.n_classes)).long()
         if not self.with_points:
             return img, pix, torch.zeros(0), seg
-        pts = torch.from_numpy(synth.point_mask(s, seg.numpy(), self.frac, 2)).long()
+        pts = torch.from_numpy(synth.point_mask(s, seg.numpy(), self.frac, self.n_classes)).long()
         return img, pix, pts, seg
 
 
@@ -528,17 +528,19 @@ class DevicePrefetcher:
         return self._hand_over(item)
 
 
-def get_dataset(root_dir, train=True, proportion=1.0, multiscale_range=None, rescale_factor=None, target_size=None):
+def get_dataset(root_dir, train=True, proportion=1.0, multiscale_range=None, rescale_factor=None, target_size=None, n_classes=2):
     """WESUPTrainer.get_default_dataset (models/wesup.py:436-443): training data with a ``points`` directory is a
     Digest2019PointDataset, everything else a SegmentationDataset ('synthetic:H:W:g:n' makes synthetic items)."""
     root = str(root_dir)
     if 'synthetic:' in root:
         spec = root[root.index('synthetic:'):].split('/')[0].split(':')[1:]
         H, W, g, n = (int(v) for v in (spec + ['480', '480', '24', '16'][len(spec):])[:4])
-        return SyntheticGlasDataset(H, W, g, max(1, int(n * proportion)), seed=0 if train else 1)
+        return SyntheticGlasDataset(H, W, g, max(1, int(n * proportion)), seed=0 if train else 1, n_classes=n_classes)
     root_dir = Path(root_dir)
     if train and (root_dir / 'points').exists():                                       # models/wesup.py:436-443
-        return Digest2019PointDataset(root_dir, target_size=target_size, rescale_factor=rescale_factor,
-                                      multiscale_range=multiscale_range, train=train, proportion=proportion)
+        ds = Digest2019PointDataset(root_dir, target_size=target_size, rescale_factor=rescale_factor,
+                                    multiscale_range=multiscale_range, train=train, proportion=proportion)
+        ds.n_classes = int(n_classes)          # (one-hot planes of the masks, and what the trainer's DevicePrefetcher reads)
+        return ds
     return SegmentationDataset(root_dir, target_size=target_size, rescale_factor=rescale_factor, train=train,
-                               proportion=proportion, multiscale_range=multiscale_range)
+                               proportion=proportion, multiscale_range=multiscale_range, n_classes=int(n_classes))

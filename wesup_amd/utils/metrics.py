@@ -39,6 +39,42 @@ def dice_from_sums(sums, epsilon=1e-7):
     return float(np.mean(2 * sums[:, 1] / (sums[:, 3] + sums[:, 2] + epsilon)))
 
 
+# More than two classes: accuracy and Dice from the confusion table (rows: ground-truth class, columns: predicted class) that
+# ``wesup_seg_confusion`` counts on the device; ``confusion`` counts the same table on the host for the slow path.
+def confusion(P, G, n_classes):
+    """(C,C) int64 table of two class-index maps of one image: [g][p] = pixels of ground-truth class g predicted as p."""
+    P, G = _to_numpy(P).astype(np.int64).ravel(), _to_numpy(G).astype(np.int64).ravel()
+    if P.size and (P.min() < 0 or P.max() >= n_classes or G.min() < 0 or G.max() >= n_classes):
+        raise ValueError(f'class index outside [0, {n_classes})')
+    return np.bincount(G * n_classes + P, minlength=n_classes * n_classes).reshape(n_classes, n_classes)
+
+
+def accuracy_from_confusion(conf):
+    """conf (B,C,C) or (C,C): trace / pixels, the mean over the images."""
+    conf = np.asarray(conf, dtype=np.float64).reshape((-1,) + np.shape(conf)[-2:])
+    return float(np.mean(np.trace(conf, axis1=1, axis2=2) / conf.sum(axis=(1, 2))))
+
+
+def dice_from_confusion(conf, epsilon=1e-7):
+    """conf (B,C,C) or (C,C): per image the mean, over the classes present in the prediction or the ground truth, of
+    2 n_cc / (row_c + col_c + epsilon); the mean over the images."""
+    conf = np.asarray(conf, dtype=np.float64).reshape((-1,) + np.shape(conf)[-2:])
+    out = []
+    for t in conf:
+        row, col, diag = t.sum(1), t.sum(0), np.diag(t)
+        present = (row + col) > 0
+        out.append(np.mean(2 * diag[present] / (row[present] + col[present] + epsilon)) if present.any() else 0.0)
+    return float(np.mean(out))
+
+
+def accuracy_multiclass(P, G, n_classes):
+    return accuracy_from_confusion(confusion(P, G, n_classes))
+
+
+def dice_multiclass(P, G, n_classes, epsilon=1e-7):
+    return dice_from_confusion(confusion(P, G, n_classes), epsilon)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # GlaS challenge metrics (utils/metrics.py:48-281; SURVEY.md 8(f) row 4).  Evaluation-time, CPU, numpy -- as in the
 # reference.  Restated around ONE contingency table of the two labelled maps (pixels per (segmented object, ground
