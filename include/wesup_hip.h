@@ -31,6 +31,11 @@ extern "C" {
 
 /* classes of the C-way head (the *_c entries, wesup_paint_argmax, wesup_seg_confusion): 2 <= C <= WESUP_MAX_CLASSES */
 #define WESUP_MAX_CLASSES 16
+/* feature width of the head (wesup_propagate, wesup_head_fwd, wesup_head_fwd_c): 1 <= D <= WESUP_HEAD_MAX_D.  The propagation
+ * kernel keeps 256 labelled rows of D + 1 floats and 16 rows of D floats in LDS, 1088 D + 1024 bytes: 163 136 B of the CU's
+ * 160 KiB (163 840 B) at D = 149, 164 224 B at D = 150.  From D = 60 (more than 64 KiB) the entries raise the kernel's dynamic
+ * LDS limit once; a wider D is WESUP_ERR_INVALID and nothing is launched. */
+#define WESUP_HEAD_MAX_D 149
 
 /* flags for wesup_gemm_nt */
 #define WESUP_RELU_IN 1    /* A := max(A, 0) while loading */
@@ -395,7 +400,7 @@ int wesup_classifier_bwd(const float* feat, const float* Wc, const float* pred, 
                          void* ws, size_t ws_bytes, void* stream);
 /* _label_propagate (models/wesup.py:99-139) per image on padded rows.  y_all[b][r][:] = sp_labels for
  * r < n_l, propagated pseudo label for n_l <= r < n_sp (zeros if max similarity <= threshold), 0 beyond.
- * src_idx/max_sim [B][Kmax] (entries for unlabelled rows; -1/0 elsewhere). */
+ * src_idx/max_sim [B][Kmax] (entries for unlabelled rows; -1/0 elsewhere).  D <= WESUP_HEAD_MAX_D (above). */
 int wesup_propagate(const float* feat, const float* sp_labels, const int32_t* n_sp, const int32_t* n_l,
                     float threshold, int enable, float* y_all, int32_t* src_idx, float* max_sim,
                     int B, int Kmax, int D, int C, void* stream);
@@ -466,7 +471,9 @@ int wesup_cross_entropy_bwd(const float* y_hat, const float* y_true, const float
 int wesup_sgd_step(float* p, const float* g, float* v, size_t n, float lr, float momentum, float weight_decay,
                    float grad_scale, int first_step, void* stream);
 /* accuracy / dice inputs (utils/metrics.py:31-45,112-135): out[b] = {#(P==G), sum(P*G), sum(P), sum(G)} with
- * P = round(pred) (half to even, models/wesup.py:534), G = argmax_c mask (first max) */
+ * P = round(pred) (half to even, models/wesup.py:534), G = argmax_c mask (first max).  The sums are formed in float: they are
+ * the exact integers while every one of them stays below 2^24 = 16 777 216 (an image of up to 2^24 pixels with P, G in {0, 1};
+ * with class indices up to C - 1 the bound is on sum(P*G) <= (C - 1)^2 HW); beyond that they are rounded. */
 size_t wesup_seg_metrics_workspace_bytes(int B);
 int wesup_seg_metrics(const float* pred, const uint8_t* mask, float* out4, int B, int HW, int C,
                       void* ws, size_t ws_bytes, void* stream);

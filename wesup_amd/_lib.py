@@ -192,6 +192,7 @@ _T = {'p': c_void_p, 'i': c_int, 'f': c_float, 'z': c_size_t, 'l': ctypes.c_long
 
 EXPORTS = sorted(_SIGS)
 MAX_CLASSES = 16         # WESUP_MAX_CLASSES
+HEAD_MAX_D = 149         # WESUP_HEAD_MAX_D: the propagation kernel's LDS tile, 1088 D + 1024 bytes, within the CU's 160 KiB
 ABI_VERSION = 6          # include/wesup_hip.h; a stale libwesup_hip.so with other signatures must not be called
 
 _lib = None

@@ -321,6 +321,17 @@ extern "C" int wesup_classifier_bwd_c(const float* feat, const float* Wc, const 
 // torch.max(dim=1) does; propagate iff W > threshold (strict).
 #define PROP_TILE 256
 #define PROP_ROWS 16
+// Dynamic LDS of a block for a feature width D: the labelled tile [PROP_TILE][D+1] and the block's own rows [PROP_ROWS][D] --
+// 1088 D + 1024 bytes.  Up to D = 59 that fits the 64 KiB a kernel gets without asking; from D = 60 (66 304 B) the entry raises
+// the kernel's limit, once, to the CU's 160 KiB, which holds D <= WESUP_HEAD_MAX_D = 149 (163 136 B; D = 150 needs 164 224 B and
+// is refused before any launch).  From D = 60 on a CU holds one block at a time; nothing changes for the step's D = 32 (35 840 B).
+#define PROP_LDS_DEFAULT (64 * 1024)
+#define PROP_LDS_MAX (160 * 1024)
+static constexpr size_t prop_lds_bytes(int D) {
+    return ((size_t)PROP_TILE * ((size_t)D + 1) + (size_t)PROP_ROWS * (size_t)D) * sizeof(float);
+}
+static_assert(prop_lds_bytes(WESUP_HEAD_MAX_D) <= PROP_LDS_MAX && prop_lds_bytes(WESUP_HEAD_MAX_D + 1) > PROP_LDS_MAX,
+              "WESUP_HEAD_MAX_D (include/wesup_hip.h) is the largest D whose propagation tile fits the CU's LDS");
 // (the body of prop_kernel and of prop_c_kernel, its form for a classifier of more than two classes: GENERIC only chooses the
 // classifier tail, everything else is the same code)
 template <bool GENERIC>
@@ -451,14 +462,27 @@ __global__ __launch_bounds__(256) void prop_c_kernel(const float* __restrict__ f
     extern __shared__ float sh[];
     prop_body<true>(sh, feat, sp_labels, n_sp, n_l, thr, enable, y_all, src_idx, max_sim, Kmax, D, C, Wc, bc, pred);
 }
+// what the three entries below do about that size before they launch: WESUP_ERR_INVALID beyond the CU's LDS, the kernel's
+// dynamic-LDS limit raised (once per kernel) where the default does not hold it
+template <bool GENERIC>
+static int prop_lds_ready(size_t lds) {
+    if (lds > PROP_LDS_MAX) return WESUP_ERR_INVALID;
+    if (lds > PROP_LDS_DEFAULT) {
+        static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(GENERIC ? prop_c_kernel : prop_kernel),
+                                                           hipFuncAttributeMaxDynamicSharedMemorySize, PROP_LDS_MAX);
+        if (attr != hipSuccess) return WESUP_ERR_LAUNCH;
+    }
+    return WESUP_OK;
+}
 extern "C" int wesup_propagate(const float* feat, const float* sp_labels, const int32_t* n_sp, const int32_t* n_l,
                                float threshold, int enable, float* y_all, int32_t* src_idx, float* max_sim, int B,
                                int Kmax, int D, int C, void* stream) {
     if (!feat || !sp_labels || !n_sp || !n_l || !y_all || !src_idx || !max_sim || B <= 0 || Kmax <= 0 || D <= 0 ||
-        D > 256 || C <= 0)
+        D > WESUP_HEAD_MAX_D || C <= 0)
         return WESUP_ERR_INVALID;
     hipStream_t st = (hipStream_t)stream;
-    const size_t lds = ((size_t)PROP_TILE * (D + 1) + (size_t)PROP_ROWS * D) * sizeof(float);
+    const size_t lds = prop_lds_bytes(D);
+    if (const int rc = prop_lds_ready<false>(lds); rc != WESUP_OK) return rc;
     WESUP_LAUNCH(prop_kernel, dim3(ceil_div(Kmax, PROP_ROWS), B), dim3(256), lds, st, feat, sp_labels, n_sp, n_l, threshold,
                  enable, y_all, src_idx, max_sim, Kmax, D, C, (const float*)nullptr, (const float*)nullptr, (float*)nullptr);
     WESUP_CHECK_LAUNCH();
@@ -470,10 +494,11 @@ extern "C" int wesup_head_fwd(const float* feat, const float* Wc, const float* b
                               const int32_t* n_sp, const int32_t* n_l, float threshold, int enable, float* y_all,
                               int32_t* src_idx, float* max_sim, int B, int Kmax, int D, int C, void* stream) {
     if (!feat || !Wc || !bc || !pred || !sp_labels || !n_sp || !n_l || !y_all || !src_idx || !max_sim || B <= 0 || Kmax <= 0 ||
-        D <= 0 || D > 256 || C <= 0)
+        D <= 0 || D > WESUP_HEAD_MAX_D || C <= 0)
         return WESUP_ERR_INVALID;
     hipStream_t st = (hipStream_t)stream;
-    const size_t lds = ((size_t)PROP_TILE * (D + 1) + (size_t)PROP_ROWS * D) * sizeof(float);
+    const size_t lds = prop_lds_bytes(D);
+    if (const int rc = prop_lds_ready<false>(lds); rc != WESUP_OK) return rc;
     WESUP_LAUNCH(prop_kernel, dim3(ceil_div(Kmax, PROP_ROWS), B), dim3(256), lds, st, feat, sp_labels, n_sp, n_l, threshold,
                  enable, y_all, src_idx, max_sim, Kmax, D, C, Wc, bc, pred);
     WESUP_CHECK_LAUNCH();
@@ -694,10 +719,11 @@ extern "C" int wesup_head_fwd_c(const float* feat, const float* Wc, const float*
                                 const int32_t* n_sp, const int32_t* n_l, float threshold, int enable, float* y_all,
                                 int32_t* src_idx, float* max_sim, int B, int Kmax, int D, int C, void* stream) {
     if (!feat || !Wc || !bc || !pred || !sp_labels || !n_sp || !n_l || !y_all || !src_idx || !max_sim || B <= 0 || Kmax <= 0 ||
-        D <= 0 || D > 256 || !cls_c_range(C))
+        D <= 0 || D > WESUP_HEAD_MAX_D || !cls_c_range(C))
         return WESUP_ERR_INVALID;
     hipStream_t st = (hipStream_t)stream;
-    const size_t lds = ((size_t)PROP_TILE * (D + 1) + (size_t)PROP_ROWS * D) * sizeof(float);
+    const size_t lds = prop_lds_bytes(D);
+    if (const int rc = prop_lds_ready<true>(lds); rc != WESUP_OK) return rc;
     WESUP_LAUNCH(prop_c_kernel, dim3(ceil_div(Kmax, PROP_ROWS), B), dim3(256), lds, st, feat, sp_labels, n_sp, n_l, threshold,
                  enable, y_all, src_idx, max_sim, Kmax, D, C, Wc, bc, pred);
     WESUP_CHECK_LAUNCH();

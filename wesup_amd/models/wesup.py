@@ -333,6 +333,9 @@ class WESUP(nn.Module):
         if not 2 <= int(n_classes) <= 16:
             raise ValueError(f'n_classes must be in [2, 16] (WESUP_MAX_CLASSES), got {n_classes}')
         self.n_classes = int(n_classes)
+        # the label propagation keeps a tile of 256 rows of D + 1 floats in LDS: wider features than this the head cannot launch
+        if not 1 <= int(D) <= ops.HEAD_MAX_D:
+            raise ValueError(f'D must be in [1, {ops.HEAD_MAX_D}] (WESUP_HEAD_MAX_D), got {D}')
         self.classifier = nn.Sequential(nn.Linear(D, self.n_classes), nn.Softmax(dim=1))
         self.fm_size = None
         self.sp_features = None

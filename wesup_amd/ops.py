@@ -1110,6 +1110,7 @@ def slic(img, n_segments, compactness=40.0, max_iter=10, enforce_connectivity=Tr
 
 # ---------------------------------------------------------------- head / loss / optimiser
 MAX_CLASSES = _lib.MAX_CLASSES       # WESUP_MAX_CLASSES: the *_c entries take 2 <= C <= MAX_CLASSES
+HEAD_MAX_D = _lib.HEAD_MAX_D         # WESUP_HEAD_MAX_D: propagate / head_fwd take 1 <= D <= HEAD_MAX_D
 
 
 def classifier_fwd(feat, Wc, bc, out=None):
