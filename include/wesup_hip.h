@@ -470,6 +470,17 @@ int wesup_cross_entropy_bwd(const float* y_hat, const float* y_true, const float
 /* torch.optim.SGD step (models/wesup.py:445-451): g' = g*grad_scale + wd*p; v = first ? g' : mu*v + g'; p -= lr*v */
 int wesup_sgd_step(float* p, const float* g, float* v, size_t n, float lr, float momentum, float weight_decay,
                    float grad_scale, int first_step, void* stream);
+/* torch.optim.Adam / AdamW (no amsgrad) for a recorded step (csrc/optim.hip).  `state` is a 32-byte, 16-byte aligned device block
+ * the optimiser owns: { double lr; int32 t; float step_size, inv_sqrt_bc2, decay; 8 bytes unused }.  The host writes lr (and t,
+ * from a checkpoint); wesup_adam_tick -- one thread -- forms t += 1, step_size = lr / (1 - b1^t), inv_sqrt_bc2 = 1 / sqrt(1 - b2^t),
+ * decay = 1 - lr wd in double with b = 1 - (double) one_minus_b, and rounds each to float once.  wesup_adam_step reads the three
+ * factors from the block:  g' = g grad_scale;  decoupled ? p *= decay : g' += wd p;  m = b1 m + (1 - b1) g';
+ * v = b2 v + (1 - b2) g' g';  p -= step_size m / (sqrt(v) inv_sqrt_bc2 + eps).  one_minus_beta* are the floats of the host's
+ * doubles 1 - beta (1.f - 0.999f is wrong in the fifth digit).  Pointers 16-byte aligned, n > 0: else WESUP_ERR_INVALID. */
+int wesup_adam_tick(void* state, float one_minus_beta1, float one_minus_beta2, float weight_decay, void* stream);
+int wesup_adam_step(float* p, const float* g, float* m, float* v, size_t n, const void* state, float beta1,
+                    float one_minus_beta1, float beta2, float one_minus_beta2, float eps, float weight_decay,
+                    float grad_scale, int decoupled, void* stream);
 /* accuracy / dice inputs (utils/metrics.py:31-45,112-135): out[b] = {#(P==G), sum(P*G), sum(P), sum(G)} with
  * P = round(pred) (half to even, models/wesup.py:534), G = argmax_c mask (first max).  The sums are formed in float: they are
  * the exact integers while every one of them stays below 2^24 = 16 777 216 (an image of up to 2^24 pixels with P, G in {0, 1};

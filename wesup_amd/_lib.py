@@ -119,6 +119,9 @@ _SIGS = {
     'wesup_cross_entropy_fwd': (c_int, 'pppfpiip'),
     'wesup_cross_entropy_bwd': (c_int, 'pppppfpiip'),
     'wesup_sgd_step': (c_int, 'pppzffffip'),
+    # Adam / AdamW with the step count and lr in a device block (csrc/optim.hip)
+    'wesup_adam_tick': (c_int, 'pfffp'),
+    'wesup_adam_step': (c_int, 'ppppzp' + 'fffffff' + 'ip'),
     'wesup_seg_metrics_workspace_bytes': (c_size_t, 'i'),
     'wesup_seg_metrics': (c_int, 'pppiiipzp'),
     # mask post-processing and challenge scoring (csrc/regions.hip)

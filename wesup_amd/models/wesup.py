@@ -590,13 +590,35 @@ class WESUPTrainer(BaseTrainer):
                            rescale_factor=self.kwargs.get('rescale_factor'),
                            n_classes=int(self.kwargs.get('n_classes') or 2))
 
+    OPTIMIZERS = ('sgd', 'adam', 'adamw')
+    LR_SCHEDULERS = (None, 'plateau')
+
     def get_default_optimizer(self):
-        from ..optim import FusedSGD
+        """Trainer kwargs (defaults: what the reference trains with, models/wesup.py:445-455): ``optimizer`` 'sgd' | 'adam' |
+        'adamw', ``lr`` 5e-5, ``betas`` (0.9, 0.999), ``adam_eps`` 1e-8, ``lr_scheduler`` None | 'plateau' -- besides ``momentum``
+        (SGD only) and ``weight_decay`` of the config.  All three optimisers are fused over the flat parameter buffer
+        (optim.py) and stay on the recorded step."""
+        from .. import optim
+        kw = self.kwargs
+        name, sched = kw.get('optimizer', 'sgd'), kw.get('lr_scheduler')
+        if name not in self.OPTIMIZERS:
+            raise ValueError(f'optimizer must be one of {self.OPTIMIZERS}, got {name!r}')
+        if sched not in self.LR_SCHEDULERS:
+            raise ValueError(f'lr_scheduler must be one of {self.LR_SCHEDULERS}, got {sched!r}')
+        lr = float(kw.get('lr', 5e-5))
         self.model._ensure_engine()
-        optimizer = FusedSGD(self.model, lr=5e-5, momentum=self.kwargs.get('momentum'),
-                             weight_decay=self.kwargs.get('weight_decay'))
-        # the reference builds a ReduceLROnPlateau scheduler and discards it (models/wesup.py:452-455)
-        return optimizer, None
+        if name == 'sgd':
+            optimizer = optim.FusedSGD(self.model, lr=lr, momentum=kw.get('momentum'), weight_decay=kw.get('weight_decay'))
+        else:
+            cls = optim.FusedAdam if name == 'adam' else optim.FusedAdamW
+            optimizer = cls(self.model, lr=lr, betas=tuple(float(b) for b in kw.get('betas', (0.9, 0.999))),
+                            eps=float(kw.get('adam_eps', 1e-8)), weight_decay=kw.get('weight_decay'))
+        # the reference builds this ReduceLROnPlateau scheduler and discards it (models/wesup.py:452-455); post_epoch_hook steps
+        # whatever is here with the epoch's labelled loss
+        scheduler = None
+        if sched == 'plateau':
+            scheduler = torch.optim.lr_scheduler.ReduceLROnPlateau(optimizer, 'min', patience=10, factor=0.5, min_lr=1e-5)
+        return optimizer, scheduler
 
     def slic(self, img):
         """Superpixel segmentation of a batch (B,3,H,W) -> (labels (B,H,W) int32 on the device, upper bound on ids).

@@ -6,6 +6,7 @@ the entry on torch's current stream.  torch is only used for device memory and
 streams here.  No CPU fallback: a CPU tensor raises.
 """
 import ctypes
+import struct
 
 import torch
 
@@ -1305,6 +1306,50 @@ def sgd_step(p, g, v, lr, momentum, weight_decay, grad_scale, first_step):
     _lib.call('wesup_sgd_step', _p(p), _p(g), _p(v), p.numel(), float(lr), float(momentum), float(weight_decay),
               float(grad_scale), int(first_step), _stream())
     _tend(tok, 20.0 * p.numel())                     # read p, g, v; write p, v
+
+
+ADAM_STATE_BYTES = 32        # AdamState of csrc/optim.hip: { double lr; int32 t; float step_size, inv_sqrt_bc2, decay; 8 unused }
+
+
+def adam_state(lr, device, t=0):
+    """A schedule block for adam_tick / adam_step on ``device``: lr as the double it is, the count t, the factors unset (the first
+    tick forms them)."""
+    raw = struct.pack('<di', float(lr), int(t)) + bytes(ADAM_STATE_BYTES - 12)
+    return torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(device, copy=True)
+
+
+def adam_state_read(state):
+    """The block's fields on the host (waits for the device)."""
+    lr, t, step_size, inv_sqrt_bc2, decay = struct.unpack('<di3f', state.cpu().numpy().tobytes()[:24])
+    return {'lr': lr, 't': t, 'step_size': step_size, 'inv_sqrt_bc2': inv_sqrt_bc2, 'decay': decay}
+
+
+def _chk_adam_state(state):
+    _chk(state, torch.uint8, 'state')
+    if state.numel() != ADAM_STATE_BYTES:
+        raise _lib.WesupHipError(f'state: expected {ADAM_STATE_BYTES} bytes, got {state.numel()}')
+
+
+def adam_tick(state, betas, weight_decay):
+    """t += 1 in the optimiser's device block and the three factors of that step from t and the block's lr.  ``betas`` are the
+    host's doubles: their complements are formed here, in double, and rounded to float once."""
+    _chk_adam_state(state)
+    tok = _tbegin('sgd')
+    _lib.call('wesup_adam_tick', _p(state), 1.0 - float(betas[0]), 1.0 - float(betas[1]), float(weight_decay), _stream())
+    _tend(tok, 2.0 * ADAM_STATE_BYTES)
+
+
+def adam_step(p, g, m, v, state, betas, eps, weight_decay, grad_scale, decoupled):
+    """One Adam (decoupled: AdamW) update of p, m, v from g with the factors the last adam_tick left in ``state``."""
+    for t, n in ((p, 'p'), (g, 'g'), (m, 'm'), (v, 'v')):
+        _chk(t, name=n)
+    _chk_adam_state(state)
+    assert p.numel() == g.numel() == m.numel() == v.numel()
+    b1, b2 = float(betas[0]), float(betas[1])
+    tok = _tbegin('sgd')
+    _lib.call('wesup_adam_step', _p(p), _p(g), _p(m), _p(v), p.numel(), _p(state), b1, 1.0 - b1, b2, 1.0 - b2, float(eps),
+              float(weight_decay), float(grad_scale), int(bool(decoupled)), _stream())
+    _tend(tok, 28.0 * p.numel())                     # read p, g, m, v; write p, m, v
 
 
 def seg_metrics(pred, mask, out=None):

@@ -3,7 +3,7 @@
 ``BaseTrainer.train_one_iteration`` (models/base.py:184-211 of the reference: preprocess -> zero_grad -> forward -> loss ->
 NaN check -> backward -> step -> evaluate -> tracker) keeps its interface; for the case every benchmark configuration and
 the GlaS / CRAG training loops are in -- train phase, label maps given with the batch (tensor or ``LabelMaps``), point /
-pixel masks as (B,C,H,W) tensors, accuracy / dice as metrics, the fused SGD -- it hands the iteration to this runner:
+pixel masks as (B,C,H,W) tensors, accuracy / dice as metrics, a fused optimiser (optim.py) -- it hands the iteration to this runner:
 
 * every buffer the iteration touches lives in a per-shape state (inputs are COPIED into it), nothing is allocated per step and
   nothing goes through autograd: the loss gradient is ``wesup_loss_bwd`` with an upstream gradient of one, the engine's
@@ -18,7 +18,7 @@ pixel masks as (B,C,H,W) tensors, accuracy / dice as metrics, the fused SGD -- i
   (engine._fit); a first walk in which a workspace grows is discarded, and the twin confirms the rest or replaces the candidate)
   (``wesup_plan_replay``): ~330 launches without Python or ctypes in between.  Host work inside the iteration (the NaN check, a
   gradient bucket handed to RCCL) splits the replay into segments.  Anything that moves a buffer (a workspace that grew, the
-  engine's buffer cache evicting the shape) or changes the walk (an engine switch, the learning rate, frozen parameters)
+  engine's buffer cache evicting the shape) or changes the walk (an engine switch, the learning rate of the SGD launch, frozen parameters)
   drops the plan; the Python walk is always there and computes the same thing.
 
 Results are bit-identical to the trainer's general path (tests/test_runner_gpu.py): the same kernels on the same operands in
@@ -153,8 +153,11 @@ class StepRunner:
         t = self.t
         if phase != 'train' or len(data) != 4 or t.kwargs.get('check_label_maps', False):
             return None
-        from .optim import FusedSGD
-        if not isinstance(t.optimizer, FusedSGD) or type(t.model).__name__ != 'WESUP':
+        # (any optimiser that steps the flat buffers in two parts and says what a recorded plan of its step depends on:
+        # optim.FusedSGD / FusedAdam / FusedAdamW)
+        if not all(callable(getattr(t.optimizer, a, None)) for a in ('step_early', 'step_late', 'plan_fields')):
+            return None
+        if type(t.model).__name__ != 'WESUP':
             return None
         names = [f.__name__ for f in (t.metric_funcs or [])]
         if not all(n in ('accuracy', 'dice') for n in names):
@@ -180,7 +183,6 @@ class StepRunner:
         the settings that shape the launch list AND the identity of every long-lived allocation whose address the launches carry
         (a plan holds raw device addresses: replaying it over a freed or re-made buffer corrupts silently)."""
         t, o = self.t, self.t.optimizer
-        g = o.param_groups[0]
         # what shapes the engine's walk: its plan key (switches, routing result of this shape, the process-wide rule behind the
         # one-kernel route, frozen parameters, diagnostics), and the rest of its public state a walk reads
         walk = (eng.plan_key(B, H, W), eng.D, eng.ctx is None, eng.on_grads_ready is None, eng.on_tail is None)
@@ -190,16 +192,19 @@ class StepRunner:
         panels = None if pk is None else tuple(0 if u is None else u.data_ptr() for u in list(pk.uf) + list(pk.ud))
         return (walk, eng.route_fn, type(eng).WINOGRAD_CONV_MIN_CI, type(eng).WINOGRAD_TILE,
                 ops.STREAMK, tuple(sorted(ops.DIAG)),
-                g['lr'], g['momentum'], g['weight_decay'], o.grad_scale, o._first,
+                # the optimiser's own fields: the scalars its launches carry and the addresses of its state (FusedSGD: lr, momentum,
+                # weight decay, grad_scale, the first-step flag, the momentum buffer; the Adam family: betas, eps, weight decay,
+                # grad_scale, decoupled, both moment buffers and the device block that holds lr and the count -- NOT lr itself)
+                o.plan_fields(),
                 tuple(p.requires_grad for _, p in t.model._named),
                 float(t.kwargs.get('propagate_threshold')), float(t.kwargs.get('propagate_weight')),
                 bool(t.kwargs.get('enable_propagation')), float(t.kwargs.get('epsilon')), self.fuse_head, self.split_sgd,
                 None if red is None else (id(red), t.world_size, red.bucket_elems, red.force),
                 ops._stream().value,
-                # the engine object itself (model.to(device) re-makes it and restarts buf_generation), the flat parameter / gradient /
-                # momentum buffers, the Winograd filter panels
+                # the engine object itself (model.to(device) re-makes it and restarts buf_generation), the flat parameter / gradient
+                # buffers, the Winograd filter panels
                 id(eng),
-                m._flat.data_ptr(), m._flat_grad.data_ptr(), o._vflat.data_ptr(), panels)
+                m._flat.data_ptr(), m._flat_grad.data_ptr(), panels)
 
     # ------------------------------------------------------------------ the iteration
     def run(self, parsed):
@@ -239,6 +244,10 @@ class StepRunner:
                 st.gt.copy_(pixel_mask, non_blocking=True)
         st.n_sp_host = counts
 
+        # a learning rate the Adam family keeps on the device: what changed since the last step goes there now, in front of
+        # everything this iteration queues -- walked, replayed or audited, the step's tick reads it
+        if hasattr(t.optimizer, 'push_hyper'):
+            t.optimizer.push_hyper()
         timing = eng.timer.enabled or (t.reducer is not None and t.reducer.profile)
         sig = self._signature(eng, B, H, W) if self.replay else None
         gens = (ops.ws_generation, eng.bufs_gen(B, H, W, st.y_all.shape[1]))
@@ -262,7 +271,7 @@ class StepRunner:
                           [i for i, (x, y) in enumerate(zip(st.sig, sig)) if x != y])
                 st.cand = None
             # (the very first optimiser step of a run differs from every later one -- buf = g --: not worth recording)
-            record = self.replay and not timing and st.count >= RECORD_AT and st.tries < MAX_RECORD_TRIES and not t.optimizer._first
+            record = self.replay and not timing and st.count >= RECORD_AT and st.tries < MAX_RECORD_TRIES and not getattr(t.optimizer, '_first', False)
             plan = _Plan() if record else None
             ws_gen0 = ops.ws_generation
             host = self._walk(st, metrics, want_seg, plan)

@@ -1,6 +1,8 @@
 """Training module (mirror of the reference's train.py:14-32; `fire` is replaced by argparse).
 
   python -m wesup_amd.train synthetic:480:480:24:16 --epochs 1 --batch_size 4 [--smoke] [--challenge-metrics]
+  python -m wesup_amd.train DATA --optimizer adam --lr 1e-4 --lr_scheduler plateau     (sgd | adam | adamw, also --betas (0.9,0.999)
+                                                                                        --adam_eps 1e-8; defaults: sgd, 5e-5, no scheduler)
 """
 import argparse
 import logging
