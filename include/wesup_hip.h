@@ -637,6 +637,31 @@ size_t wesup_spl_paint_workspace_bytes(int K, int C);
 int wesup_spl_paint(const int32_t* labels, const int32_t* points, uint8_t* out, int32_t* status, int H, int W, int K, int C, int P,
                     void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------ exact t-SNE of superpixel features (csrc/tsne.hip)
+ * The embedding the reference's plot_tsne.py asks sklearn.manifold.TSNE() for, method 'exact', two output dimensions.  All
+ * matrices are dense row-major fp32: x [n][d], d2 and p [n][n], y / upd / gains [n][2] (8-byte aligned).  2 <= n <=
+ * WESUP_TSNE_MAX_N (p is 4 GiB there), 1 <= d <= WESUP_TSNE_MAX_D, 0 < perplexity < n; outside that, or with a null pointer,
+ * every entry returns WESUP_ERR_INVALID without a launch.  No floating-point atomics: the same input gives the same bits. */
+#define WESUP_TSNE_MAX_N 32768
+#define WESUP_TSNE_MAX_D 4096
+#define WESUP_TSNE_STATS 4
+/* d2[i][j] = sum_k (x[i][k] - x[j][k])^2, from differences in ascending k: bit-symmetric, the diagonal exactly 0 */
+int wesup_tsne_sqdist(const float* x, int n, int d, float* d2, void* stream);
+/* scikit-learn's search for beta[i] (start 1, double / halve while a bound is infinite, else bisect; at most 100 steps; stop at
+ * |H_i - log perplexity| <= 1e-5) on d2[i][:] minus the row's smallest off-diagonal entry, then p = max((C + C^T) / max(sum, eps),
+ * eps) with C the conditional rows, eps = 2.220446049250313e-16 and p[i][i] = 0; p is bit-symmetric.  beta [n]: the value each
+ * row's C was built with.  d2 and p must not overlap. */
+size_t wesup_tsne_affinities_workspace_bytes(int n);
+int wesup_tsne_affinities(const float* d2, int n, float perplexity, float* p, float* beta, void* ws, size_t ws_bytes, void* stream);
+/* Enqueues `iters` gradient iterations (0 <= iters <= 65536) on y with scikit-learn's delta-bar-delta rule: g = 4 (att - rep / Z)
+ * with p scaled by `exaggeration` (> 0), gains += 0.2 where upd g < 0 else *= 0.8, floored at min_gain (>= 0), upd = momentum upd -
+ * lr g gains (momentum >= 0, lr > 0), y += upd.  The last iteration also writes stats [WESUP_TSNE_STATS] = {KL divergence of the
+ * UNexaggerated p, |g|_2 of the exaggerated gradient, Z, sum p log p}, all at the y that iteration started from.  iters = 0 moves
+ * nothing and writes the stats of y as it stands. */
+size_t wesup_tsne_iterate_workspace_bytes(int n);
+int wesup_tsne_iterate(const float* p, float* y, float* upd, float* gains, float* stats, int n, int iters, float exaggeration,
+                       float momentum, float lr, float min_gain, void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------ entries by the names of SURVEY.md 8(b)
  * One call per ATen op of the reference for a binding that replaces them one by one; each is a thin entry over the
  * kernels above (csrc/named.hip).  Matrices are row-major with the channel / feature index contiguous (NHWC pixels). */

@@ -139,6 +139,12 @@ _SIGS = {
     'wesup_object_match_workspace_bytes': (c_size_t, 'ii'),
     'wesup_object_match': (c_int, 'pppp' + 'iii' + 'pzp'),
     'wesup_label_paint': (c_int, 'pppp' + 'iii' + 'p'),
+    # exact t-SNE of superpixel features (csrc/tsne.hip)
+    'wesup_tsne_sqdist': (c_int, 'pii' + 'pp'),
+    'wesup_tsne_affinities_workspace_bytes': (c_size_t, 'i'),
+    'wesup_tsne_affinities': (c_int, 'pif' + 'pp' + 'pzp'),
+    'wesup_tsne_iterate_workspace_bytes': (c_size_t, 'i'),
+    'wesup_tsne_iterate': (c_int, 'ppppp' + 'ii' + 'ffff' + 'pzp'),
     # window inference on large images (csrc/tiles.hip)
     'wesup_window_gather': (c_int, 'pppp' + 'iiiiiii' + 'p'),
     'wesup_window_merge': (c_int, 'pppp' + 'iiiiiii' + 'p'),
@@ -196,6 +202,9 @@ _T = {'p': c_void_p, 'i': c_int, 'f': c_float, 'z': c_size_t, 'l': ctypes.c_long
 EXPORTS = sorted(_SIGS)
 MAX_CLASSES = 16         # WESUP_MAX_CLASSES
 HEAD_MAX_D = 149         # WESUP_HEAD_MAX_D: the propagation kernel's LDS tile, 1088 D + 1024 bytes, within the CU's 160 KiB
+TSNE_MAX_N = 32768       # WESUP_TSNE_MAX_N: the joint probabilities are dense fp32, 4 GiB there
+TSNE_MAX_D = 4096        # WESUP_TSNE_MAX_D
+TSNE_STATS = 4           # WESUP_TSNE_STATS: KL, |g|, Z, sum p log p
 ABI_VERSION = 6          # include/wesup_hip.h; a stale libwesup_hip.so with other signatures must not be called
 
 _lib = None

@@ -1563,6 +1563,78 @@ def label_paint(labels, lut):
     return (out[0] if single else out), status
 
 
+# ---------------------------------------------------------------- exact t-SNE of superpixel features (csrc/tsne.hip)
+TSNE_MAX_N = _lib.TSNE_MAX_N
+TSNE_MAX_D = _lib.TSNE_MAX_D
+TSNE_STATS = _lib.TSNE_STATS
+
+
+def tsne_check_shape(n, d=1, perplexity=None):
+    """The limits of the t-SNE entries, as ValueErrors before any tensor is looked at."""
+    if not 2 <= int(n) <= TSNE_MAX_N:
+        raise ValueError(f't-SNE: {n} rows, expected 2 .. {TSNE_MAX_N} (the joint probabilities are a dense fp32 matrix)')
+    if not 1 <= int(d) <= TSNE_MAX_D:
+        raise ValueError(f't-SNE: {d} features, expected 1 .. {TSNE_MAX_D}')
+    if perplexity is not None and not 0 < float(perplexity) < int(n):
+        raise ValueError(f't-SNE: perplexity {perplexity} for {n} rows, expected 0 < perplexity < rows')
+
+
+def tsne_sqdist(x, out=None):
+    """x (N, D) -> (N, N) squared Euclidean distances from differences: bit-symmetric, the diagonal exactly 0."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 2:
+        raise ValueError('tsne_sqdist: expected an (N, D) tensor')
+    n, d = x.shape
+    tsne_check_shape(n, d)
+    _chk(x, name='x')
+    if out is None:
+        out = torch.empty(n, n, dtype=torch.float32, device=x.device)
+    _chk(out, name='out')
+    if tuple(out.shape) != (n, n) or out.device != x.device:
+        raise _lib.WesupHipError(f'tsne_sqdist: out {tuple(out.shape)} for {n} rows')
+    _lib.call('wesup_tsne_sqdist', _p(x), n, d, _p(out), _stream())
+    return out
+
+
+def tsne_affinities(d2, perplexity, p=None, beta=None):
+    """d2 (N, N) squared distances -> (P (N, N) joint probabilities, beta (N,)): scikit-learn's per-row perplexity search on the
+    row minus its smallest off-diagonal entry, then max((C + C^T) / sum, eps) with the diagonal 0."""
+    if not isinstance(d2, torch.Tensor) or d2.dim() != 2 or d2.shape[0] != d2.shape[1]:
+        raise ValueError('tsne_affinities: expected an (N, N) tensor')
+    n = d2.shape[0]
+    tsne_check_shape(n, 1, perplexity)
+    _chk(d2, name='d2')
+    dev = d2.device
+    p = torch.empty(n, n, dtype=torch.float32, device=dev) if p is None else _chk(p, name='p')
+    beta = torch.empty(n, dtype=torch.float32, device=dev) if beta is None else _chk(beta, name='beta')
+    if tuple(p.shape) != (n, n) or tuple(beta.shape) != (n,) or p.device != dev or beta.device != dev or p.data_ptr() == d2.data_ptr():
+        raise _lib.WesupHipError(f'tsne_affinities: p {tuple(p.shape)}, beta {tuple(beta.shape)} for {n} rows (p apart from d2)')
+    nb = _lib.load().wesup_tsne_affinities_workspace_bytes(n)
+    ws = workspace(nb, dev, 'tsne')
+    _lib.call('wesup_tsne_affinities', _p(d2), n, float(perplexity), _p(p), _p(beta), _p(ws), nb, _stream())
+    return p, beta
+
+
+def tsne_iterate(p, y, upd, gains, stats, iters, exaggeration=1.0, momentum=0.8, lr=200.0, min_gain=0.01):
+    """Enqueues ``iters`` gradient iterations on y (N, 2) in place (upd, gains (N, 2) with it); the last one writes stats
+    (TSNE_STATS,) = KL of the unexaggerated p, |g|, Z, sum p log p at the y it started from.  ``iters`` 0 only writes the stats.
+    Nothing is synchronised."""
+    if not isinstance(p, torch.Tensor) or p.dim() != 2 or p.shape[0] != p.shape[1]:
+        raise ValueError('tsne_iterate: expected an (N, N) tensor p')
+    n = p.shape[0]
+    tsne_check_shape(n)
+    for t, name in ((p, 'p'), (y, 'y'), (upd, 'upd'), (gains, 'gains'), (stats, 'stats')):
+        _chk(t, name=name)
+        if t.device != p.device:
+            raise _lib.WesupHipError('tsne_iterate: tensors on different devices')
+    if any(tuple(t.shape) != (n, 2) for t in (y, upd, gains)) or stats.numel() < TSNE_STATS:
+        raise _lib.WesupHipError(f'tsne_iterate: y, upd, gains must be ({n}, 2) and stats hold {TSNE_STATS} floats')
+    nb = _lib.load().wesup_tsne_iterate_workspace_bytes(n)
+    ws = workspace(nb, p.device, 'tsne')
+    _lib.call('wesup_tsne_iterate', _p(p), _p(y), _p(upd), _p(gains), _p(stats), n, int(iters), float(exaggeration),
+              float(momentum), float(lr), float(min_gain), _p(ws), nb, _stream())
+    return y
+
+
 # ---------------------------------------------------------------- window inference on large images (csrc/tiles.hip)
 _lattice_cache = {}    # (device, axis positions) -> int32 device tensor: an image size meets the same few lattices again and again
 
