@@ -610,6 +610,38 @@ int wesup_patch_scatter_u8(const float* pred, uint8_t* out, int H, int W, int p,
  * exact in any order; accuracy = eq / n and dice = 2 * inter / (sumG + sumS + 1e-7) are the host's, in float64. */
 int wesup_mask_scores(const uint8_t* S, const uint8_t* G, int64_t* out4, long n, int negative, void* stream);
 
+/* ------------------------------------------------------------------ class maps for more than two classes (csrc/classmap.hip)
+ * The merge, the resize back, the paste and the scoring of the three sections above as reductions over the C values of a pixel
+ * (DESIGN.md 3.15).  A pixel's class is the first maximum over ascending c under a strict > (no comparison with a NaN is true: a
+ * NaN behind the first entry is never the maximum, a row whose first entry is NaN gives class 0); class
+ * maps are uint8 class indices.  All entries: WESUP_ERR_INVALID without a launch for C outside [2, WESUP_MAX_CLASSES], a null
+ * pointer or a size the one-plane entry refuses; no workspace, no host sync.  A class index that comes in as data (a vote, a
+ * painted map, a label byte) is never used as an address: one outside [0, C) -- a NaN included -- is not counted and sets
+ * *status (int32, device memory) to non-zero.
+ *
+ * wesup_window_merge_classes: the lattice of wesup_window_merge.  votes = 0: pred fp32 [n_h * n_w][p][p][C] probabilities; per
+ * pixel and class wesup_window_merge's fp64 mean over the covering windows, then the first maximum -- the argmax of
+ * infer_tile.combine_patches_to_image.  votes = 1: pred fp32 [n_h * n_w][p][p] class indices (rintf of them); every covering
+ * window votes, the first maximum of the integer counts.  out uint8 [H][W]; *status is zeroed here. */
+int wesup_window_merge_classes(const float* pred, const int32_t* tops, const int32_t* lefts, uint8_t* out, int32_t* status, int H,
+                               int W, int C, int n_h, int n_w, int p, int votes, void* stream);
+/* in fp32 [h][w][C] -> out fp32 [H][W][C] = (accumulate ? out : 0) + alpha * bilinear_ac(in): every plane c is
+ * wesup_plane_resize_acc of in[..., c] (stride C) bit for bit; the four corner vectors are read once per pixel */
+int wesup_planes_resize_acc(const float* in, float* out, int h, int w, int H, int W, int C, float alpha, int accumulate,
+                            void* stream);
+/* in fp32 [n][C] -> out uint8 [n]: the first maximum of every row */
+int wesup_class_argmax_u8(const float* in, uint8_t* out, long n, int C, void* stream);
+/* wesup_patch_scatter_u8 with a class index as the pasted byte: the same lattice, crop and "nothing else of out is touched".
+ * mode 0: pred fp32 [count][h][w] class indices (rintf of them), the nearest texel; an index outside [0, C) pastes 0 and sets
+ * *status.  mode 1: pred fp32 [count][h][w][C] probabilities, per class the value of wesup_planes_resize_acc at alpha = 1, then
+ * the first maximum.  *status is OR-ed into, not zeroed: it collects over the passes of a slide (the caller zeroes it once). */
+int wesup_patch_scatter_classes_u8(const float* pred, uint8_t* out, int32_t* status, int H, int W, int p, int h, int w, int C,
+                                   int mode, int first, int count, void* stream);
+/* S, G uint8 [n] class-index maps (n <= 2^40) -> conf int64 [C][C] (8-byte aligned), conf[g][s] = positions with ground truth g
+ * predicted as s: utils.metrics.confusion.  Integer counts in LDS, integer adds of the non-zero cells: exact in any order.  conf
+ * and *status are zeroed here. */
+int wesup_label_confusion(const uint8_t* S, const uint8_t* G, int64_t* conf, int32_t* status, long n, int C, void* stream);
+
 /* ------------------------------------------------------------------ weak-label preparation (csrc/prepare.hip)
  * The integer label-map passes of wesup_amd/prepare.py (scripts/generate_points.py, generate_spl_masks.py and
  * search_slic_params.py of the reference).  Label maps are int32, images at most 2^22 on a side.  All entries: WESUP_ERR_INVALID

@@ -156,6 +156,12 @@ _SIGS = {
     'wesup_patch_gather_resize': (c_int, 'pp' + 'iiiiiiii' + 'p'),
     'wesup_patch_scatter_u8': (c_int, 'pp' + 'iiiiiiiii' + 'p'),
     'wesup_mask_scores': (c_int, 'ppp' + 'li' + 'p'),
+    # class maps for more than two classes (csrc/classmap.hip)
+    'wesup_window_merge_classes': (c_int, 'ppppp' + 'iiiiiii' + 'p'),
+    'wesup_planes_resize_acc': (c_int, 'pp' + 'iiiii' + 'fi' + 'p'),
+    'wesup_class_argmax_u8': (c_int, 'pp' + 'li' + 'p'),
+    'wesup_patch_scatter_classes_u8': (c_int, 'ppp' + 'iiiiiiiii' + 'p'),
+    'wesup_label_confusion': (c_int, 'pppp' + 'li' + 'p'),
     # weak-label preparation (csrc/prepare.hip)
     'wesup_prepare_lds_entries': (c_int, 'i'),
     'wesup_label_stats': (c_int, 'ppp' + 'iiii' + 'p'),

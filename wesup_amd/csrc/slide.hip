@@ -7,6 +7,7 @@
 // Every offset that involves H * W is a long: a slide may be larger than 2^31 bytes.
 #include "common.hpp"
 #include "bilinear.hpp"
+#include "lattice.hpp"
 
 #define SD_BLOCK 256
 #define SD_MAX_BLOCKS 4096     // grid-stride above this (cdna_hip_programming.md, guideline 11)
@@ -143,17 +144,6 @@ __global__ __launch_bounds__(SD_BLOCK) void sd_scores_kernel(const uint8_t* __re
         for (int wv = 0; wv < SD_BLOCK / 64; ++wv) t += part[wv][threadIdx.x];
         if (t) atomicAdd(&out4[threadIdx.x], t);
     }
-}
-
-// the lattice of an (H, W) slide under patch size p; false when a size is outside what the kernels index (see the header)
-inline bool sd_lattice(int H, int W, int p, int* n_w, int* last) {
-    const int LIM = 1 << 30;
-    if (H <= 0 || W <= 0 || p <= 0 || H > LIM || W > LIM || p > LIM) return false;
-    const long nh = ((long)H + p - 1) / p, nw = ((long)W + p - 1) / p;
-    if (nh * nw > 0x7fffffffl) return false;
-    *n_w = (int)nw;
-    *last = (int)(nh * nw - 1);
-    return true;
 }
 
 }  // namespace

@@ -10,7 +10,13 @@ is the HIP path (``trainer.preprocess`` with the GPU SLIC -> ``WESUP.forward`` -
 
 ``predict_array_batched`` / ``pixel_predict_array_batched`` (``--batch N``) are the same inference with the image resident on
 the device: windows cut by ``ops.window_gather``, ``batch`` of them per pass through the network, one ``ops.window_merge``
-(equal to ``combine_patches_to_image`` bit for bit) and one copy to the host per image."""
+(equal to ``combine_patches_to_image`` bit for bit) and one copy to the host per image.
+
+A model of more than two classes gives a class map, (H, W) uint8 class indices: ``predict_array_classes`` /
+``pixel_predict_array_classes`` and their ``_batched`` forms, which ``infer`` / ``pixel_infer`` take for ``n_classes > 2``.  The
+pixel-wise paths merge the C probabilities as class 1 is merged above and take the first maximum (a soft vote); on the superpixel
+paths every covering window votes with the class index it painted and the first maximum of the counts wins (a hard vote);
+``combine_patches_to_classes`` states both."""
 import argparse
 import math
 from pathlib import Path
@@ -69,6 +75,26 @@ def combine_patches_to_image(patches, target_height, target_width):
     return merged[..., 0] if flat else np.squeeze(merged)
 
 
+def combine_patches_to_classes(patches, target_height, target_width, n_classes, votes=False):
+    """The class map of merged window predictions -> (H, W) uint8.  ``votes=False``: patches (N, p, p, C) probabilities; the
+    argmax of ``combine_patches_to_image`` (np.argmax: the first maximum).  ``votes=True``: patches (N, p, p) class indices; every
+    covering window votes -- the argmax of ``combine_patches_to_image`` over the one-hot votes, so a tie of the counts goes to the
+    lowest class.  A vote outside [0, n_classes) (or a NaN) counts for no class.  With two classes the hard vote is
+    ``round(combine_patches_to_image(round(p)))``: the mean of the rounded values is above 0.5 exactly when class 1 has more
+    votes, and np.round takes the tie at 0.5 to 0."""
+    C = int(n_classes)
+    patches = np.asarray(patches)
+    if votes:
+        if patches.ndim != 3:
+            raise ValueError(f'votes: expected (N, p, p) class indices, got {patches.shape}')
+        idx = np.rint(patches.astype(np.float64))
+        patches = (idx[..., None] == np.arange(C, dtype=np.float64)).astype(np.float64)      # (a NaN equals no class)
+    elif patches.ndim != 4 or patches.shape[-1] != C:
+        raise ValueError(f'expected (N, p, p, {C}) probabilities, got {patches.shape}')
+    merged = combine_patches_to_image(patches, target_height, target_width).reshape(target_height, target_width, C)
+    return merged.argmax(axis=-1).astype(np.uint8)
+
+
 def _to_tensor(patch, device):
     """uint8 (h, w, 3) -> float (1, 3, h, w) in [0, 1] (torchvision's to_tensor, infer_tile.py:111)."""
     return torch.from_numpy(np.ascontiguousarray(patch)).to(device).permute(2, 0, 1).float().div_(255.).unsqueeze(0)
@@ -98,6 +124,40 @@ def pixel_predict_array(model, img, patch_size, device='cuda'):
             predictions.append(np.expand_dims(pred.detach().cpu().numpy()[..., 1], 0))
     predictions = np.concatenate(predictions)
     return combine_patches_to_image(predictions, img.shape[0], img.shape[1])
+
+
+def _n_classes(model):
+    return int(getattr(model, 'n_classes', None) or 2)
+
+
+def _check_status(status, n_classes, what):
+    """Raise when a device path met a painted class index outside [0, n_classes) (the status word of the class-map entries, read
+    once, after the map has been copied back)."""
+    if int(status.cpu()) != 0:
+        raise RuntimeError(f'{what}: the model painted a class index outside [0, {n_classes})')
+
+
+def predict_array_classes(trainer, img, patch_size, device='cuda'):
+    """``predict_array`` for a model of more than two classes -> (H, W) uint8 class map: every window's painted class indices
+    (what ``trainer.model`` returns for C > 2) come to the host and vote (``combine_patches_to_classes(votes=True)``)."""
+    patches = divide_image_to_patches(img, patch_size)
+    predictions = []
+    with torch.no_grad():
+        for patch in patches:
+            input_, _ = trainer.preprocess(_to_tensor(patch, device))
+            predictions.append(trainer.model(input_).detach().cpu().numpy())              # (1, p, p) class indices
+    return combine_patches_to_classes(np.concatenate(predictions), img.shape[0], img.shape[1], _n_classes(trainer.model), votes=True)
+
+
+def pixel_predict_array_classes(model, img, patch_size, device='cuda'):
+    """``pixel_predict_array`` for a model of more than two classes -> (H, W) uint8 class map: all C probabilities of every
+    window are merged on the host, then the first maximum."""
+    patches = divide_image_to_patches(img, patch_size)
+    predictions = []
+    with torch.no_grad():
+        for patch in patches:
+            predictions.append(model(_to_tensor(patch, device)).detach().cpu().numpy()[np.newaxis])      # (1, p, p, C)
+    return combine_patches_to_classes(np.concatenate(predictions), img.shape[0], img.shape[1], _n_classes(model))
 
 
 def window_batches(n_windows, batch):
@@ -174,21 +234,74 @@ def pixel_predict_array_batched(model, img, patch_size, batch=2, device='cuda'):
     return merged.view(H, W).cpu().numpy()
 
 
+def predict_array_classes_batched(trainer, img, patch_size, batch=4, device='cuda'):
+    """``predict_array_classes`` with the image resident on the device (``predict_array_batched`` for C > 2): the painted class
+    indices of all windows kept in one (N, p, p) device buffer, one ``ops.window_merge_classes(votes=True)`` and ONE copy of the
+    (H, W) uint8 map to the host.  Equal to ``predict_array_classes`` bit for bit at ``batch=1``."""
+    p = int(patch_size)
+    H, W = img.shape[:2]
+    tops, lefts = window_grid(H, W, p)
+    passes, batch = window_batches(len(tops) * len(lefts), batch)
+    img_d = _upload(img, device)
+    kept = torch.empty(len(tops) * len(lefts), p, p, dtype=torch.float32, device=img_d.device)
+    x = torch.empty(batch, 3, p, p, dtype=torch.float32, device=img_d.device)
+    with torch.no_grad():
+        for first, valid in passes:
+            ops.window_gather(img_d, tops, lefts, p, first, batch, out=x)
+            input_, _ = trainer.preprocess(x)
+            _keep(kept, trainer.model(input_), first, valid)
+        merged, status = ops.window_merge_classes(kept, tops, lefts, H, W, n_classes=_n_classes(trainer.model), votes=True)
+    merged = merged.cpu().numpy()
+    _check_status(status, _n_classes(trainer.model), 'predict_array_classes_batched')      # (behind the copy: no wait of its own)
+    return merged
+
+
+def pixel_predict_array_classes_batched(model, img, patch_size, batch=2, device='cuda'):
+    """``pixel_predict_array_classes`` with the image resident on the device: the (p, p, C) probabilities of every window kept on
+    the device, one ``ops.window_merge_classes`` (the fp64 means per class live in registers: no (H, W, C) tensor) and one copy
+    of the (H, W) uint8 map to the host."""
+    p = int(patch_size)
+    H, W = img.shape[:2]
+    C = _n_classes(model)
+    tops, lefts = window_grid(H, W, p)
+    passes, batch = window_batches(len(tops) * len(lefts), batch)
+    img_d = _upload(img, device)
+    kept = torch.empty(len(tops) * len(lefts), p, p, C, dtype=torch.float32, device=img_d.device)
+    x = torch.empty(batch, 3, p, p, dtype=torch.float32, device=img_d.device)
+    with torch.no_grad():
+        for first, valid in passes:
+            ops.window_gather(img_d, tops, lefts, p, first, batch, out=x)
+            _keep(kept, model.forward_batch(x).contiguous(), first, valid)             # (batch, p, p, C)
+        merged, _ = ops.window_merge_classes(kept, tops, lefts, H, W)          # (probabilities: nothing comes in as an index)
+    return merged.cpu().numpy()
+
+
 def predict(trainer, img_path, patch_size, device='cuda', batch=None):
-    """One image file -> (H, W) map; ``batch=None`` is the per-window path, a number the device-resident one."""
+    """One image file -> (H, W) map; ``batch=None`` is the per-window path, a number the device-resident one.  A model of more
+    than two classes gives the uint8 class map of the ``_classes`` forms."""
     from PIL import Image
     img = np.asarray(Image.open(img_path).convert('RGB'))
+    if _n_classes(getattr(trainer, 'model', None)) > 2:
+        if batch is None:
+            return predict_array_classes(trainer, img, patch_size, device=device)
+        return predict_array_classes_batched(trainer, img, patch_size, batch=batch, device=device)
     if batch is None:
         return predict_array(trainer, img, patch_size, device=device)
     return predict_array_batched(trainer, img, patch_size, batch=batch, device=device)
 
 
-def save_predictions(predictions, img_paths, output_dir='predictions'):
+def save_predictions(predictions, img_paths, output_dir='predictions', n_classes=2):
+    """One image per prediction.  Two classes: {0, 255} under the input's own name, as ever.  More: the class indices themselves
+    as ``<stem>.png`` whatever the input is called (as ``infer.save_predictions``) -- under the name of a ``.jpg`` input a lossy
+    format would blur the indices."""
     from PIL import Image
     output_dir = Path(output_dir)
     output_dir.mkdir(parents=True, exist_ok=True)
     for pred, img_path in zip(predictions, img_paths):
-        Image.fromarray(pred.astype('uint8') * 255).save(output_dir / Path(img_path).name)
+        if n_classes == 2:
+            Image.fromarray(pred.astype('uint8') * 255).save(output_dir / Path(img_path).name)
+        else:
+            Image.fromarray(pred.astype('uint8')).save(output_dir / Path(img_path).with_suffix('.png').name, format='PNG')
 
 
 def infer(trainer, data_dir, patch_size, output_dir=None, device='cuda', batch=None):
@@ -198,37 +311,56 @@ def infer(trainer, data_dir, patch_size, output_dir=None, device='cuda', batch=N
     img_paths = sorted((data_dir / 'images').iterdir())
     predictions = [predict(trainer, p, patch_size, device=device, batch=batch) for p in img_paths]
     if output_dir is not None:
-        save_predictions(predictions, img_paths, output_dir)
+        save_predictions(predictions, img_paths, output_dir, n_classes=_n_classes(trainer.model))
     return predictions
 
 
 def pixel_infer(model, data_dir, patch_size, output_dir=None, device='cuda', batch=None):
     """Pixel-wise window inference on ``data_dir/images`` (pixel_infer_tile.py:41-60): the merged class-1 probabilities are
-    rounded here, before they are saved."""
+    rounded here, before they are saved.  A model of more than two classes gives class maps."""
     from PIL import Image
     model.eval()
     data_dir = Path(data_dir).expanduser()
     img_paths = sorted((data_dir / 'images').iterdir())
     predictions = []
+    C = _n_classes(model)
     for path in img_paths:
         img = np.asarray(Image.open(path).convert('RGB'))
+        if C > 2:
+            if batch is None:
+                predictions.append(pixel_predict_array_classes(model, img, patch_size, device=device))
+            else:
+                predictions.append(pixel_predict_array_classes_batched(model, img, patch_size, batch=batch, device=device))
+            continue
         if batch is None:
             merged = pixel_predict_array(model, img, patch_size, device=device)
         else:
             merged = pixel_predict_array_batched(model, img, patch_size, batch=batch, device=device)
         predictions.append(merged.round())
     if output_dir is not None:
-        save_predictions(predictions, img_paths, output_dir)
+        save_predictions(predictions, img_paths, output_dir, n_classes=C)
     return predictions
 
 
-def _load_pixel_model(checkpoint, device):
+def _load_pixel_model(checkpoint, device, multiclass=False):
+    """The pixel-wise model of a checkpoint.  A caller that reads the class-1 probability keeps ``multiclass=False``: a checkpoint
+    of more than two classes is refused.  One that dispatches on ``model.n_classes`` (the command-line tools) passes ``True`` and
+    gets the model with the checkpoint's class count.  ``checkpoint``: a path, or the dict ``torch.load`` made of one; a file is
+    read once."""
     from .models.wesup import WESUPPixelInference
-    model = WESUPPixelInference().to(device)
+    n_classes = 2
     if checkpoint is not None:
-        from .models import require_two_class_checkpoint
-        require_two_class_checkpoint(checkpoint, 'tile / pixel inference')
-        model.load_state_dict(torch.load(checkpoint, map_location=device)['model_state_dict'])
+        if not isinstance(checkpoint, dict):
+            checkpoint = torch.load(checkpoint, map_location=device)
+        if multiclass:
+            from .models import checkpoint_n_classes
+            n_classes = checkpoint_n_classes(checkpoint)
+        else:
+            from .models import require_two_class_checkpoint
+            require_two_class_checkpoint(checkpoint, 'tile / pixel inference')
+    model = WESUPPixelInference(n_classes=n_classes).to(device)
+    if checkpoint is not None:
+        model.load_state_dict(checkpoint['model_state_dict'])
     return model
 
 
@@ -249,13 +381,17 @@ def main(argv=None):
     if output_dir is None and a.checkpoint is not None:
         output_dir = Path(a.checkpoint).expanduser().parent.parent / 'results'
     if a.pixel:
-        model = _load_pixel_model(a.checkpoint, a.device)
+        if a.checkpoint is None:                     # (no checkpoint: no class count to read, the two-class default)
+            model = _load_pixel_model(None, a.device)
+        else:
+            model = _load_pixel_model(a.checkpoint, a.device, multiclass=True)
         pixel_infer(model, a.data_dir, a.patch_size, output_dir, device=a.device, batch=a.batch)
         return
-    trainer = initialize_trainer(a.model_type, device=a.device)
-    if a.checkpoint is not None:
-        from .models import require_two_class_checkpoint
-        require_two_class_checkpoint(a.checkpoint, 'tile inference')
+    if a.checkpoint is None:
+        trainer = initialize_trainer(a.model_type, device=a.device)
+    else:
+        from .models import checkpoint_n_classes
+        trainer = initialize_trainer(a.model_type, device=a.device, n_classes=checkpoint_n_classes(a.checkpoint))
         trainer.load_checkpoint(a.checkpoint)
     infer(trainer, a.data_dir, a.patch_size, output_dir, device=a.device, batch=a.batch)
 

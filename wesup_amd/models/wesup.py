@@ -255,13 +255,15 @@ def checkpoint_n_classes(checkpoint):
 
 
 def require_two_class_checkpoint(checkpoint, what):
-    """The tools that read the class-1 probability (pixel_infer, infer_tile, slide, evaluate) are two-class: a checkpoint of a
-    model with more classes is refused, not read through column 1."""
+    """What reads the class-1 probability or binary masks (evaluate's GlaS object metrics, a caller of
+    ``infer_tile._load_pixel_model`` without ``multiclass``) is two-class: a checkpoint of a model with more classes is refused,
+    not read through column 1.  The inference tools themselves (infer, infer_tile, pixel_infer, slide) write class-index maps for
+    such a checkpoint."""
     if checkpoint is not None:
         C = checkpoint_n_classes(checkpoint)
         if C != 2:
-            raise ValueError(f'{what} is two-class (it reads the class-1 probability): the checkpoint holds a {C}-class model; '
-                             'wesup_amd.infer writes class-index maps for it')
+            raise ValueError(f'{what} is two-class (it reads the class-1 probability or binary masks): the checkpoint holds a '
+                             f'{C}-class model; wesup_amd.infer, infer_tile, pixel_infer and slide write class-index maps for it')
 
 
 def _vgg16_features():

@@ -1856,6 +1856,146 @@ def mask_scores(S, G, negative=False, out=None):
     return out
 
 
+# ---------------------------------------------------------------- class maps for more than two classes (csrc/classmap.hip)
+def _chk_classes(C, name):
+    C = int(C)
+    if not 2 <= C <= _lib.MAX_CLASSES:
+        raise _lib.WesupHipError(f'{name}: {C} classes, expected 2 .. {_lib.MAX_CLASSES}')
+    return C
+
+
+def _status(status, device, name):
+    """The (1,) int32 status word of an entry: the caller's, or a new zeroed one."""
+    if status is None:
+        return torch.zeros(1, dtype=torch.int32, device=device)
+    _chk(status, torch.int32, 'status')
+    if status.numel() != 1 or status.device != device:
+        raise _lib.WesupHipError(f'{name}: status {tuple(status.shape)} on {status.device}, expected one int32 on {device}')
+    return status
+
+
+def window_merge_classes(pred, tops, lefts, H, W, n_classes=None, votes=False, out=None, status=None):
+    """The class map of a window-merged prediction for ALL N = len(tops) * len(lefts) windows of one image (row-major) ->
+    (out (H,W) uint8 class indices, status (1,) int32), equal to infer_tile.combine_patches_to_classes bit for bit.
+    ``votes=False``: pred (N,p,p,C) fp32 probabilities; per class the fp64 mean over the covering windows of ``window_merge``,
+    then the first maximum.  ``votes=True``: pred (N,p,p) fp32 class indices (what the superpixel model paints for C > 2) and
+    ``n_classes``; every covering window votes and the first maximum of the counts wins.  A vote outside [0, C) is not counted
+    and sets ``status`` (zeroed by the entry)."""
+    votes = bool(votes)
+    if not isinstance(pred, torch.Tensor) or pred.dim() != (3 if votes else 4):
+        raise _lib.WesupHipError('window_merge_classes: expected (N,p,p,C) probabilities, or (N,p,p) class indices with votes=True')
+    N, p, p2 = pred.shape[:3]
+    if votes and n_classes is None:
+        raise _lib.WesupHipError('window_merge_classes: votes=True needs n_classes')
+    C = _chk_classes(n_classes if votes else pred.shape[3], 'window_merge_classes')
+    if n_classes is not None and int(n_classes) != C:
+        raise _lib.WesupHipError(f'window_merge_classes: pred {tuple(pred.shape)} for {n_classes} classes')
+    H, W = int(H), int(W)
+    if p != p2:
+        raise _lib.WesupHipError(f'window_merge_classes: pred {tuple(pred.shape)}')
+    tops_d, lefts_d = _lattice(tops, lefts, H, W, p, pred.device)
+    if N != tops_d.numel() * lefts_d.numel():
+        raise _lib.WesupHipError(f'window_merge_classes: {N} windows for a lattice of {tops_d.numel()} x {lefts_d.numel()}')
+    _chk(pred, name='pred')
+    if out is None:
+        out = torch.empty(H, W, dtype=torch.uint8, device=pred.device)
+    _chk(out, torch.uint8, 'out')
+    if out.shape != (H, W) or out.device != pred.device:
+        raise _lib.WesupHipError(f'window_merge_classes: out {tuple(out.shape)} on {out.device}, expected {(H, W)}')
+    status = _status(status, pred.device, 'window_merge_classes')
+    tok = _tbegin('window_merge_classes')
+    _lib.call('wesup_window_merge_classes', _p(pred), _p(tops_d), _p(lefts_d), _p(out), _p(status), H, W, C, tops_d.numel(),
+              lefts_d.numel(), p, int(votes), _stream())
+    _tend(tok, 4.0 * N * p * p * (1 if votes else C) + 1.0 * H * W)
+    return out, status
+
+
+def planes_resize_acc(src, out, alpha=1.0, accumulate=False):
+    """out (H,W,C) = (accumulate ? out : 0) + alpha * bilinear_ac(src) for an (h,w,C) fp32 prediction, all C planes in one pass:
+    every plane equals ``plane_resize_acc(src[..., c], out[..., c])`` bit for bit."""
+    _chk(src, name='src'); _chk(out, name='out')
+    if src.dim() != 3 or out.dim() != 3 or src.shape[2] != out.shape[2] or src.device != out.device:
+        raise _lib.WesupHipError(f'planes_resize_acc: src {tuple(src.shape)}, out {tuple(out.shape)}: expected (h,w,C) and (H,W,C)')
+    h, w, C = src.shape
+    C = _chk_classes(C, 'planes_resize_acc')
+    H, W = out.shape[:2]
+    if min(h, w, H, W) < 1:
+        raise _lib.WesupHipError(f'planes_resize_acc: src {tuple(src.shape)}, out {tuple(out.shape)}')
+    tok = _tbegin('planes_resize_acc')
+    _lib.call('wesup_planes_resize_acc', _p(src), _p(out), h, w, H, W, C, float(alpha), int(bool(accumulate)), _stream())
+    _tend(tok, 4.0 * C * (h * w + (2 if accumulate else 1) * H * W))
+    return out
+
+
+def class_argmax_u8(src, out=None):
+    """src (..., C) fp32 -> (...) uint8: the first maximum of every row of C values (np.argmax on data without NaNs)."""
+    _chk(src, name='src')
+    if src.dim() < 2 or src.numel() < 1:
+        raise _lib.WesupHipError(f'class_argmax_u8: src {tuple(src.shape)}: expected (..., C)')
+    C = _chk_classes(src.shape[-1], 'class_argmax_u8')
+    shape = tuple(src.shape[:-1])
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=src.device)
+    _chk(out, torch.uint8, 'out')
+    if tuple(out.shape) != shape or out.device != src.device:
+        raise _lib.WesupHipError(f'class_argmax_u8: out {tuple(out.shape)} on {out.device}, expected {shape}')
+    n = src.numel() // C
+    tok = _tbegin('class_argmax_u8')
+    _lib.call('wesup_class_argmax_u8', _p(src), _p(out), n, C, _stream())
+    _tend(tok, (4.0 * C + 1.0) * n)
+    return out
+
+
+def patch_scatter_classes_u8(pred, out, p, first, n_classes=None, mode=0, status=None):
+    """``patch_scatter_u8`` for class maps: pastes a class index per slide pixel of the patches ``first .. first + count - 1`` into
+    out (H,W) uint8 -- the same lattice, the same crop, the rest of ``out`` left as it is.  ``mode`` 0: pred (count,h,w) fp32
+    class indices (the superpixel model's painted map) and ``n_classes``, nearest resize; an index outside [0, C) pastes 0 and
+    sets ``status``.  ``mode`` 1: pred (count,h,w,C) fp32 probabilities; per class the bilinear align_corners value of
+    ``planes_resize_acc(alpha=1)``, then the first maximum.  ``status`` (1,) int32 is OR-ed into, so that one word serves all the
+    passes of a slide; a new zeroed one is made when none is given.  Returns (out, status)."""
+    _chk(out, torch.uint8, 'out'); _chk(pred, name='pred')
+    if mode not in (0, 1):
+        raise _lib.WesupHipError(f'patch_scatter_classes_u8: mode {mode}')
+    if pred.dim() != (3 if mode == 0 else 4) or out.dim() != 2 or pred.device != out.device:
+        raise _lib.WesupHipError('patch_scatter_classes_u8: expected (count,h,w) class indices (mode 0) or (count,h,w,C) '
+                                 'probabilities (mode 1) and an (H,W) uint8 map on one device')
+    if mode == 0 and n_classes is None:
+        raise _lib.WesupHipError('patch_scatter_classes_u8: mode 0 needs n_classes')
+    C = _chk_classes(n_classes if mode == 0 else pred.shape[3], 'patch_scatter_classes_u8')
+    if n_classes is not None and int(n_classes) != C:
+        raise _lib.WesupHipError(f'patch_scatter_classes_u8: pred {tuple(pred.shape)} for {n_classes} classes')
+    count, h, w = pred.shape[:3]
+    H, W, p, first, count = _patch_lattice(out.shape[0], out.shape[1], p, first, count, 'patch_scatter_classes_u8')
+    if h < 1 or w < 1:
+        raise _lib.WesupHipError(f'patch_scatter_classes_u8: pred {tuple(pred.shape)}')
+    status = _status(status, out.device, 'patch_scatter_classes_u8')
+    tok = _tbegin('patch_scatter_classes_u8')
+    _lib.call('wesup_patch_scatter_classes_u8', _p(pred), _p(out), _p(status), H, W, p, h, w, C, int(mode), first, count,
+              _stream())
+    _tend(tok, 4.0 * count * h * w * (C if mode else 1) + 1.0 * count * p * p)
+    return out, status
+
+
+def label_confusion(S, G, n_classes, out=None, status=None):
+    """The confusion table of two uint8 class-index maps of one shape: (conf (C,C) int64, status (1,) int32) on the device,
+    ``conf[g][s]`` = pixels of ground-truth class g predicted as s (utils.metrics.confusion); a byte >= C is not counted and sets
+    ``status``.  Both are zeroed by the entry."""
+    _chk(S, torch.uint8, 'S'); _chk(G, torch.uint8, 'G')
+    C = _chk_classes(n_classes, 'label_confusion')
+    if S.shape != G.shape or S.numel() < 1 or S.device != G.device:
+        raise _lib.WesupHipError(f'label_confusion: maps {tuple(S.shape)} and {tuple(G.shape)}')
+    if out is None:
+        out = torch.empty(C, C, dtype=torch.int64, device=S.device)
+    _chk(out, torch.int64, 'conf')
+    if out.shape != (C, C) or out.device != S.device:
+        raise _lib.WesupHipError(f'label_confusion: conf {tuple(out.shape)} on {out.device}, expected {(C, C)}')
+    status = _status(status, S.device, 'label_confusion')
+    tok = _tbegin('label_confusion')
+    _lib.call('wesup_label_confusion', _p(S), _p(G), _p(out), _p(status), S.numel(), C, _stream())
+    _tend(tok, 2.0 * S.numel())
+    return out, status
+
+
 # ---------------------------------------------------------------- weak-label preparation (csrc/prepare.hip)
 LABEL_STATS_MAX_LABELS = 1 << 26     # labels 0 .. L with L below this
 SP_VOTE_MAX_PIXELS = ((1 << 32) - 1) // 255      # 32-bit sums of uint8 values

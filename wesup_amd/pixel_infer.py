@@ -75,9 +75,31 @@ def pixel_predict(model, img_u8_hwc, scales=(0.5,), device='cuda', full_maps=Fal
     return mean.cpu().numpy()
 
 
+def pixel_predict_classes(model, img_u8_hwc, scales=(0.5,), device='cuda', full_maps=False):
+    """``pixel_predict`` for a model of more than two classes: (H, W, 3) uint8 image -> (H, W) uint8 class map.  Per scale all C
+    probabilities are resized back in one pass into one (H, W, C) running mean (``ops.planes_resize_acc``, every plane the
+    arithmetic of ``plane_resize_acc``), then the first maximum per pixel (``ops.class_argmax_u8``) and one copy to the host."""
+    scales = tuple(scales)
+    if not scales:
+        raise ValueError('pixel_predict_classes: no scales')
+    img_d = _upload(img_u8_hwc, device)
+    H, W = img_d.shape[:2]
+    mean = torch.empty(H, W, model.n_classes, dtype=torch.float32, device=img_d.device)
+    with torch.no_grad():
+        for i, scale in enumerate(scales):
+            h, w = target_size(H, W, scale)
+            if h < 1 or w < 1:
+                raise ValueError(f'scale {scale} leaves nothing of a {H} x {W} image')
+            x = ops.image_resize_u8(img_d, h, w)
+            pred = model(x) if full_maps else model.forward_per_resolution(x)[0]          # (h, w, C)
+            ops.planes_resize_acc(pred.contiguous(), mean, alpha=1.0 / len(scales), accumulate=i > 0)
+        classes = ops.class_argmax_u8(mean)
+    return classes.cpu().numpy()
+
+
 def main(data_root, checkpoint=None, output_dir=None, scales=(0.5,), device=None, full_maps=False):
-    """pixel_infer.py:20-56 on ``data_root/images``: one PNG of ``round(mean probability) * 255`` per image.  Returns the
-    written paths."""
+    """pixel_infer.py:20-56 on ``data_root/images``: one PNG of ``round(mean probability) * 255`` per image -- of the class
+    indices for a checkpoint of more than two classes (``pixel_predict_classes``).  Returns the written paths."""
     from PIL import Image
     if device is None:
         device = 'cuda'
@@ -87,13 +109,17 @@ def main(data_root, checkpoint=None, output_dir=None, scales=(0.5,), device=None
         raise ValueError('pixel_infer: neither an output directory nor a checkpoint to derive one from')
     output_dir = Path(output_dir).expanduser()
     output_dir.mkdir(parents=True, exist_ok=True)
-    model = _load_pixel_model(checkpoint, device)
+    model = _load_pixel_model(checkpoint, device, multiclass=True)
     model.eval()
     written = []
     for path in image_paths(data_root):
         img = np.asarray(Image.open(path).convert('RGB'))
-        prob = pixel_predict(model, img, scales, device=device, full_maps=full_maps)
         out = output_dir / output_name(path.name)
+        if model.n_classes > 2:                      # the class indices themselves, no x 255 (infer.save_predictions)
+            Image.fromarray(pixel_predict_classes(model, img, scales, device=device, full_maps=full_maps)).save(out, format='PNG')
+            written.append(out)
+            continue
+        prob = pixel_predict(model, img, scales, device=device, full_maps=full_maps)
         Image.fromarray(prob.round().astype('uint8') * 255).save(out, format='PNG')
         written.append(out)
     return written

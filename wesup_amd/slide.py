@@ -12,6 +12,10 @@ The slide is uploaded once as uint8 and comes back once as a uint8 map: per pass
 ``ops.patch_gather_resize`` (cut + resize) -> the model -> ``ops.patch_scatter_u8`` (resize back + round + paste), nothing
 in between waits for the device.
 
+A checkpoint of more than two classes gives class maps: ``ops.patch_scatter_classes_u8`` pastes class indices,
+the PNGs hold them as they are, and all slides are scored as one group against class-index masks from the C x C confusion table
+(``slide_class_scores``; ``ops.label_confusion`` on the device).
+
 Two deliberate deviations from the reference:
 
 * **No extra patch at exact multiples.**  The reference cuts at ``range(0, size + 1, patch_size)``, which asks for one more,
@@ -30,7 +34,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .infer_tile import _load_pixel_model, _upload, window_batches
+from .infer_tile import _check_status, _load_pixel_model, _n_classes, _upload, window_batches
 from .pixel_infer import target_size
 
 PATCH_SIZE = 1000              # test_dp2019_pipeline.py:122
@@ -121,7 +125,8 @@ def slide_predict(trainer, img_u8, patch_size=PATCH_SIZE, input_size=INPUT_SIZE,
     per pass of ``batch`` patches ``ops.patch_gather_resize`` -> ``trainer.preprocess`` (batched GPU SLIC) -> ``trainer.model``
     -> ``ops.patch_scatter_u8`` (round, nearest resize to the patch, paste, crop); one copy back, or the device tensor with
     ``keep_on_device``.  At ``batch=1`` equal to the per-patch path bit for bit; at another batch size the convolutions tile
-    differently and a pixel whose probability sits at 0.5 can turn (tests/test_slide_gpu.py)."""
+    differently and a pixel whose probability sits at 0.5 can turn (tests/test_slide_gpu.py).  A model of more than two classes
+    gives the (H, W) uint8 map of class indices (``ops.patch_scatter_classes_u8``)."""
     p = int(patch_size)
     h, w = (int(s) for s in input_size)
     img_d = _resident(img_u8, device)
@@ -130,19 +135,28 @@ def slide_predict(trainer, img_u8, patch_size=PATCH_SIZE, input_size=INPUT_SIZE,
     passes, batch = window_batches(n_h * n_w, batch)
     out = torch.empty(H, W, dtype=torch.uint8, device=img_d.device)            # (the lattice covers every pixel)
     x = torch.empty(batch, 3, h, w, dtype=torch.float32, device=img_d.device)
+    C = _n_classes(trainer.model)
+    status = torch.zeros(1, dtype=torch.int32, device=img_d.device) if C > 2 else None
     with torch.no_grad():
         for first, valid in passes:
             ops.patch_gather_resize(img_d, p, h, w, first, batch, align_corners=False, out=x)
             input_, _ = trainer.preprocess(x)
-            ops.patch_scatter_u8(trainer.model(input_)[:valid], out, p, first, mode=0)
-    return out if keep_on_device else out.cpu().numpy()
+            if C > 2:                                # the painted class indices, pasted as they are
+                ops.patch_scatter_classes_u8(trainer.model(input_)[:valid], out, p, first, n_classes=C, mode=0, status=status)
+            else:
+                ops.patch_scatter_u8(trainer.model(input_)[:valid], out, p, first, mode=0)
+    result = out if keep_on_device else out.cpu().numpy()
+    if status is not None:                           # one word over all passes, read once, behind the map
+        _check_status(status, C, 'slide_predict')
+    return result
 
 
 def slide_pixel_predict(model, img_u8, patch_size=PATCH_SIZE, scale=PIXEL_SCALE, batch=2, device='cuda', keep_on_device=False):
     """Pixel-wise prediction of a whole slide -> (H, W) uint8 map in {0, 255}: ``pixel_infer`` with ``scales=(scale,)`` on every
     zero-padded patch, pasted and cropped.  Per pass ``ops.patch_gather_resize(align_corners=True)`` to
     ``pixel_infer.target_size`` -> ``model.forward_per_resolution`` -> ``ops.patch_scatter_u8`` reading class 1 in place
-    (bilinear back to the patch, round, paste)."""
+    (bilinear back to the patch, round, paste).  A model of more than two classes gives the map of class indices: all C
+    planes bilinear back to the patch, the first maximum pasted (``ops.patch_scatter_classes_u8``)."""
     p = int(patch_size)
     h, w = target_size(p, p, scale)
     if h < 1 or w < 1:
@@ -153,12 +167,43 @@ def slide_pixel_predict(model, img_u8, patch_size=PATCH_SIZE, scale=PIXEL_SCALE,
     passes, batch = window_batches(n_h * n_w, batch)
     out = torch.empty(H, W, dtype=torch.uint8, device=img_d.device)
     x = torch.empty(batch, 3, h, w, dtype=torch.float32, device=img_d.device)
+    C = _n_classes(model)
+    # (mode 1 takes probabilities: nothing comes in as an index and the word is never set -- one for all passes, not read)
+    status = torch.zeros(1, dtype=torch.int32, device=img_d.device) if C > 2 else None
     with torch.no_grad():
         for first, valid in passes:
             ops.patch_gather_resize(img_d, p, h, w, first, batch, align_corners=True, out=x)
             probs = model.forward_per_resolution(x)                             # (batch, h, w, C)
-            ops.patch_scatter_u8(probs[:valid, :, :, 1], out, p, first, mode=1)
+            if C > 2:                                # all C planes resized back, the first maximum pasted
+                ops.patch_scatter_classes_u8(probs[:valid], out, p, first, mode=1, status=status)
+            else:
+                ops.patch_scatter_u8(probs[:valid, :, :, 1], out, p, first, mode=1)
     return out if keep_on_device else out.cpu().numpy()
+
+
+def slide_class_scores(pred, gt, n_classes, device=None):
+    """``(accuracy, dice)`` of two uint8 class-index maps as Python floats, by the definitions of DESIGN.md 3.12: the trace of
+    the confusion table over the pixels, and the mean over the classes present in either map of 2 n_cc / (row_c + col_c + eps)
+    (``utils.metrics.accuracy_from_confusion`` / ``dice_from_confusion``).  With ``device`` (or for maps that are device tensors
+    already) the table is ``ops.label_confusion``'s, otherwise ``utils.metrics.confusion``'s: integers either way, the same
+    numbers.  A class index outside [0, n_classes) is an error on both paths."""
+    from .utils import metrics as M
+    C = int(n_classes)
+    on_device = isinstance(pred, torch.Tensor) and pred.is_cuda
+    if device is None and not on_device:
+        conf = M.confusion(pred.cpu() if isinstance(pred, torch.Tensor) else pred, gt.cpu() if isinstance(gt, torch.Tensor) else gt, C)
+    else:
+        device = pred.device if on_device else device
+
+        def resident(a):
+            if isinstance(a, torch.Tensor):
+                return a.to(device).contiguous()
+            return torch.from_numpy(np.ascontiguousarray(np.asarray(a).astype(np.uint8, copy=False))).to(device)
+        table, status = ops.label_confusion(resident(pred), resident(gt), C)
+        conf = table.cpu().numpy()
+        if int(status.cpu()) != 0:
+            raise ValueError(f'class index outside [0, {C})')
+    return M.accuracy_from_confusion(conf), M.dice_from_confusion(conf)
 
 
 def slide_scores(pred_u8, gt_u8, negative=False, device=None):
@@ -201,10 +246,35 @@ def _read_gray(path):
     return np.asarray(Image.open(path).convert('L'))
 
 
-def score_directory(output_dir, gt_dir, log=print, device=None):
+def _read_classes(path):
+    """A class-index PNG as it is stored: the bytes of a grey ('L') image, the palette INDICES of a palette ('P') one, which is how
+    label masks are often written -- ``convert('L')`` would turn those into the luminance of their colours."""
+    from PIL import Image
+    with Image.open(path) as im:
+        return np.asarray(im if im.mode in ('L', 'P') else im.convert('L'))
+
+
+def score_directory(output_dir, gt_dir, log=print, device=None, n_classes=2):
     """The scoring half of the reference (test_dp2019_pipeline.py:197-219) on the combined PNGs of ``output_dir`` against the
     masks of ``gt_dir``.  Returns ``{'positive': (accuracy, dice), 'negative': (accuracy, dice)}`` (a group without slides is
-    left out)."""
+    left out).
+
+    With ``n_classes > 2`` the PNGs and the masks are class-index maps and ALL of them are scored as one group: the inversion
+    that tells the negative slides from the positive ones swaps foreground and background, which has no meaning for class
+    indices.  A prediction is scored against the mask of its own stem.  Returns ``{'all': (accuracy, dice)}``, the means of
+    ``slide_class_scores`` over the slides."""
+    if int(n_classes) > 2:
+        preds, gts = sorted(Path(output_dir).glob('*.png')), sorted(Path(gt_dir).glob('*.png'))
+        log('\nEvaluating OA and Dice ...')
+        if [p.stem for p in preds] != [g.stem for g in gts]:
+            raise ValueError(f'predictions {[p.stem for p in preds]} in {output_dir} but masks {[g.stem for g in gts]} in {gt_dir}')
+        if not preds:
+            return {}
+        scores = [slide_class_scores(_read_classes(p), _read_classes(g), n_classes, device) for p, g in zip(preds, gts)]
+        acc, dsc = float(np.mean([s[0] for s in scores])), float(np.mean([s[1] for s in scores]))
+        log('Accuracy:', acc)
+        log('Dice:', dsc)
+        return {'all': (acc, dsc)}
     pos_pred, neg_pred = split_stems(Path(output_dir).glob('*.png'))
     pos_gt, neg_gt = split_stems(Path(gt_dir).glob('*.png'))
     result = {}
@@ -220,25 +290,34 @@ def score_directory(output_dir, gt_dir, log=print, device=None):
 def main(data_root, checkpoint, model_type='wesup', pixel=False, patch_size=PATCH_SIZE, skip_infer=False, device=None, batch=None,
          post_threshold=None, log=print):
     """test_dp2019_pipeline.py:114-219 without its patch files: predict every slide of ``data_root/images/*.jpg`` (unless
-    ``skip_infer``), write the combined PNGs, score them against ``data_root/masks``.  Returns ``score_directory``'s result."""
+    ``skip_infer``), write the combined PNGs, score them against ``data_root/masks``.  Returns ``score_directory``'s result.
+
+    The class count is the checkpoint's.  For more than two classes the PNGs hold class indices, the masks are read as class
+    indices and ``post_threshold`` (a clean-up of binary maps) is refused.  Under ``skip_infer`` the checkpoint only names the
+    output directory and need not exist: without the file the PNGs on disk are scored as two-class maps."""
     from PIL import Image
     data_root = Path(data_root).expanduser()
     output_dir = output_dir_for(checkpoint, pixel)
     output_dir.mkdir(parents=True, exist_ok=True)
     if device is None:
         device = 'cuda'
+    C, loaded = 2, None
+    if not skip_infer or Path(checkpoint).expanduser().is_file():
+        from .models import checkpoint_n_classes
+        loaded = torch.load(Path(checkpoint).expanduser(), map_location='cpu')      # read once: the class count, the pixel model
+        C = checkpoint_n_classes(loaded)
+    if C > 2 and post_threshold is not None:
+        raise ValueError('--post-threshold removes small regions of a binary map: undefined for class indices')
     if not skip_infer:
         log('\nMaking inference ...')
         if pixel:
             if model_type != 'wesup':
                 raise ValueError('--pixel is the wesup model\'s pixel-wise inference')
-            model = _load_pixel_model(checkpoint, device)
+            model = _load_pixel_model(loaded, device, multiclass=True)
             model.eval()
         else:
             from .models import initialize_trainer
-            trainer = initialize_trainer(model_type, device=device)
-            from .models import require_two_class_checkpoint
-            require_two_class_checkpoint(checkpoint, 'whole-slide evaluation')
+            trainer = initialize_trainer(model_type, device=device, n_classes=C)
             trainer.load_checkpoint(checkpoint)
             trainer.model.eval()
         for path in sorted((data_root / 'images').glob('*.jpg')):
@@ -251,7 +330,7 @@ def main(data_root, checkpoint, model_type='wesup', pixel=False, patch_size=PATC
                 combined = postprocess(combined, post_threshold, device)
             Image.fromarray(combined).save(output_dir / f'{path.stem}.png', format='PNG')
         log(f'Combined results saved to {output_dir}.')
-    return score_directory(output_dir, data_root / 'masks', log, device if not skip_infer else None)
+    return score_directory(output_dir, data_root / 'masks', log, device if not skip_infer else None, n_classes=C)
 
 
 def parse_args(argv=None):
