@@ -694,6 +694,47 @@ size_t wesup_tsne_iterate_workspace_bytes(int n);
 int wesup_tsne_iterate(const float* p, float* y, float* upd, float* gains, float* stats, int n, int iters, float exaggeration,
                        float momentum, float lr, float min_gain, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------ stain normalisation and stain jitter (csrc/stain.hip)
+ * Macenko normalisation of H&E images (Macenko et al., ISBI 2009) and its augmentation twin, a jitter of the two stain
+ * concentrations (the reference has neither).  Images are (B, H, W, 3) uint8. */
+/* Exact order statistics: out[r] = the element that np.sort(keys)[ranks[r]] names, bit for bit (-0 sorts in front of +0, NaNs by
+ * their bits at the two ends), 1 <= n_ranks <= WESUP_SELECT_MAX_RANKS.  ranks is a DEVICE array (a rank outside [0, n) is taken
+ * to the nearest end).  Radix select, four passes of 8 bits over the same keys: per pass a histogram launch of
+ * min(WESUP_SELECT_MAX_BLOCKS, ceil(n / WESUP_SELECT_BLOCK)) blocks and a one-block step.
+ * workspace = 256 + blocks * WESUP_SELECT_MAX_RANKS * 256 * 4 bytes. */
+#define WESUP_SELECT_BLOCK 256
+#define WESUP_SELECT_MAX_BLOCKS 256
+#define WESUP_SELECT_MAX_RANKS 4
+size_t wesup_select_f32_workspace_bytes(long n);
+int wesup_select_f32(const float* keys, long n, const long* ranks, int n_ranks, float* out, void* ws, size_t ws_bytes,
+                     void* stream);
+/* The fit of image b, WESUP_STAIN_BLOCK floats (64 bytes) that stay on the device:
+ *   [0..5] HE[c][k] (c = r, g, b; k = 0 "H", 1 "E"), [6..11] pinv[k][c], [12..13] maxC[k], [14] n_tissue, [15] valid (1 or 0;
+ *   an invalid fit is all zeros but n_tissue). */
+#define WESUP_STAIN_BLOCK 16
+/* OD = -log((v + 1) / io) per channel; tissue = all three OD >= beta; the fit samples every stride-th row and column
+ * (ceil(H / stride) * ceil(W / stride) <= 2^24 samples per image).  Tissue covariance, its two leading eigenvectors, the
+ * alpha-th and (100 - alpha)-th percentile of the angle in their plane, the two stain vectors (the redder one first), the
+ * pseudo-inverse, the 99th percentile of both concentrations over ALL samples.  Invalid: n_tissue < min_tissue (>= 2),
+ * |det(HE^T HE)| < 1e-6 (parallel vectors), or a maxC below 1e-6.  One chain of launches, no host read-back.
+ * The workspace also holds the stages (wesup_stain_fit_stage_offset, bytes from ws): MOMENTS [B][10] doubles {n, sum r g b,
+ * sum rr rg rb gg gb bb} of the tissue OD; SCRATCH [B] slots of 256 bytes that start with the eigenvectors V[c][k] as 6 doubles;
+ * PHI [B][samples] floats (+inf where not tissue); CONC [B][2][samples] floats. */
+#define WESUP_STAIN_STAGE_MOMENTS 0
+#define WESUP_STAIN_STAGE_SCRATCH 1
+#define WESUP_STAIN_STAGE_PHI 2
+#define WESUP_STAIN_STAGE_CONC 3
+size_t wesup_stain_fit_workspace_bytes(int B, int H, int W, int stride);
+size_t wesup_stain_fit_stage_offset(int B, int H, int W, int stride, int stage);
+int wesup_stain_fit(const uint8_t* img, float* blocks, int B, int H, int W, int stride, float io, float alpha, float beta,
+                    int min_tissue, void* ws, size_t ws_bytes, void* stream);
+/* Per pixel, with the source fit of image b, the destination block (dst_stride = 0: one for all, WESUP_STAIN_BLOCK: one each)
+ * and jitter[b] = {a_H, b_H, a_E, b_E} (NULL: 1, 0, 1, 0):  c = pinv_s OD;  c' = c (maxC_d / maxC_s) a + b;
+ * OD' = HE_d c' + keep_residual (OD - HE_s c);  v' = rint(clamp(io exp(-OD') - 1, 0, 255)).  An invalid source or destination
+ * makes the image a plain copy.  out == img is allowed (any other overlap is refused). */
+int wesup_stain_apply(const uint8_t* img, uint8_t* out, const float* src_blocks, const float* dst_blocks, int dst_stride,
+                      const float* jitter, float keep_residual, int B, int H, int W, float io, void* stream);
+
 /* ------------------------------------------------------------------ entries by the names of SURVEY.md 8(b)
  * One call per ATen op of the reference for a binding that replaces them one by one; each is a thin entry over the
  * kernels above (csrc/named.hip).  Matrices are row-major with the channel / feature index contiguous (NHWC pixels). */

@@ -145,6 +145,13 @@ _SIGS = {
     'wesup_tsne_affinities': (c_int, 'pif' + 'pp' + 'pzp'),
     'wesup_tsne_iterate_workspace_bytes': (c_size_t, 'i'),
     'wesup_tsne_iterate': (c_int, 'ppppp' + 'ii' + 'ffff' + 'pzp'),
+    # stain normalisation and stain jitter, exact order statistics (csrc/stain.hip)
+    'wesup_select_f32_workspace_bytes': (c_size_t, 'l'),
+    'wesup_select_f32': (c_int, 'plpip' + 'pzp'),
+    'wesup_stain_fit_workspace_bytes': (c_size_t, 'iiii'),
+    'wesup_stain_fit_stage_offset': (c_size_t, 'iiiii'),
+    'wesup_stain_fit': (c_int, 'pp' + 'iiii' + 'fffi' + 'pzp'),
+    'wesup_stain_apply': (c_int, 'pppp' + 'ipf' + 'iii' + 'fp'),
     # window inference on large images (csrc/tiles.hip)
     'wesup_window_gather': (c_int, 'pppp' + 'iiiiiii' + 'p'),
     'wesup_window_merge': (c_int, 'pppp' + 'iiiiiii' + 'p'),
@@ -211,6 +218,10 @@ HEAD_MAX_D = 149         # WESUP_HEAD_MAX_D: the propagation kernel's LDS tile, 
 TSNE_MAX_N = 32768       # WESUP_TSNE_MAX_N: the joint probabilities are dense fp32, 4 GiB there
 TSNE_MAX_D = 4096        # WESUP_TSNE_MAX_D
 TSNE_STATS = 4           # WESUP_TSNE_STATS: KL, |g|, Z, sum p log p
+SELECT_BLOCK = 256       # WESUP_SELECT_BLOCK
+SELECT_MAX_BLOCKS = 256  # WESUP_SELECT_MAX_BLOCKS
+SELECT_MAX_RANKS = 4     # WESUP_SELECT_MAX_RANKS
+STAIN_BLOCK = 16         # WESUP_STAIN_BLOCK: HE[3][2], pinv[2][3], maxC[2], n_tissue, valid
 ABI_VERSION = 6          # include/wesup_hip.h; a stale libwesup_hip.so with other signatures must not be called
 
 _lib = None

@@ -47,7 +47,7 @@ def n_classes_of(trainer):
     return int(C or (getattr(trainer, 'kwargs', None) or {}).get('n_classes') or 2)
 
 
-def predict(trainer, dataset, input_size=None, scales=(0.5,), device='cuda', device_post=False):
+def predict(trainer, dataset, input_size=None, scales=(0.5,), device='cuda', device_post=False, stain=None):
     """Predict every image of ``dataset`` (raw items of utils.data.SegmentationDataset).  Returns a list of (H,W) masks --
     class-index maps for a model of more than two classes, which single-scale and fixed-size inference handle unchanged.
     ``device_post``: the opening of a multi-scale prediction runs on the device too (ops.binary_opening: scipy's conventions
@@ -61,6 +61,8 @@ def predict(trainer, dataset, input_size=None, scales=(0.5,), device='cuda', dev
         raw = dataset[i]
         img, mask = dataset.to_reference_item(raw)
         img = img.unsqueeze(0).to(device)
+        if stain is not None:                        # the raw uint8 image, normalised on the device in front of ToTensor's scaling
+            img = stain(raw[0].to(device).contiguous()).permute(2, 0, 1).float().div_(255.).unsqueeze(0)
         mask = mask.unsqueeze(0).to(device).float() if mask.dim() == 3 else mask
         orig_size = (img.size(2), img.size(3))
 
@@ -123,16 +125,17 @@ def evaluate_predictions(predictions, dataset, device=None):
     return {k: float(np.nanmean([r[k] for r in rows])) for k in keys}, rows
 
 
-def infer(trainer, data_dir, output_dir=None, input_size=None, scales=(0.5,), device='cuda', device_post=False):
+def infer(trainer, data_dir, output_dir=None, input_size=None, scales=(0.5,), device='cuda', device_post=False, stain=None):
     trainer.model.eval()
     dataset = SegmentationDataset(data_dir, train=False, n_classes=n_classes_of(trainer))
-    predictions = predict(trainer, dataset, input_size=input_size, scales=scales, device=device, device_post=device_post)
+    predictions = predict(trainer, dataset, input_size=input_size, scales=scales, device=device, device_post=device_post,
+                          **({} if stain is None else {'stain': stain}))
     if output_dir is not None:
         save_predictions(predictions, dataset, output_dir, n_classes=n_classes_of(trainer))
     return predictions
 
 
-def main(argv=None):
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     ap.add_argument('data_dir')
     ap.add_argument('--model-type', default='wesup')
@@ -142,17 +145,24 @@ def main(argv=None):
     ap.add_argument('--scales', type=float, nargs='+', default=[0.5])
     ap.add_argument('--device', default='cuda')
     ap.add_argument('--device-post', action='store_true', help='open multi-scale predictions on the device (default: scipy on the CPU)')
-    a = ap.parse_args(argv)
+    from .stain import add_argument
+    add_argument(ap)
+    return ap.parse_args(argv)
+
+
+def main(argv=None):
+    a = parse_args(argv)
     output_dir = a.output_dir
     if output_dir is None and a.checkpoint is not None:
         output_dir = Path(a.checkpoint).parent.parent / 'results'
     from .models import checkpoint_n_classes
+    from .stain import make_normalizer
     C = checkpoint_n_classes(a.checkpoint) if a.checkpoint is not None else 2
     trainer = initialize_trainer(a.model_type, device=a.device, n_classes=C)
     if a.checkpoint is not None:
         trainer.load_checkpoint(a.checkpoint)
     infer(trainer, a.data_dir, output_dir, input_size=a.input_size, scales=tuple(a.scales), device=a.device,
-          device_post=a.device_post)
+          device_post=a.device_post, **({} if a.stain_normalize is None else {'stain': make_normalizer(a.stain_normalize, a.device)}))
 
 
 if __name__ == '__main__':

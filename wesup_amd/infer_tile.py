@@ -100,8 +100,9 @@ def _to_tensor(patch, device):
     return torch.from_numpy(np.ascontiguousarray(patch)).to(device).permute(2, 0, 1).float().div_(255.).unsqueeze(0)
 
 
-def predict_array(trainer, img, patch_size, device='cuda'):
+def predict_array(trainer, img, patch_size, device='cuda', stain=None):
     """Window-based superpixel prediction of one (H, W, 3) uint8 image -> (H, W) float map (infer_tile.py:94-119)."""
+    img = _stained(img, stain, device)
     patches = divide_image_to_patches(img, patch_size)
     predictions = []
     with torch.no_grad():
@@ -113,9 +114,10 @@ def predict_array(trainer, img, patch_size, device='cuda'):
     return combine_patches_to_image(predictions, img.shape[0], img.shape[1])
 
 
-def pixel_predict_array(model, img, patch_size, device='cuda'):
+def pixel_predict_array(model, img, patch_size, device='cuda', stain=None):
     """Window-based pixel-wise prediction with WESUPPixelInference -> (H, W) class-1 probability
     (pixel_infer_tile.py:41-60; the caller rounds)."""
+    img = _stained(img, stain, device)
     patches = divide_image_to_patches(img, patch_size)
     predictions = []
     with torch.no_grad():
@@ -137,9 +139,10 @@ def _check_status(status, n_classes, what):
         raise RuntimeError(f'{what}: the model painted a class index outside [0, {n_classes})')
 
 
-def predict_array_classes(trainer, img, patch_size, device='cuda'):
+def predict_array_classes(trainer, img, patch_size, device='cuda', stain=None):
     """``predict_array`` for a model of more than two classes -> (H, W) uint8 class map: every window's painted class indices
     (what ``trainer.model`` returns for C > 2) come to the host and vote (``combine_patches_to_classes(votes=True)``)."""
+    img = _stained(img, stain, device)
     patches = divide_image_to_patches(img, patch_size)
     predictions = []
     with torch.no_grad():
@@ -149,9 +152,10 @@ def predict_array_classes(trainer, img, patch_size, device='cuda'):
     return combine_patches_to_classes(np.concatenate(predictions), img.shape[0], img.shape[1], _n_classes(trainer.model), votes=True)
 
 
-def pixel_predict_array_classes(model, img, patch_size, device='cuda'):
+def pixel_predict_array_classes(model, img, patch_size, device='cuda', stain=None):
     """``pixel_predict_array`` for a model of more than two classes -> (H, W) uint8 class map: all C probabilities of every
     window are merged on the host, then the first maximum."""
+    img = _stained(img, stain, device)
     patches = divide_image_to_patches(img, patch_size)
     predictions = []
     with torch.no_grad():
@@ -172,12 +176,23 @@ def window_batches(n_windows, batch):
     return [(first, min(batch, n_windows - first)) for first in range(0, n_windows, batch)], batch
 
 
-def _upload(img, device):
-    """(H, W, 3) image -> uint8 tensor on the device, uploaded once (the cast is divide_image_to_patches')."""
+def _upload(img, device, stain=None):
+    """(H, W, 3) image -> uint8 tensor on the device, uploaded once (the cast is divide_image_to_patches').  ``stain`` (a
+    wesup_amd.stain.StainNormalizer): fitted once on the resident tensor and applied in place, in front of every window gather."""
     img = np.asarray(img)
     if img.ndim != 3 or img.shape[-1] != 3:
         raise AssertionError('expected an (H, W, 3) image')
-    return torch.from_numpy(np.ascontiguousarray(img.astype(np.uint8, copy=False))).to(device)
+    img_d = torch.from_numpy(np.ascontiguousarray(img.astype(np.uint8, copy=False))).to(device)
+    if stain is not None:
+        stain(img_d, out=img_d)
+    return img_d
+
+
+def _stained(img, stain, device):
+    """The per-window paths cut their windows on the host: one upload, one normalisation, one copy back in front of them."""
+    if stain is None:
+        return img
+    return _upload(img, device, stain).cpu().numpy()
 
 
 def _keep(dst, src, first, valid):
@@ -188,7 +203,7 @@ def _keep(dst, src, first, valid):
     _lib.call('wesup_copy', ops._p(dst[first]), ops._p(src), valid * row * 4, ops._stream())
 
 
-def predict_array_batched(trainer, img, patch_size, batch=4, device='cuda'):
+def predict_array_batched(trainer, img, patch_size, batch=4, device='cuda', stain=None):
     """``predict_array`` with the image resident on the device: one upload, ``batch`` windows per pass (``ops.window_gather``
     -> ``trainer.preprocess`` with the batched GPU SLIC -> ``trainer.model``), the painted probabilities of all windows kept
     in one (N, p, p, 1) device buffer, one ``ops.window_merge(round_first=True)`` and ONE copy to the host.  Nothing between
@@ -202,7 +217,7 @@ def predict_array_batched(trainer, img, patch_size, batch=4, device='cuda'):
     H, W = img.shape[:2]
     tops, lefts = window_grid(H, W, p)
     passes, batch = window_batches(len(tops) * len(lefts), batch)
-    img_d = _upload(img, device)
+    img_d = _upload(img, device, stain)
     kept = torch.empty(len(tops) * len(lefts), p, p, 1, dtype=torch.float32, device=img_d.device)
     x = torch.empty(batch, 3, p, p, dtype=torch.float32, device=img_d.device)
     with torch.no_grad():
@@ -214,7 +229,7 @@ def predict_array_batched(trainer, img, patch_size, batch=4, device='cuda'):
     return merged.view(H, W).cpu().numpy()
 
 
-def pixel_predict_array_batched(model, img, patch_size, batch=2, device='cuda'):
+def pixel_predict_array_batched(model, img, patch_size, batch=2, device='cuda', stain=None):
     """``pixel_predict_array`` with the image resident on the device: ``batch`` windows per
     ``WESUPPixelInference.forward_batch`` (mind its memory: ~3.6 GB per 464 x 464 window), class 1 of every window kept on
     the device, one ``ops.window_merge`` of the probabilities and one copy to the host (the caller rounds)."""
@@ -222,7 +237,7 @@ def pixel_predict_array_batched(model, img, patch_size, batch=2, device='cuda'):
     H, W = img.shape[:2]
     tops, lefts = window_grid(H, W, p)
     passes, batch = window_batches(len(tops) * len(lefts), batch)
-    img_d = _upload(img, device)
+    img_d = _upload(img, device, stain)
     kept = torch.empty(len(tops) * len(lefts), p, p, 1, dtype=torch.float32, device=img_d.device)
     x = torch.empty(batch, 3, p, p, dtype=torch.float32, device=img_d.device)
     with torch.no_grad():
@@ -234,7 +249,7 @@ def pixel_predict_array_batched(model, img, patch_size, batch=2, device='cuda'):
     return merged.view(H, W).cpu().numpy()
 
 
-def predict_array_classes_batched(trainer, img, patch_size, batch=4, device='cuda'):
+def predict_array_classes_batched(trainer, img, patch_size, batch=4, device='cuda', stain=None):
     """``predict_array_classes`` with the image resident on the device (``predict_array_batched`` for C > 2): the painted class
     indices of all windows kept in one (N, p, p) device buffer, one ``ops.window_merge_classes(votes=True)`` and ONE copy of the
     (H, W) uint8 map to the host.  Equal to ``predict_array_classes`` bit for bit at ``batch=1``."""
@@ -242,7 +257,7 @@ def predict_array_classes_batched(trainer, img, patch_size, batch=4, device='cud
     H, W = img.shape[:2]
     tops, lefts = window_grid(H, W, p)
     passes, batch = window_batches(len(tops) * len(lefts), batch)
-    img_d = _upload(img, device)
+    img_d = _upload(img, device, stain)
     kept = torch.empty(len(tops) * len(lefts), p, p, dtype=torch.float32, device=img_d.device)
     x = torch.empty(batch, 3, p, p, dtype=torch.float32, device=img_d.device)
     with torch.no_grad():
@@ -256,7 +271,7 @@ def predict_array_classes_batched(trainer, img, patch_size, batch=4, device='cud
     return merged
 
 
-def pixel_predict_array_classes_batched(model, img, patch_size, batch=2, device='cuda'):
+def pixel_predict_array_classes_batched(model, img, patch_size, batch=2, device='cuda', stain=None):
     """``pixel_predict_array_classes`` with the image resident on the device: the (p, p, C) probabilities of every window kept on
     the device, one ``ops.window_merge_classes`` (the fp64 means per class live in registers: no (H, W, C) tensor) and one copy
     of the (H, W) uint8 map to the host."""
@@ -265,7 +280,7 @@ def pixel_predict_array_classes_batched(model, img, patch_size, batch=2, device=
     C = _n_classes(model)
     tops, lefts = window_grid(H, W, p)
     passes, batch = window_batches(len(tops) * len(lefts), batch)
-    img_d = _upload(img, device)
+    img_d = _upload(img, device, stain)
     kept = torch.empty(len(tops) * len(lefts), p, p, C, dtype=torch.float32, device=img_d.device)
     x = torch.empty(batch, 3, p, p, dtype=torch.float32, device=img_d.device)
     with torch.no_grad():
@@ -276,18 +291,19 @@ def pixel_predict_array_classes_batched(model, img, patch_size, batch=2, device=
     return merged.cpu().numpy()
 
 
-def predict(trainer, img_path, patch_size, device='cuda', batch=None):
+def predict(trainer, img_path, patch_size, device='cuda', batch=None, stain=None):
     """One image file -> (H, W) map; ``batch=None`` is the per-window path, a number the device-resident one.  A model of more
     than two classes gives the uint8 class map of the ``_classes`` forms."""
     from PIL import Image
     img = np.asarray(Image.open(img_path).convert('RGB'))
+    kw = {} if stain is None else {'stain': stain}          # (--stain-normalize: fitted once per image, applied on the device)
     if _n_classes(getattr(trainer, 'model', None)) > 2:
         if batch is None:
-            return predict_array_classes(trainer, img, patch_size, device=device)
-        return predict_array_classes_batched(trainer, img, patch_size, batch=batch, device=device)
+            return predict_array_classes(trainer, img, patch_size, device=device, **kw)
+        return predict_array_classes_batched(trainer, img, patch_size, batch=batch, device=device, **kw)
     if batch is None:
-        return predict_array(trainer, img, patch_size, device=device)
-    return predict_array_batched(trainer, img, patch_size, batch=batch, device=device)
+        return predict_array(trainer, img, patch_size, device=device, **kw)
+    return predict_array_batched(trainer, img, patch_size, batch=batch, device=device, **kw)
 
 
 def save_predictions(predictions, img_paths, output_dir='predictions', n_classes=2):
@@ -304,18 +320,18 @@ def save_predictions(predictions, img_paths, output_dir='predictions', n_classes
             Image.fromarray(pred.astype('uint8')).save(output_dir / Path(img_path).with_suffix('.png').name, format='PNG')
 
 
-def infer(trainer, data_dir, patch_size, output_dir=None, device='cuda', batch=None):
+def infer(trainer, data_dir, patch_size, output_dir=None, device='cuda', batch=None, stain=None):
     """Window-based inference on ``data_dir/images`` (infer_tile.py:143-162)."""
     trainer.model.eval()
     data_dir = Path(data_dir).expanduser()
     img_paths = sorted((data_dir / 'images').iterdir())
-    predictions = [predict(trainer, p, patch_size, device=device, batch=batch) for p in img_paths]
+    predictions = [predict(trainer, p, patch_size, device=device, batch=batch, **({} if stain is None else {'stain': stain})) for p in img_paths]
     if output_dir is not None:
         save_predictions(predictions, img_paths, output_dir, n_classes=_n_classes(trainer.model))
     return predictions
 
 
-def pixel_infer(model, data_dir, patch_size, output_dir=None, device='cuda', batch=None):
+def pixel_infer(model, data_dir, patch_size, output_dir=None, device='cuda', batch=None, stain=None):
     """Pixel-wise window inference on ``data_dir/images`` (pixel_infer_tile.py:41-60): the merged class-1 probabilities are
     rounded here, before they are saved.  A model of more than two classes gives class maps."""
     from PIL import Image
@@ -324,18 +340,19 @@ def pixel_infer(model, data_dir, patch_size, output_dir=None, device='cuda', bat
     img_paths = sorted((data_dir / 'images').iterdir())
     predictions = []
     C = _n_classes(model)
+    kw = {} if stain is None else {'stain': stain}
     for path in img_paths:
         img = np.asarray(Image.open(path).convert('RGB'))
         if C > 2:
             if batch is None:
-                predictions.append(pixel_predict_array_classes(model, img, patch_size, device=device))
+                predictions.append(pixel_predict_array_classes(model, img, patch_size, device=device, **kw))
             else:
-                predictions.append(pixel_predict_array_classes_batched(model, img, patch_size, batch=batch, device=device))
+                predictions.append(pixel_predict_array_classes_batched(model, img, patch_size, batch=batch, device=device, **kw))
             continue
         if batch is None:
-            merged = pixel_predict_array(model, img, patch_size, device=device)
+            merged = pixel_predict_array(model, img, patch_size, device=device, **kw)
         else:
-            merged = pixel_predict_array_batched(model, img, patch_size, batch=batch, device=device)
+            merged = pixel_predict_array_batched(model, img, patch_size, batch=batch, device=device, **kw)
         predictions.append(merged.round())
     if output_dir is not None:
         save_predictions(predictions, img_paths, output_dir, n_classes=C)
@@ -364,7 +381,7 @@ def _load_pixel_model(checkpoint, device, multiclass=False):
     return model
 
 
-def main(argv=None):
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     ap.add_argument('data_dir')
     ap.add_argument('--model-type', default='wesup')
@@ -376,7 +393,17 @@ def main(argv=None):
                     help='windows per pass of the device-resident path (default: the per-window path)')
     ap.add_argument('--pixel', action='store_true',
                     help='pixel-wise inference with WESUPPixelInference (pixel_infer_tile.py)')
-    a = ap.parse_args(argv)
+    from .stain import add_argument
+    add_argument(ap)
+    return ap.parse_args(argv)
+
+
+def main(argv=None):
+    a = parse_args(argv)
+    kw = {}
+    if a.stain_normalize is not None:                # --stain-normalize [TARGET]: off by default, nothing of it is touched
+        from .stain import make_normalizer
+        kw['stain'] = make_normalizer(a.stain_normalize, a.device)
     output_dir = a.output_dir
     if output_dir is None and a.checkpoint is not None:
         output_dir = Path(a.checkpoint).expanduser().parent.parent / 'results'
@@ -385,7 +412,7 @@ def main(argv=None):
             model = _load_pixel_model(None, a.device)
         else:
             model = _load_pixel_model(a.checkpoint, a.device, multiclass=True)
-        pixel_infer(model, a.data_dir, a.patch_size, output_dir, device=a.device, batch=a.batch)
+        pixel_infer(model, a.data_dir, a.patch_size, output_dir, device=a.device, batch=a.batch, **kw)
         return
     if a.checkpoint is None:
         trainer = initialize_trainer(a.model_type, device=a.device)
@@ -393,7 +420,7 @@ def main(argv=None):
         from .models import checkpoint_n_classes
         trainer = initialize_trainer(a.model_type, device=a.device, n_classes=checkpoint_n_classes(a.checkpoint))
         trainer.load_checkpoint(a.checkpoint)
-    infer(trainer, a.data_dir, a.patch_size, output_dir, device=a.device, batch=a.batch)
+    infer(trainer, a.data_dir, a.patch_size, output_dir, device=a.device, batch=a.batch, **kw)
 
 
 if __name__ == '__main__':

@@ -384,12 +384,21 @@ class BaseTrainer(ABC):
         # datasets read from disk hand out raw uint8 items: H2D through pinned memory one batch ahead, augmentation /
         # ToTensor / one-hot on the GPU (utils/data.py: DevicePrefetcher)
         from ..utils import data as D
+        stain = None
+        if self.kwargs.get('stain_normalize') not in (None, False):          # off by default: nothing of wesup_amd.stain is touched
+            from ..stain import make_normalizer
+            stain = make_normalizer(self.kwargs.get('stain_normalize'), self.device)
         for phase, ds in (('train', train_dataset), ('val', val_dataset if has_val else None)):
             if isinstance(ds, D.SegmentationDataset):
                 self.dataloaders[phase] = D.DevicePrefetcher(
                     self.dataloaders[phase], self.device, train=(phase == 'train'),
                     with_points=isinstance(ds, D.PointSupervisionDataset), has_masks=ds.mask_paths is not None,
-                    n_classes=ds.n_classes, seed=self.rank, segment_fn=self.prefetch_segment_fn())
+                    n_classes=ds.n_classes, seed=self.rank, segment_fn=self.prefetch_segment_fn(), stain=stain,
+                    stain_jitter=float(self.kwargs.get('stain_jitter') or 0.0) if phase == 'train' else 0.0)
+        if (stain is not None or self.kwargs.get('stain_jitter')) and not isinstance(self.dataloaders['train'], D.DevicePrefetcher):
+            # (the prefetcher is what applies them: a dataset it does not wrap, e.g. 'synthetic:', would train on as if they were off)
+            raise ValueError(f'stain_normalize / stain_jitter need raw uint8 items staged by DevicePrefetcher; '
+                             f'{type(train_dataset).__name__} is not one of its datasets')
 
         self.logger.info(underline('\nTraining Stage', '='))
         self.metric_funcs = self.kwargs.get('metrics')

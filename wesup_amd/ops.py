@@ -1635,6 +1635,121 @@ def tsne_iterate(p, y, upd, gains, stats, iters, exaggeration=1.0, momentum=0.8,
     return y
 
 
+# ---------------------------------------------------------------- stain normalisation and stain jitter (csrc/stain.hip)
+STAIN_BLOCK = _lib.STAIN_BLOCK
+STAIN_IO, STAIN_ALPHA, STAIN_BETA, STAIN_MIN_TISSUE = 240.0, 1.0, 0.15, 16
+STAIN_MAX_SAMPLES = 1 << 24        # samples of one fit: n_tissue travels as a float
+_stain_ws = {}                     # (device, stream) -> grow-only byte buffer
+
+
+def _stain_workspace(nbytes, device):
+    """The stain entries' scratch, one per stream (the prefetcher's copy stream runs beside the step).  Apart from ``workspace()``
+    on purpose: no recorded step plan holds one of these addresses, so a growth -- every new largest shape under multi-scale
+    training -- must not bump ``ws_generation`` and drop the plans.  A replaced buffer goes back to torch's allocator, which
+    orders its reuse behind the kernels queued on the stream it was allocated on: this one."""
+    key = (str(device), torch.cuda.current_stream().cuda_stream)
+    buf = _stain_ws.get(key)
+    if buf is None or buf.numel() < nbytes:
+        _stain_ws.pop(key, None)
+        buf = _stain_ws[key] = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
+    return buf
+
+
+def select_f32(keys, ranks, out=None):
+    """keys (n,) fp32, ranks (r,) int64 ON THE DEVICE, r <= 4 -> (r,) fp32: np.sort(keys)[ranks], bit for bit, without a
+    read-back.  A rank outside [0, n) is taken to the nearest end."""
+    _chk(keys, name='keys'); _chk(ranks, torch.int64, 'ranks')
+    n, r = keys.numel(), ranks.numel()
+    if keys.dim() != 1 or ranks.dim() != 1 or n < 1 or not 1 <= r <= _lib.SELECT_MAX_RANKS or ranks.device != keys.device:
+        raise _lib.WesupHipError(f'select_f32: keys {tuple(keys.shape)}, ranks {tuple(ranks.shape)} (1 .. {_lib.SELECT_MAX_RANKS} ranks)')
+    out = torch.empty(r, dtype=torch.float32, device=keys.device) if out is None else _chk(out, name='out')
+    if out.numel() != r or out.device != keys.device:
+        raise _lib.WesupHipError(f'select_f32: out {tuple(out.shape)} for {r} ranks')
+    nb = _lib.load().wesup_select_f32_workspace_bytes(n)
+    ws = _stain_workspace(nb, keys.device)
+    _lib.call('wesup_select_f32', _p(keys), n, _p(ranks), r, _p(out), _p(ws), nb, _stream())
+    return out
+
+
+def stain_stride(H, W):
+    """The smallest sampling stride that keeps a fit at or below 2^24 samples."""
+    s = 1
+    while -(-H // s) * -(-W // s) > STAIN_MAX_SAMPLES:
+        s += 1
+    return s
+
+
+def _stain_images(img, name):
+    _chk(img, torch.uint8, name)
+    if img.dim() == 3:
+        img = img[None]
+    if img.dim() != 4 or img.shape[-1] != 3 or img.numel() == 0:
+        raise _lib.WesupHipError(f'{name}: expected (H, W, 3) or (B, H, W, 3) uint8, got {tuple(img.shape)}')
+    return img
+
+
+def stain_fit(img, stride=None, io=STAIN_IO, alpha=STAIN_ALPHA, beta=STAIN_BETA, min_tissue=STAIN_MIN_TISSUE, blocks=None,
+              return_stages=False):
+    """img (B, H, W, 3) or (H, W, 3) uint8 -> (B, 16) fp32 fit blocks {HE[3][2], pinv[2][3], maxC[2], n_tissue, valid}: one chain of
+    launches, nothing read back.  ``stride`` None picks stain_stride(H, W).  ``return_stages`` also returns views of the
+    workspace, valid until the next stain call on this stream: moments (B, 10) fp64, eig (B, 3, 2) fp64, phi (B, n) fp32 (+inf where
+    a sample is not tissue), conc (B, 2, n) fp32."""
+    img = _stain_images(img, 'stain_fit: img')
+    B, H, W, _ = img.shape
+    stride = stain_stride(H, W) if stride is None else int(stride)
+    if stride < 1 or -(-H // stride) * -(-W // stride) > STAIN_MAX_SAMPLES:
+        raise _lib.WesupHipError(f'stain_fit: stride {stride} for {H} x {W} (at most 2^24 samples)')
+    blocks = torch.empty(B, STAIN_BLOCK, dtype=torch.float32, device=img.device) if blocks is None else _chk(blocks, name='blocks')
+    if tuple(blocks.shape) != (B, STAIN_BLOCK) or blocks.device != img.device:
+        raise _lib.WesupHipError(f'stain_fit: blocks {tuple(blocks.shape)} for {B} images')
+    lib = _lib.load()
+    nb = lib.wesup_stain_fit_workspace_bytes(B, H, W, stride)
+    ws = _stain_workspace(nb, img.device)
+    _lib.call('wesup_stain_fit', _p(img), _p(blocks), B, H, W, stride, float(io), float(alpha), float(beta), int(min_tissue),
+              _p(ws), nb, _stream())
+    if not return_stages:
+        return blocks
+    n = -(-H // stride) * -(-W // stride)
+    off = [lib.wesup_stain_fit_stage_offset(B, H, W, stride, s) for s in range(4)]
+    stages = {
+        'moments': ws[off[0]:off[0] + B * 80].view(torch.float64).view(B, 10),
+        'eig': ws[off[1]:off[1] + B * 256].view(torch.float64).view(B, 32)[:, :6].reshape(B, 3, 2),
+        'phi': ws[off[2]:off[2] + B * n * 4].view(torch.float32).view(B, n),
+        'conc': ws[off[3]:off[3] + B * 2 * n * 4].view(torch.float32).view(B, 2, n),
+    }
+    return blocks, stages
+
+
+def stain_apply(img, src_blocks, dst_blocks, jitter=None, keep_residual=0.0, io=STAIN_IO, out=None):
+    """c = pinv_s OD;  c' = c (maxC_d / maxC_s) a + b;  OD' = HE_d c' + keep_residual (OD - HE_s c);  uint8 again.  src_blocks
+    (B, 16); dst_blocks (16,) or (1, 16) for one target, (B, 16) for one each; jitter (B, 4) fp32 {a_H, b_H, a_E, b_E} or None;
+    ``out`` may be ``img`` (in place).  An invalid fit on either side makes that image a copy."""
+    squeeze = isinstance(img, torch.Tensor) and img.dim() == 3
+    img = _stain_images(img, 'stain_apply: img')
+    B, H, W, _ = img.shape
+    dev = img.device
+    _chk(src_blocks, name='src_blocks'); _chk(dst_blocks, name='dst_blocks')
+    dst_rows = dst_blocks.numel() // STAIN_BLOCK
+    if src_blocks.numel() != B * STAIN_BLOCK or dst_blocks.numel() != dst_rows * STAIN_BLOCK or dst_rows not in (1, B) \
+            or src_blocks.device != dev or dst_blocks.device != dev:
+        raise _lib.WesupHipError(f'stain_apply: src_blocks {tuple(src_blocks.shape)}, dst_blocks {tuple(dst_blocks.shape)} for {B} images')
+    dst_stride = STAIN_BLOCK if dst_rows > 1 else 0
+    if jitter is not None:
+        _chk(jitter, name='jitter')
+        if tuple(jitter.shape) != (B, 4) or jitter.device != dev:
+            raise _lib.WesupHipError(f'stain_apply: jitter {tuple(jitter.shape)} for {B} images')
+    if out is None:
+        out = torch.empty_like(img)
+    else:
+        o4 = _stain_images(out, 'stain_apply: out')
+        if o4.shape != img.shape or o4.device != dev:
+            raise _lib.WesupHipError(f'stain_apply: out {tuple(out.shape)} for img {tuple(img.shape)}')
+        out = o4
+    _lib.call('wesup_stain_apply', _p(img), _p(out), _p(src_blocks), _p(dst_blocks), dst_stride, _p(jitter), float(keep_residual),
+              B, H, W, float(io), _stream())
+    return out[0] if squeeze else out
+
+
 # ---------------------------------------------------------------- window inference on large images (csrc/tiles.hip)
 _lattice_cache = {}    # (device, axis positions) -> int32 device tensor: an image size meets the same few lattices again and again
 

@@ -54,14 +54,14 @@ def image_paths(data_root):
     return sorted((Path(data_root).expanduser() / 'images').iterdir())
 
 
-def pixel_predict(model, img_u8_hwc, scales=(0.5,), device='cuda', full_maps=False):
+def pixel_predict(model, img_u8_hwc, scales=(0.5,), device='cuda', full_maps=False, stain=None):
     """(H, W, 3) uint8 image -> (H, W) fp32 class-1 probability averaged over ``scales`` (pixel_infer.py:40-53; the caller
     rounds).  One upload; per scale the down-resize, the model and the up-resize into the running mean
     (``alpha = 1 / len(scales)``: no pass of its own for the mean); one copy to the host."""
     scales = tuple(scales)
     if not scales:
         raise ValueError('pixel_predict: no scales')
-    img_d = _upload(img_u8_hwc, device)
+    img_d = _upload(img_u8_hwc, device, stain)
     H, W = img_d.shape[:2]
     mean = torch.empty(H, W, dtype=torch.float32, device=img_d.device)
     with torch.no_grad():
@@ -75,14 +75,14 @@ def pixel_predict(model, img_u8_hwc, scales=(0.5,), device='cuda', full_maps=Fal
     return mean.cpu().numpy()
 
 
-def pixel_predict_classes(model, img_u8_hwc, scales=(0.5,), device='cuda', full_maps=False):
+def pixel_predict_classes(model, img_u8_hwc, scales=(0.5,), device='cuda', full_maps=False, stain=None):
     """``pixel_predict`` for a model of more than two classes: (H, W, 3) uint8 image -> (H, W) uint8 class map.  Per scale all C
     probabilities are resized back in one pass into one (H, W, C) running mean (``ops.planes_resize_acc``, every plane the
     arithmetic of ``plane_resize_acc``), then the first maximum per pixel (``ops.class_argmax_u8``) and one copy to the host."""
     scales = tuple(scales)
     if not scales:
         raise ValueError('pixel_predict_classes: no scales')
-    img_d = _upload(img_u8_hwc, device)
+    img_d = _upload(img_u8_hwc, device, stain)
     H, W = img_d.shape[:2]
     mean = torch.empty(H, W, model.n_classes, dtype=torch.float32, device=img_d.device)
     with torch.no_grad():
@@ -97,7 +97,7 @@ def pixel_predict_classes(model, img_u8_hwc, scales=(0.5,), device='cuda', full_
     return classes.cpu().numpy()
 
 
-def main(data_root, checkpoint=None, output_dir=None, scales=(0.5,), device=None, full_maps=False):
+def main(data_root, checkpoint=None, output_dir=None, scales=(0.5,), device=None, full_maps=False, stain_normalize=None):
     """pixel_infer.py:20-56 on ``data_root/images``: one PNG of ``round(mean probability) * 255`` per image -- of the class
     indices for a checkpoint of more than two classes (``pixel_predict_classes``).  Returns the written paths."""
     from PIL import Image
@@ -111,15 +111,19 @@ def main(data_root, checkpoint=None, output_dir=None, scales=(0.5,), device=None
     output_dir.mkdir(parents=True, exist_ok=True)
     model = _load_pixel_model(checkpoint, device, multiclass=True)
     model.eval()
+    kw = {}
+    if stain_normalize not in (None, False):                   # --stain-normalize [TARGET]: one fit per image on the resident tensor
+        from .stain import make_normalizer
+        kw['stain'] = make_normalizer(stain_normalize, device)
     written = []
     for path in image_paths(data_root):
         img = np.asarray(Image.open(path).convert('RGB'))
         out = output_dir / output_name(path.name)
         if model.n_classes > 2:                      # the class indices themselves, no x 255 (infer.save_predictions)
-            Image.fromarray(pixel_predict_classes(model, img, scales, device=device, full_maps=full_maps)).save(out, format='PNG')
+            Image.fromarray(pixel_predict_classes(model, img, scales, device=device, full_maps=full_maps, **kw)).save(out, format='PNG')
             written.append(out)
             continue
-        prob = pixel_predict(model, img, scales, device=device, full_maps=full_maps)
+        prob = pixel_predict(model, img, scales, device=device, full_maps=full_maps, **kw)
         Image.fromarray(prob.round().astype('uint8') * 255).save(out, format='PNG')
         written.append(out)
     return written
@@ -134,6 +138,8 @@ def parse_args(argv=None):
     ap.add_argument('--device', default=None)
     ap.add_argument('--full-maps', action='store_true',
                     help="the shipped forward on the (HW, 2112) feature map instead of the per-resolution one (cross-check)")
+    from .stain import add_argument
+    add_argument(ap)
     a = ap.parse_args(argv)
     a.scale_values = parse_scales(a.scales)
     a.output_dir = Path(a.output).expanduser() if a.output else cli_output_dir(a.checkpoint, a.scales, a.data_root)
@@ -143,7 +149,7 @@ def parse_args(argv=None):
 def cli(argv=None):
     a = parse_args(argv)
     main(a.data_root, checkpoint=a.checkpoint, output_dir=a.output_dir, scales=a.scale_values, device=a.device,
-         full_maps=a.full_maps)
+         full_maps=a.full_maps, **({} if a.stain_normalize is None else {'stain_normalize': a.stain_normalize}))
 
 
 if __name__ == '__main__':

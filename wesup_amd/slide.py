@@ -113,13 +113,17 @@ def compute_metrics(predictions, gts, negative=False, log=print, device=None):
 
 
 # ------------------------------------------------------------------------------------------------ device-resident path
-def _resident(img_u8, device):
+def _resident(img_u8, device, stain=None):
+    """``stain`` (wesup_amd.stain.StainNormalizer): one strided fit of the whole slide and one pass over it, in place on the
+    uploaded tensor (a tensor the caller owns is normalised into a copy); an invalid fit -- empty glass, the near-white
+    ``negative-*`` slides -- leaves the slide as it is."""
     if isinstance(img_u8, torch.Tensor) and img_u8.is_cuda:
-        return img_u8
-    return _upload(img_u8, device)
+        return img_u8 if stain is None else stain(img_u8)
+    return _upload(img_u8, device, stain)
 
 
-def slide_predict(trainer, img_u8, patch_size=PATCH_SIZE, input_size=INPUT_SIZE, batch=4, device='cuda', keep_on_device=False):
+def slide_predict(trainer, img_u8, patch_size=PATCH_SIZE, input_size=INPUT_SIZE, batch=4, device='cuda', keep_on_device=False,
+                  stain=None):
     """Superpixel prediction of a whole (H, W, 3) uint8 slide -> (H, W) uint8 map in {0, 255}: what the reference gets from
     ``split_patches`` -> ``infer(input_size=...)`` -> ``combine_single``, with the slide resident on the device.  One upload;
     per pass of ``batch`` patches ``ops.patch_gather_resize`` -> ``trainer.preprocess`` (batched GPU SLIC) -> ``trainer.model``
@@ -129,7 +133,7 @@ def slide_predict(trainer, img_u8, patch_size=PATCH_SIZE, input_size=INPUT_SIZE,
     gives the (H, W) uint8 map of class indices (``ops.patch_scatter_classes_u8``)."""
     p = int(patch_size)
     h, w = (int(s) for s in input_size)
-    img_d = _resident(img_u8, device)
+    img_d = _resident(img_u8, device, stain)
     H, W = img_d.shape[:2]
     n_h, n_w = patch_grid(H, W, p)
     passes, batch = window_batches(n_h * n_w, batch)
@@ -151,7 +155,8 @@ def slide_predict(trainer, img_u8, patch_size=PATCH_SIZE, input_size=INPUT_SIZE,
     return result
 
 
-def slide_pixel_predict(model, img_u8, patch_size=PATCH_SIZE, scale=PIXEL_SCALE, batch=2, device='cuda', keep_on_device=False):
+def slide_pixel_predict(model, img_u8, patch_size=PATCH_SIZE, scale=PIXEL_SCALE, batch=2, device='cuda', keep_on_device=False,
+                        stain=None):
     """Pixel-wise prediction of a whole slide -> (H, W) uint8 map in {0, 255}: ``pixel_infer`` with ``scales=(scale,)`` on every
     zero-padded patch, pasted and cropped.  Per pass ``ops.patch_gather_resize(align_corners=True)`` to
     ``pixel_infer.target_size`` -> ``model.forward_per_resolution`` -> ``ops.patch_scatter_u8`` reading class 1 in place
@@ -161,7 +166,7 @@ def slide_pixel_predict(model, img_u8, patch_size=PATCH_SIZE, scale=PIXEL_SCALE,
     h, w = target_size(p, p, scale)
     if h < 1 or w < 1:
         raise ValueError(f'scale {scale} leaves nothing of a {p} x {p} patch')
-    img_d = _resident(img_u8, device)
+    img_d = _resident(img_u8, device, stain)
     H, W = img_d.shape[:2]
     n_h, n_w = patch_grid(H, W, p)
     passes, batch = window_batches(n_h * n_w, batch)
@@ -288,7 +293,7 @@ def score_directory(output_dir, gt_dir, log=print, device=None, n_classes=2):
 
 
 def main(data_root, checkpoint, model_type='wesup', pixel=False, patch_size=PATCH_SIZE, skip_infer=False, device=None, batch=None,
-         post_threshold=None, log=print):
+         post_threshold=None, log=print, stain_normalize=None):
     """test_dp2019_pipeline.py:114-219 without its patch files: predict every slide of ``data_root/images/*.jpg`` (unless
     ``skip_infer``), write the combined PNGs, score them against ``data_root/masks``.  Returns ``score_directory``'s result.
 
@@ -320,12 +325,16 @@ def main(data_root, checkpoint, model_type='wesup', pixel=False, patch_size=PATC
             trainer = initialize_trainer(model_type, device=device, n_classes=C)
             trainer.load_checkpoint(checkpoint)
             trainer.model.eval()
+        kw = {}
+        if stain_normalize not in (None, False):               # --stain-normalize [TARGET]: off by default
+            from .stain import make_normalizer
+            kw['stain'] = make_normalizer(stain_normalize, device)
         for path in sorted((data_root / 'images').glob('*.jpg')):
             img = np.asarray(Image.open(path).convert('RGB'))
             if pixel:
-                combined = slide_pixel_predict(model, img, patch_size, PIXEL_SCALE, batch=batch or 2, device=device)
+                combined = slide_pixel_predict(model, img, patch_size, PIXEL_SCALE, batch=batch or 2, device=device, **kw)
             else:
-                combined = slide_predict(trainer, img, patch_size, INPUT_SIZE, batch=batch or 4, device=device)
+                combined = slide_predict(trainer, img, patch_size, INPUT_SIZE, batch=batch or 4, device=device, **kw)
             if post_threshold is not None:
                 combined = postprocess(combined, post_threshold, device)
             Image.fromarray(combined).save(output_dir / f'{path.stem}.png', format='PNG')
@@ -345,13 +354,16 @@ def parse_args(argv=None):
     ap.add_argument('--batch', type=int, default=None, help='patches per pass (default: 4, with --pixel 2)')
     ap.add_argument('--post-threshold', type=int, default=None,
                     help='remove regions and fill holes smaller than this many pixels (the reference never does)')
+    from .stain import add_argument
+    add_argument(ap)
     return ap.parse_args(argv)
 
 
 def cli(argv=None):
     a = parse_args(argv)
     return main(a.data_root, a.checkpoint, model_type=a.model, pixel=a.pixel, patch_size=a.patch_size, skip_infer=a.skip_infer,
-                device=a.device, batch=a.batch, post_threshold=a.post_threshold)
+                device=a.device, batch=a.batch, post_threshold=a.post_threshold,
+                **({} if a.stain_normalize is None else {'stain_normalize': a.stain_normalize}))
 
 
 if __name__ == '__main__':

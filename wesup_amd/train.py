@@ -3,6 +3,10 @@
   python -m wesup_amd.train synthetic:480:480:24:16 --epochs 1 --batch_size 4 [--smoke] [--challenge-metrics]
   python -m wesup_amd.train DATA --optimizer adam --lr 1e-4 --lr_scheduler plateau     (sgd | adam | adamw, also --betas (0.9,0.999)
                                                                                         --adam_eps 1e-8; defaults: sgd, 5e-5, no scheduler)
+  python -m wesup_amd.train DATA --stain-normalize [TARGET] --stain-jitter 0.1         (Macenko normalisation of every batch on the
+                                                                                        device, to the default target or to TARGET's
+                                                                                        stains; jitter of the two stain concentrations
+                                                                                        while training; both off by default)
 """
 import argparse
 import logging

@@ -395,22 +395,45 @@ class LabelMaps:
         self.labels, self.counts = labels, counts
 
 
+def stain_jitter_generator(seed):
+    """The generator of the stain jitter rows: derived from the prefetcher's seed, apart from its ``rs``."""
+    return np.random.RandomState((int(seed) + 0x57A1) % (1 << 32))
+
+
+def sample_stain_jitter(rs, sigma, B):
+    """(B, 4) fp32 rows {a_H, b_H, a_E, b_E}: a ~ U(1 - sigma, 1 + sigma), b ~ U(-sigma, sigma), drawn image by image in that order."""
+    rows = np.empty((B, 4), dtype=np.float32)
+    for b in range(B):
+        for k in range(2):
+            rows[b, 2 * k] = rs.uniform(1.0 - sigma, 1.0 + sigma)
+            rows[b, 2 * k + 1] = rs.uniform(-sigma, sigma)
+    return rows
+
+
 class DevicePrefetcher:
     """Wraps a DataLoader over raw items: pinned staging + asynchronous H2D on a copy stream one batch ahead,
     augmentation / ToTensor / one-hot / point rasterisation on the GPU.  Yields the trainer's data tuple
     ``(img, pixel_mask, point_mask)`` (or ``(img, pixel_mask)`` for mask datasets)."""
 
     def __init__(self, loader, device, train=True, with_points=True, has_masks=True, n_classes=2, seed=0,
-                 segment_fn=None):
+                 segment_fn=None, stain=None, stain_jitter=0.0):
         """``segment_fn(img (B,3,H,W) float on the device) -> ((B,H,W) int32 label maps, (B,) int32 counts)``: when
         given, the superpixel segmentation of the NEXT batch also runs on the copy stream, beside the training step of
         the current one; its counts are copied to pinned host memory behind it, so that when the batch is consumed they
         are plain integers (exact row count, no host sync in the step) and the label maps travel as a ``LabelMaps``
-        fourth element of the data tuple (WESUPTrainer.preprocess takes it)."""
+        fourth element of the data tuple (WESUPTrainer.preprocess takes it).
+
+        ``stain`` (a wesup_amd.stain.StainNormalizer on this device) and ``stain_jitter`` (sigma > 0) normalise and then jitter the
+        stains of the uploaded uint8 batch on the copy stream, in front of everything else (wesup_amd/stain.py).  The jitter rows
+        come from a generator of their own (``stain_rs``): ``rs`` draws the same stream whether the feature is on or off."""
         self.loader, self.device, self.train = loader, torch.device(device), train
         self.with_points, self.has_masks, self.n_classes = with_points, has_masks, n_classes
         self.segment_fn = segment_fn
+        self.stain, self.stain_jitter = stain, float(stain_jitter)
+        if self.stain_jitter < 0 or self.stain_jitter >= 1:
+            raise ValueError(f'DevicePrefetcher: stain_jitter {stain_jitter}, expected 0 <= sigma < 1')
         self.rs = np.random.RandomState(seed)
+        self.stain_rs = stain_jitter_generator(seed)
         self.copy_stream = torch.cuda.Stream(device=self.device)
 
     def __len__(self):
@@ -452,6 +475,12 @@ class DevicePrefetcher:
             d_img = img.pin_memory().to(self.device, non_blocking=True)
             d_mask = mask.pin_memory().to(self.device, non_blocking=True) if self.has_masks else None
             d_par = params.pin_memory().to(self.device, non_blocking=True)
+            if self.stain is not None:
+                d_img = self.stain(d_img, out=d_img)
+            if self.stain_jitter > 0:
+                from ..stain import stain_jitter
+                jit = torch.from_numpy(sample_stain_jitter(self.stain_rs, self.stain_jitter, B))
+                d_img = stain_jitter(d_img, jit.pin_memory().to(self.device, non_blocking=True), out=d_img)
             if need_app:
                 d_img = ops.appearance(d_img, torch.from_numpy(app).pin_memory().to(self.device, non_blocking=True))
             d_el = None
