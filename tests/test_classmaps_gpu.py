@@ -346,8 +346,7 @@ def _top_two_gap(p):
     return (top[..., 0] - top[..., 1]).cpu().numpy()
 
 
-@pytest.fixture(scope='module')
-def trainer3():
+def _trainer3():
     """The three-class superpixel trainer (sp_area 64), biases shifted by the medians over the superpixels of window 0 of the
     150 x 333 image."""
     from wesup_amd import infer_tile as T
@@ -367,6 +366,11 @@ def trainer3():
     return trainer
 
 
+@pytest.fixture(scope='module')
+def trainer3():
+    return _trainer3()
+
+
 def _pixel_model(x0):
     """The three-class pixel-wise model, biases shifted by the medians over the pixels of the network input ``x0`` (1,3,h,w)."""
     from wesup_amd.models.wesup import WESUPPixelInference
@@ -380,11 +384,15 @@ def _pixel_model(x0):
     return model
 
 
-@pytest.fixture(scope='module')
-def pixel3():
+def _pixel3():
     """The pixel-wise model whose shifts come from window 0 of the 150 x 333 image."""
     from wesup_amd import infer_tile as T
     return _pixel_model(T._to_tensor(T.divide_image_to_patches(_image(IMAGE_SEED, 150, 333), 64)[0], DEV))
+
+
+@pytest.fixture(scope='module')
+def pixel3():
+    return _pixel3()
 
 
 def _sp_window_run(trainer, x):
@@ -611,3 +619,65 @@ def test_two_class_paths_call_none_of_the_new_entries(monkeypatch):
     assert set(np.unique(d)) <= {0, 255} and set(np.unique(e)) <= {0, 255}
     assert 'wesup_window_merge' in names and 'wesup_plane_resize_acc' in names and 'wesup_patch_scatter_u8' in names
     assert not set(names) & set(ENTRIES), sorted(set(names) & set(ENTRIES))
+
+
+# -------------------------------------------------------------------- 13. the launch sequence around the network is the recorded one
+# the entries of tiles.hip, pixel.hip, slide.hip and classmap.hip, and the device copy that keeps a pass
+INFERENCE_ENTRIES = ['wesup_window_gather', 'wesup_window_merge', 'wesup_image_resize_u8', 'wesup_plane_resize_acc',
+                     'wesup_pixel_gather_fwd', 'wesup_patch_gather_resize', 'wesup_patch_scatter_u8', 'wesup_mask_scores',
+                     'wesup_copy'] + ENTRIES
+INFERENCE_CALLS = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'inference_calls.json')
+
+
+def _inference_calls(trainer3, pixel3):
+    """driver -> the ordered names of its ``_lib.call``s among INFERENCE_ENTRIES, for the nine device-resident drivers on test 12's
+    image, patch, batch, input size and scales (tools/make_inference_calls_golden.py writes them to INFERENCE_CALLS)."""
+    from oracle import wesup_oracle as orc
+    from wesup_amd import _lib
+    from wesup_amd import infer_tile as T
+    from wesup_amd import pixel_infer as PI
+    from wesup_amd import slide as S
+    from wesup_amd.models import initialize_trainer
+    from wesup_amd.models.wesup import WESUPPixelInference
+    weights = orc.make_weights(WEIGHT_SEED, feat_scale=FEAT_SCALE)
+    trainer = initialize_trainer('wesup', device=DEV, sp_area=64)
+    _load(trainer.model, weights)
+    model = WESUPPixelInference().to(DEV)
+    _load(model, weights)
+    img = _image(IMAGE_SEED, 80, 112)
+    drivers = {
+        'predict_array_batched': lambda: T.predict_array_batched(trainer, img, 64, batch=2, device=DEV),
+        'pixel_predict_array_batched': lambda: T.pixel_predict_array_batched(model, img, 64, batch=2, device=DEV),
+        'predict_array_classes_batched': lambda: T.predict_array_classes_batched(trainer3, img, 64, batch=2, device=DEV),
+        'pixel_predict_array_classes_batched': lambda: T.pixel_predict_array_classes_batched(pixel3, img, 64, batch=2, device=DEV),
+        'pixel_predict': lambda: PI.pixel_predict(model, img, (0.5, 1.0), device=DEV),
+        'pixel_predict_classes': lambda: PI.pixel_predict_classes(pixel3, img, (0.5, 1.0), device=DEV),
+        'slide_predict, C = 2': lambda: S.slide_predict(trainer, img, 64, (48, 40), batch=2, device=DEV),
+        'slide_predict, C = 3': lambda: S.slide_predict(trainer3, img, 64, (48, 40), batch=2, device=DEV),
+        'slide_pixel_predict': lambda: S.slide_pixel_predict(model, img, 64, 0.6, batch=2, device=DEV),
+    }
+    names, real = [], _lib.call
+
+    def recording(name, *args):
+        names.append(name)
+        return real(name, *args)
+    calls = {}
+    _lib.call = recording
+    try:
+        for driver, run in drivers.items():
+            del names[:]
+            run()
+            calls[driver] = [n for n in names if n in INFERENCE_ENTRIES]
+    finally:
+        _lib.call = real
+    return calls
+
+
+def test_inference_launch_sequences_are_the_recorded_ones(trainer3, pixel3):
+    import json
+    with open(INFERENCE_CALLS) as f:
+        want = json.load(f)
+    got = _inference_calls(trainer3, pixel3)
+    assert sorted(got) == sorted(want) and len(got) == 9
+    for driver, names in got.items():
+        assert names and names == want[driver], (driver, names, want[driver])

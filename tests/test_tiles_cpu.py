@@ -172,3 +172,50 @@ def test_predict_takes_the_per_window_path_by_default(tmp_path):
         assert T.predict('trainer', tmp_path / 'a.png', 8) == 'old' and not new.called
         assert T.predict('trainer', tmp_path / 'a.png', 8, batch=2) == 'new'
     assert new.call_args[1] == {'batch': 2, 'device': 'cuda'} and old.call_count == 1
+
+
+class _Stub:
+    """A model for the per-window forms: a deterministic function of the window tensor, and the class count the forms read."""
+    def __init__(self, fn, n_classes):
+        self.fn, self.n_classes = fn, n_classes
+
+    def __call__(self, x):
+        return self.fn(x)
+
+
+@pytest.mark.parametrize('C', [2, 3])
+def test_per_window_forms_equal_the_composition_written_out(C):
+    """The four per-window forms on the CPU with stub models: each is divide_image_to_patches -> the stub -> its merge.  20 x 27 at
+    patch 8 is a 3 x 4 lattice that overlaps on both axes; the stubs add a ramp over the window, so two windows disagree about a
+    pixel they share and the order of the merge shows."""
+    from types import SimpleNamespace
+    from wesup_amd import infer_tile as T
+    H, W, p = 20, 27, 8
+    assert [len(axis) for axis in T.window_grid(H, W, p)] == [3, 4]
+    img = np.random.RandomState(C).randint(0, 256, (H, W, 3)).astype(np.uint8)
+    ramp = torch.linspace(0., 1., p * p).view(p, p)
+
+    def probabilities(x):                                              # (1, 3, p, p) -> (p, p, C)
+        return torch.softmax(torch.stack([x[0, c] * (c + 1) + ramp * (C - c) for c in range(C)], dim=-1), dim=-1)
+
+    def painted(x):                                                    # what WESUP.forward paints: (1, p, p)
+        return probabilities(x)[..., 1][None] if C == 2 else probabilities(x).argmax(dim=-1).float()[None]
+    pixel = _Stub(probabilities, C)
+    trainer = SimpleNamespace(preprocess=lambda x: (x * 0.5, None), model=_Stub(painted, C), postprocess=torch.round)
+    windows = [T._to_tensor(patch, 'cpu') for patch in T.divide_image_to_patches(img, p)]
+    assert len(windows) == 12
+    with mock.patch.object(T, '_host_windows', wraps=T._host_windows) as walk:
+        if C == 2:
+            sp = T.predict_array(trainer, img, p, device='cpu')
+            px = T.pixel_predict_array(pixel, img, p, device='cpu')
+            want_sp = T.combine_patches_to_image(np.stack([torch.round(painted(x * 0.5))[0].numpy()[..., None] for x in windows]), H, W)
+            want_px = T.combine_patches_to_image(np.stack([probabilities(x).numpy()[..., 1] for x in windows]), H, W)
+        else:
+            sp = T.predict_array_classes(trainer, img, p, device='cpu')
+            px = T.pixel_predict_array_classes(pixel, img, p, device='cpu')
+            want_sp = T.combine_patches_to_classes(np.stack([painted(x * 0.5)[0].numpy() for x in windows]), H, W, C, votes=True)
+            want_px = T.combine_patches_to_classes(np.stack([probabilities(x).numpy() for x in windows]), H, W, C)
+    assert walk.call_count == 2
+    for got, want in ((sp, want_sp), (px, want_px)):
+        assert got.shape == (H, W) and got.dtype == want.dtype and np.array_equal(got, want)
+    assert len(np.unique(want_sp)) > 1 and len(np.unique(want_px)) > 1          # (not one value everywhere)

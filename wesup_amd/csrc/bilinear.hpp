@@ -1,7 +1,8 @@
 // Bilinear interpolation with align_corners=True: the one statement of the source coordinates, shared by every kernel that
 // resamples (spatial.hip: side outputs; pixel.hip: images, probability planes, the per-resolution fc maps; slide.hip: patches).
 // Behind them: the align_corners=False ("half pixel") coordinates of F.interpolate's default, for slide.hip.  At the end of the
-// file: the blend of the four neighbours, in the two forms whose bits results depend on, each rounding written out.
+// file: the blend of the four neighbours, in the two forms whose bits results depend on, and the step into a running mean, each
+// rounding written out.
 #pragma once
 #include "common.hpp"
 
@@ -60,4 +61,16 @@ __device__ __forceinline__ float blend_plane(const Lerp ly, const Lerp lx, float
 #pragma clang fp contract(off)
     const float a = __builtin_fmaf(lx.l1, v01, lx.l0 * v00), b = __builtin_fmaf(lx.l1, v11, lx.l0 * v10);
     return ly.l0 * a + ly.l1 * b;
+}
+// A plane into the running mean over the scales -- out = (accumulate ? out : 0) + alpha * blend_plane: px_plane_resize_kernel
+// (pixel.hip) and every plane of cm_planes_resize_kernel (classmap.hip).  The product by alpha is rounded, and the add onto out is
+// a second rounding: no contraction of the two into one fma.
+__device__ __forceinline__ float blend_plane_times(const Lerp ly, const Lerp lx, float alpha, float v00, float v01, float v10,
+                                                   float v11) {
+#pragma clang fp contract(off)
+    return alpha * blend_plane(ly, lx, v00, v01, v10, v11);
+}
+__device__ __forceinline__ float add_rounded_product(float out, float product) {
+#pragma clang fp contract(off)
+    return out + product;
 }

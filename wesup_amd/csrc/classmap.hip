@@ -1,7 +1,8 @@
 // Class maps for models of more than two classes: the four steps behind the networks of infer_tile.py,
 // pixel_infer.py and slide.py that exist for one plane in tiles.hip, pixel.hip and slide.hip -- the merge over the covering
 // windows, the resize back to the image's size, the paste into the slide-size map and the scoring -- as per-pixel reductions over
-// the C values of a pixel, 2 <= C <= WESUP_MAX_CLASSES.  The two-class kernels stay as they are; nothing here is reached for C = 2
+// the C values of a pixel, 2 <= C <= WESUP_MAX_CLASSES.  The index code and the roundings are the one-plane kernels' own: the
+// lattice walks of lattice.hpp, the blends of bilinear.hpp.  The two-class kernels stay as they are; nothing here is reached for C = 2
 // by the tools.
 //
 // A pixel's class is the FIRST MAXIMUM over ascending c, compared with a strict > (np.argmax on data without NaNs.  No comparison
@@ -38,12 +39,42 @@ __device__ __forceinline__ int first_max(const T (&v)[CMAX], int C) {
     return bi;
 }
 
+// use(c, src[c]) for the C values of a pixel, one contiguous run, in ascending c: float4 per class quad with VEC4 (C % 4 == 0, src
+// 16-byte aligned).  c is a constant once the loop is unrolled, so use may index a register array with it.
+template <int CMAX, bool VEC4, typename Use>
+__device__ __forceinline__ void load_classes(const float* __restrict__ src, int C, Use use) {
+    if constexpr (VEC4) {
+#pragma unroll
+        for (int c = 0; c + 3 < CMAX; c += 4)
+            if (c < C) {
+                const float4 q = ld4(src + c);
+                use(c, q.x);
+                use(c + 1, q.y);
+                use(c + 2, q.z);
+                use(c + 3, q.w);
+            }
+    } else {
+#pragma unroll
+        for (int c = 0; c < CMAX; ++c)
+            if (c < C) use(c, src[c]);
+    }
+}
+
+// the four neighbours of a bilinear sample in an [h][w][C] map: the C values of each are one contiguous run
+struct Corners {
+    const float *p00, *p01, *p10, *p11;
+};
+__device__ __forceinline__ Corners corners_of(const float* in, const Lerp ly, const Lerp lx, int w, int C) {
+    return {in + ((long)ly.i0 * w + lx.i0) * C, in + ((long)ly.i0 * w + lx.i1) * C, in + ((long)ly.i1 * w + lx.i0) * C,
+            in + ((long)ly.i1 * w + lx.i1) * C};
+}
+
 // ---- 1. merge: out[y][x] = first maximum over c of the mean over the covering windows.  One thread per PIXEL: the covering
-// windows are found once (tl_merge_kernel's search), a window's C values are one contiguous run, and the (H, W, C) fp64 tensor
-// is never formed.  VOTES = 0: pred [N][p][p][C] probabilities; per class tl_merge_kernel's arithmetic -- ascending row-major adds
-// onto 0.0 in fp64, one IEEE division by the count -- then the argmax of the quotients (two sums may round to one quotient: the
-// division is not skipped).  VOTES = 1: pred [N][p][p] class indices as floats; integer counts per class (a vote is compared with
-// every c, it never indexes), the first maximum of the counts.
+// windows are found once (covering, lattice.hpp: tl_merge_kernel's search), a window's C values are one contiguous run, and the
+// (H, W, C) fp64 tensor is never formed.  VOTES = 0: pred [N][p][p][C] probabilities; per class tl_merge_kernel's arithmetic --
+// ascending row-major adds onto 0.0 in fp64, one IEEE division by the count -- then the argmax of the quotients (two sums may round
+// to one quotient: the division is not skipped).  VOTES = 1: pred [N][p][p] class indices as floats; integer counts per class (a
+// vote is compared with every c, it never indexes), the first maximum of the counts.
 template <int CMAX, bool VEC4, bool VOTES>
 __global__ __launch_bounds__(CM_BLOCK) void cm_merge_kernel(const float* __restrict__ pred, const int32_t* __restrict__ tops,
                                                             const int32_t* __restrict__ lefts, uint8_t* __restrict__ out,
@@ -52,15 +83,7 @@ __global__ __launch_bounds__(CM_BLOCK) void cm_merge_kernel(const float* __restr
     const long total = (long)H * W;
     for (long idx = (long)blockIdx.x * CM_BLOCK + threadIdx.x; idx < total; idx += (long)gridDim.x * CM_BLOCK) {
         const int y = (int)(idx / W), x = (int)(idx - (long)y * W);
-        int i0 = n_h, i1 = 0, j0 = n_w, j1 = 0;      // [i0, i1) x [j0, j1): the covering windows
-        for (int i = 0; i < n_h; ++i) {
-            const int d = y - tops[i];
-            if (d >= 0 && d < p) { i0 = i < i0 ? i : i0; i1 = i + 1; }
-        }
-        for (int j = 0; j < n_w; ++j) {
-            const int d = x - lefts[j];
-            if (d >= 0 && d < p) { j0 = j < j0 ? j : j0; j1 = j + 1; }
-        }
+        const Covering rows = covering(tops, n_h, y, p), cols = covering(lefts, n_w, x, p);
         double acc[CMAX];
         int votes[CMAX];
 #pragma unroll
@@ -70,10 +93,10 @@ __global__ __launch_bounds__(CM_BLOCK) void cm_merge_kernel(const float* __restr
         }
         int cnt = 0;
         bool bad = false;
-        for (int i = i0; i < i1; ++i) {
+        for (int i = rows.i0; i < rows.i1; ++i) {
             const int dy = y - tops[i];
             if (dy < 0 || dy >= p) continue;         // (an unsorted lattice: never an address outside the window)
-            for (int j = j0; j < j1; ++j) {
+            for (int j = cols.i0; j < cols.i1; ++j) {
                 const int dx = x - lefts[j];
                 if (dx < 0 || dx >= p) continue;
                 const long at = ((long)(i * n_w + j) * p + dy) * p + dx;
@@ -84,22 +107,8 @@ __global__ __launch_bounds__(CM_BLOCK) void cm_merge_kernel(const float* __restr
                         for (int c = 0; c < CMAX; ++c)
                             if (c < C) votes[c] += (v == (float)c) ? 1 : 0;
                     } else bad = true;               // (a NaN lands here too)
-                } else if constexpr (VEC4) {
-                    const float* src = pred + at * C;
-#pragma unroll
-                    for (int c = 0; c + 3 < CMAX; c += 4)
-                        if (c < C) {
-                            const float4 v = ld4(src + c);
-                            acc[c] += (double)v.x;
-                            acc[c + 1] += (double)v.y;
-                            acc[c + 2] += (double)v.z;
-                            acc[c + 3] += (double)v.w;
-                        }
                 } else {
-                    const float* src = pred + at * C;
-#pragma unroll
-                    for (int c = 0; c < CMAX; ++c)
-                        if (c < C) acc[c] += (double)src[c];
+                    load_classes<CMAX, VEC4>(pred + at * C, C, [&](int c, float v) { acc[c] += (double)v; });
                 }
                 ++cnt;
             }
@@ -120,18 +129,10 @@ __global__ __launch_bounds__(CM_BLOCK) void cm_merge_kernel(const float* __restr
 }
 
 // ---- 2. resize: out[Y][X][c] = (accumulate ? out[Y][X][c] : 0) + alpha * bilinear_ac(in[..][..][c])(Y, X), every plane the
-// bits of px_plane_resize_kernel on in[..., c].  One thread per output pixel: the coordinates and the four corner addresses are
-// worked out once, the four corner vectors are read once (float4 per class quad with VEC4) and serve all C planes.
-// The product by alpha and the add onto out are two roundings, as px_plane_resize_kernel is compiled: no contraction of them
-// into one fma here, whatever a compiler would pick.
-__device__ __forceinline__ float cm_resized(const Lerp ly, const Lerp lx, float alpha, float v00, float v01, float v10, float v11) {
-#pragma clang fp contract(off)
-    return alpha * blend_plane(ly, lx, v00, v01, v10, v11);
-}
-__device__ __forceinline__ float cm_added(float o, float v) {
-#pragma clang fp contract(off)
-    return o + v;
-}
+// bits of px_plane_resize_kernel on in[..., c]: the same two functions (blend_plane_times, add_rounded_product: bilinear.hpp) state
+// the product by alpha and the add onto out as two roundings in both kernels.  One thread per output pixel: the coordinates and the
+// four corner addresses are worked out once, the four corner vectors are read once (float4 per class quad with VEC4) and serve
+// all C planes.
 template <int CMAX, bool VEC4>
 __global__ __launch_bounds__(CM_BLOCK) void cm_planes_resize_kernel(const float* __restrict__ in, float* __restrict__ out, int h,
                                                                     int w, int H, int W, int C, float alpha, int accumulate,
@@ -140,21 +141,21 @@ __global__ __launch_bounds__(CM_BLOCK) void cm_planes_resize_kernel(const float*
     for (long idx = (long)blockIdx.x * CM_BLOCK + threadIdx.x; idx < total; idx += (long)gridDim.x * CM_BLOCK) {
         const int Y = (int)(idx / W), X = (int)(idx - (long)Y * W);
         const Lerp ly = lerp_of(Y, sh, h), lx = lerp_of(X, sw, w);
-        const float* p00 = in + ((long)ly.i0 * w + lx.i0) * C;
-        const float* p01 = in + ((long)ly.i0 * w + lx.i1) * C;
-        const float* p10 = in + ((long)ly.i1 * w + lx.i0) * C;
-        const float* p11 = in + ((long)ly.i1 * w + lx.i1) * C;
+        const Corners k = corners_of(in, ly, lx, w, C);
         float* dst = out + idx * C;
         if constexpr (VEC4) {
 #pragma unroll
             for (int c = 0; c + 3 < CMAX; c += 4)
                 if (c < C) {
-                    const float4 a = ld4(p00 + c), b = ld4(p01 + c), d = ld4(p10 + c), e = ld4(p11 + c);
-                    float4 v = make_float4(cm_resized(ly, lx, alpha, a.x, b.x, d.x, e.x), cm_resized(ly, lx, alpha, a.y, b.y, d.y, e.y),
-                                           cm_resized(ly, lx, alpha, a.z, b.z, d.z, e.z), cm_resized(ly, lx, alpha, a.w, b.w, d.w, e.w));
+                    const float4 a = ld4(k.p00 + c), b = ld4(k.p01 + c), d = ld4(k.p10 + c), e = ld4(k.p11 + c);
+                    float4 v = make_float4(blend_plane_times(ly, lx, alpha, a.x, b.x, d.x, e.x),
+                                           blend_plane_times(ly, lx, alpha, a.y, b.y, d.y, e.y),
+                                           blend_plane_times(ly, lx, alpha, a.z, b.z, d.z, e.z),
+                                           blend_plane_times(ly, lx, alpha, a.w, b.w, d.w, e.w));
                     if (accumulate) {
                         const float4 o = ld4(dst + c);
-                        v = make_float4(cm_added(o.x, v.x), cm_added(o.y, v.y), cm_added(o.z, v.z), cm_added(o.w, v.w));
+                        v = make_float4(add_rounded_product(o.x, v.x), add_rounded_product(o.y, v.y), add_rounded_product(o.z, v.z),
+                                        add_rounded_product(o.w, v.w));
                     }
                     st4(dst + c, v);
                 }
@@ -162,8 +163,8 @@ __global__ __launch_bounds__(CM_BLOCK) void cm_planes_resize_kernel(const float*
 #pragma unroll
             for (int c = 0; c < CMAX; ++c)
                 if (c < C) {
-                    const float v = cm_resized(ly, lx, alpha, p00[c], p01[c], p10[c], p11[c]);
-                    dst[c] = accumulate ? cm_added(dst[c], v) : v;
+                    const float v = blend_plane_times(ly, lx, alpha, k.p00[c], k.p01[c], k.p10[c], k.p11[c]);
+                    dst[c] = accumulate ? add_rounded_product(dst[c], v) : v;
                 }
         }
     }
@@ -173,67 +174,41 @@ __global__ __launch_bounds__(CM_BLOCK) void cm_planes_resize_kernel(const float*
 template <int CMAX, bool VEC4>
 __global__ __launch_bounds__(CM_BLOCK) void cm_argmax_kernel(const float* __restrict__ in, uint8_t* __restrict__ out, long n, int C) {
     for (long r = (long)blockIdx.x * CM_BLOCK + threadIdx.x; r < n; r += (long)gridDim.x * CM_BLOCK) {
-        const float* src = in + r * C;
         float v[CMAX];
-        if constexpr (VEC4) {
-#pragma unroll
-            for (int c = 0; c + 3 < CMAX; c += 4)
-                if (c < C) {
-                    const float4 q = ld4(src + c);
-                    v[c] = q.x;
-                    v[c + 1] = q.y;
-                    v[c + 2] = q.z;
-                    v[c + 3] = q.w;
-                }
-        } else {
-#pragma unroll
-            for (int c = 0; c < CMAX; ++c)
-                if (c < C) v[c] = src[c];
-        }
+        load_classes<CMAX, VEC4>(in + r * C, C, [&](int c, float x) { v[c] = x; });
         out[r] = (uint8_t)first_max<CMAX>(v, C);
     }
 }
 
-// ---- 4. paste: sd_scatter_kernel's lattice walk (one thread per pixel of the padded lattice, x fastest; pixels beyond the slide
-// and patches past the end of the lattice are never written) with a class index as the pasted byte.  MODE 0: pred [count][h][w]
-// class indices as floats, the nearest texel (torch's floorf(dst * scale)); an index outside [0, C) pastes 0 and sets status.
-// MODE 1: pred [count][h][w][C] probabilities, per class cm_planes_resize_kernel's value at alpha = 1 (1.f * v is v), then the
-// first maximum.
+// ---- 4. paste: sd_scatter_kernel's lattice walk (patch_pixel, lattice.hpp: one thread per pixel of the padded lattice, x fastest;
+// pixels beyond the slide and patches past the end of the lattice are never written) with a class index as the pasted byte.
+// MODE 0: pred [count][h][w] class indices as floats, the nearest texel (torch's floorf(dst * scale)); an index outside [0, C)
+// pastes 0 and sets status.  MODE 1: pred [count][h][w][C] probabilities, per class cm_planes_resize_kernel's value at alpha = 1
+// (1.f * v is v), then the first maximum.
 template <int CMAX, bool VEC4, int MODE>
 __global__ __launch_bounds__(CM_BLOCK) void cm_scatter_kernel(const float* __restrict__ pred, uint8_t* __restrict__ out,
                                                               int32_t* __restrict__ status, int H, int W, int n_w, int last, int p,
                                                               int h, int w, int C, int first, int count, float sh, float sw) {
-    const long pp = (long)p * p;
-    const long total = (long)count * pp;
+    const long total = (long)count * p * p;
     bool bad = false;
     for (long idx = (long)blockIdx.x * CM_BLOCK + threadIdx.x; idx < total; idx += (long)gridDim.x * CM_BLOCK) {
-        const int n = (int)(idx / pp);
-        const long r = idx - (long)n * pp;
-        const int y = (int)(r / p), x = (int)(r - (long)y * p);
-        const int k = first + n;
-        if (k > last) continue;
-        const int ky = k / n_w, kx = k - ky * n_w;
-        const long Y = (long)ky * p + y, X = (long)kx * p + x;
-        if (Y >= H || X >= W) continue;
+        const PatchPixel q = patch_pixel(idx, p, first, n_w, last, H, W);
+        if (q.skip) continue;
         int cls = 0;
         if constexpr (MODE == 0) {
-            const int sy = min((int)floorf((float)y * sh), h - 1), sx = min((int)floorf((float)x * sw), w - 1);
-            const float v = rintf(pred[((long)n * h + sy) * w + sx]);
+            const int sy = min((int)floorf((float)q.y * sh), h - 1), sx = min((int)floorf((float)q.x * sw), w - 1);
+            const float v = rintf(pred[((long)q.n * h + sy) * w + sx]);
             if (v >= 0.f && v < (float)C) cls = (int)v;
             else bad = true;                         // (a NaN lands here too)
         } else {
-            const Lerp ly = lerp_of(y, sh, h), lx = lerp_of(x, sw, w);
-            const float* src = pred + (long)n * h * w * C;
-            const float* p00 = src + ((long)ly.i0 * w + lx.i0) * C;
-            const float* p01 = src + ((long)ly.i0 * w + lx.i1) * C;
-            const float* p10 = src + ((long)ly.i1 * w + lx.i0) * C;
-            const float* p11 = src + ((long)ly.i1 * w + lx.i1) * C;
+            const Lerp ly = lerp_of(q.y, sh, h), lx = lerp_of(q.x, sw, w);
+            const Corners k = corners_of(pred + (long)q.n * h * w * C, ly, lx, w, C);
             float v[CMAX];
             if constexpr (VEC4) {
 #pragma unroll
                 for (int c = 0; c + 3 < CMAX; c += 4)
                     if (c < C) {
-                        const float4 a = ld4(p00 + c), b = ld4(p01 + c), d = ld4(p10 + c), e = ld4(p11 + c);
+                        const float4 a = ld4(k.p00 + c), b = ld4(k.p01 + c), d = ld4(k.p10 + c), e = ld4(k.p11 + c);
                         v[c] = blend_plane(ly, lx, a.x, b.x, d.x, e.x);
                         v[c + 1] = blend_plane(ly, lx, a.y, b.y, d.y, e.y);
                         v[c + 2] = blend_plane(ly, lx, a.z, b.z, d.z, e.z);
@@ -242,11 +217,11 @@ __global__ __launch_bounds__(CM_BLOCK) void cm_scatter_kernel(const float* __res
             } else {
 #pragma unroll
                 for (int c = 0; c < CMAX; ++c)
-                    if (c < C) v[c] = blend_plane(ly, lx, p00[c], p01[c], p10[c], p11[c]);
+                    if (c < C) v[c] = blend_plane(ly, lx, k.p00[c], k.p01[c], k.p10[c], k.p11[c]);
             }
             cls = first_max<CMAX>(v, C);
         }
-        out[Y * W + X] = (uint8_t)cls;
+        out[q.Y * W + q.X] = (uint8_t)cls;
     }
     if (bad) atomicOr(status, 1);
 }

@@ -40,9 +40,9 @@ __global__ __launch_bounds__(PX_BLOCK) void px_plane_resize_kernel(const float* 
         const Lerp ly = lerp_of(Y, sh, h), lx = lerp_of(X, sw, w);
         const float* r0 = in + (long)ly.i0 * w * stride;
         const float* r1 = in + (long)ly.i1 * w * stride;
-        const float v = alpha * blend_plane(ly, lx, r0[(long)lx.i0 * stride], r0[(long)lx.i1 * stride], r1[(long)lx.i0 * stride],
-                                            r1[(long)lx.i1 * stride]);
-        out[idx] = accumulate ? out[idx] + v : v;
+        const float v = blend_plane_times(ly, lx, alpha, r0[(long)lx.i0 * stride], r0[(long)lx.i1 * stride], r1[(long)lx.i0 * stride],
+                                          r1[(long)lx.i1 * stride]);
+        out[idx] = accumulate ? add_rounded_product(out[idx], v) : v;
     }
 }
 

@@ -50,37 +50,30 @@ __global__ __launch_bounds__(SD_BLOCK) void sd_gather_kernel(const uint8_t* __re
 
 // out[Y][X] = 255 * rintf(v) for the slide pixels inside the patches first .. first + count - 1; v = the nearest texel of the
 // patch's (h, w) prediction (MODE 0: torch's floorf(dst * scale) index) or its align_corners bilinear value (MODE 1: the
-// arithmetic of px_plane_resize_kernel at alpha = 1).  One thread per pixel of the padded lattice, x fastest: a wave writes 64
-// neighbouring bytes (row starts are not aligned: W is any number).  Pixels of the lattice beyond the slide, and patches past
-// the end of the lattice, are never written.
+// arithmetic of px_plane_resize_kernel at alpha = 1).  One thread per pixel of the padded lattice, x fastest (patch_pixel,
+// lattice.hpp): a wave writes 64 neighbouring bytes (row starts are not aligned: W is any number).  Pixels of the lattice beyond
+// the slide, and patches past the end of the lattice, are never written.
 template <int MODE>
 __global__ __launch_bounds__(SD_BLOCK) void sd_scatter_kernel(const float* __restrict__ pred, uint8_t* __restrict__ out, int H, int W,
                                                               int n_w, int last, int p, int h, int w, int stride, int first,
                                                               int count, float sh, float sw) {
-    const long pp = (long)p * p;
-    const long total = (long)count * pp;
+    const long total = (long)count * p * p;
     for (long idx = (long)blockIdx.x * SD_BLOCK + threadIdx.x; idx < total; idx += (long)gridDim.x * SD_BLOCK) {
-        const int n = (int)(idx / pp);
-        const long r = idx - (long)n * pp;
-        const int y = (int)(r / p), x = (int)(r - (long)y * p);
-        const int k = first + n;
-        if (k > last) continue;
-        const int ky = k / n_w, kx = k - ky * n_w;
-        const long Y = (long)ky * p + y, X = (long)kx * p + x;
-        if (Y >= H || X >= W) continue;
-        const float* src = pred + (long)n * h * w * stride;
+        const PatchPixel q = patch_pixel(idx, p, first, n_w, last, H, W);
+        if (q.skip) continue;
+        const float* src = pred + (long)q.n * h * w * stride;
         float v;
         if (MODE == 0) {
-            const int sy = min((int)floorf((float)y * sh), h - 1), sx = min((int)floorf((float)x * sw), w - 1);
+            const int sy = min((int)floorf((float)q.y * sh), h - 1), sx = min((int)floorf((float)q.x * sw), w - 1);
             v = src[((long)sy * w + sx) * stride];
         } else {
-            const Lerp ly = lerp_of(y, sh, h), lx = lerp_of(x, sw, w);
+            const Lerp ly = lerp_of(q.y, sh, h), lx = lerp_of(q.x, sw, w);
             const float* r0 = src + (long)ly.i0 * w * stride;
             const float* r1 = src + (long)ly.i1 * w * stride;
             v = blend_plane(ly, lx, r0[(long)lx.i0 * stride], r0[(long)lx.i1 * stride], r1[(long)lx.i0 * stride],
                             r1[(long)lx.i1 * stride]);
         }
-        out[Y * W + X] = (uint8_t)(int)(255.f * rintf(v));      // rintf: half to even, torch.round
+        out[q.Y * W + q.X] = (uint8_t)(int)(255.f * rintf(v));      // rintf: half to even, torch.round
     }
 }
 

@@ -7,6 +7,7 @@
 // them with an address.  The gather clamps a corner into the image, the merge only ever reads pred at offsets it has itself
 // tested to lie in [0, p), so a wrong lattice gives wrong numbers (NaN where no window covers a pixel), never a fault.
 #include "common.hpp"
+#include "lattice.hpp"
 
 #define TL_BLOCK 256
 #define TL_MAX_BLOCKS 4096     // grid-stride above this (cdna_hip_programming.md, guideline 11)
@@ -58,8 +59,8 @@ __global__ __launch_bounds__(TL_BLOCK) void tl_gather_kernel(const uint8_t* __re
 
 // out[y][x][c] = mean over the windows that cover (y, x) of pred[k][y - top][x - left][c], in fp64.  One thread per output
 // element (c fastest: loads and stores of neighbouring lanes are neighbours).  The lattice is sorted, so the covering windows
-// are a range of rows times a range of columns: n_h + n_w comparisons find it.  The values are added as doubles in ascending
-// row-major window order onto 0.0 and divided by the count once -- the order and the operations of
+// are a range of rows times a range of columns: n_h + n_w comparisons find it (covering, lattice.hpp).  The values are added
+// as doubles in ascending row-major window order onto 0.0 and divided by the count once -- the order and the operations of
 // infer_tile.combine_patches_to_image, hence its result bit for bit (adds and one IEEE division: nothing to contract).
 __global__ __launch_bounds__(TL_BLOCK) void tl_merge_kernel(const float* __restrict__ pred, const int32_t* __restrict__ tops,
                                                             const int32_t* __restrict__ lefts, double* __restrict__ out, int H,
@@ -70,21 +71,13 @@ __global__ __launch_bounds__(TL_BLOCK) void tl_merge_kernel(const float* __restr
         const int y = (int)(idx / WC);
         const int r = (int)(idx - (long)y * WC);
         const int x = r / C, c = r - x * C;
-        int i0 = n_h, i1 = 0, j0 = n_w, j1 = 0;      // [i0, i1) x [j0, j1): the covering windows
-        for (int i = 0; i < n_h; ++i) {
-            const int d = y - tops[i];
-            if (d >= 0 && d < p) { i0 = i < i0 ? i : i0; i1 = i + 1; }
-        }
-        for (int j = 0; j < n_w; ++j) {
-            const int d = x - lefts[j];
-            if (d >= 0 && d < p) { j0 = j < j0 ? j : j0; j1 = j + 1; }
-        }
+        const Covering rows = covering(tops, n_h, y, p), cols = covering(lefts, n_w, x, p);
         double acc = 0.0;
         int cnt = 0;
-        for (int i = i0; i < i1; ++i) {
+        for (int i = rows.i0; i < rows.i1; ++i) {
             const int dy = y - tops[i];
             if (dy < 0 || dy >= p) continue;         // (an unsorted lattice: never an address outside the window)
-            for (int j = j0; j < j1; ++j) {
+            for (int j = cols.i0; j < cols.i1; ++j) {
                 const int dx = x - lefts[j];
                 if (dx < 0 || dx >= p) continue;
                 float v = pred[(((long)(i * n_w + j) * p + dy) * p + dx) * C + c];

@@ -100,32 +100,29 @@ def _to_tensor(patch, device):
     return torch.from_numpy(np.ascontiguousarray(patch)).to(device).permute(2, 0, 1).float().div_(255.).unsqueeze(0)
 
 
+def _host_windows(img, patch_size, stain, device, forward):
+    """The per-window walk: the stain round trip, the cut on the host, ``forward(window tensor)`` -> numpy array with a leading
+    axis of 1 for every window under ``torch.no_grad()``.  Returns (the (N, ...) concatenation, H, W)."""
+    img = _stained(img, stain, device)
+    with torch.no_grad():
+        predictions = [forward(_to_tensor(patch, device)) for patch in divide_image_to_patches(img, patch_size)]
+    return np.concatenate(predictions), img.shape[0], img.shape[1]
+
+
 def predict_array(trainer, img, patch_size, device='cuda', stain=None):
     """Window-based superpixel prediction of one (H, W, 3) uint8 image -> (H, W) float map (infer_tile.py:94-119)."""
-    img = _stained(img, stain, device)
-    patches = divide_image_to_patches(img, patch_size)
-    predictions = []
-    with torch.no_grad():
-        for patch in patches:
-            input_, _ = trainer.preprocess(_to_tensor(patch, device))
-            prediction = trainer.postprocess(trainer.model(input_))
-            predictions.append(prediction.detach().cpu().numpy()[..., np.newaxis])
-    predictions = np.concatenate(predictions)
-    return combine_patches_to_image(predictions, img.shape[0], img.shape[1])
+    def forward(x):
+        input_, _ = trainer.preprocess(x)
+        return trainer.postprocess(trainer.model(input_)).detach().cpu().numpy()[..., np.newaxis]
+    return combine_patches_to_image(*_host_windows(img, patch_size, stain, device, forward))
 
 
 def pixel_predict_array(model, img, patch_size, device='cuda', stain=None):
     """Window-based pixel-wise prediction with WESUPPixelInference -> (H, W) class-1 probability
     (pixel_infer_tile.py:41-60; the caller rounds)."""
-    img = _stained(img, stain, device)
-    patches = divide_image_to_patches(img, patch_size)
-    predictions = []
-    with torch.no_grad():
-        for patch in patches:
-            pred = model(_to_tensor(patch, device))
-            predictions.append(np.expand_dims(pred.detach().cpu().numpy()[..., 1], 0))
-    predictions = np.concatenate(predictions)
-    return combine_patches_to_image(predictions, img.shape[0], img.shape[1])
+    def forward(x):
+        return np.expand_dims(model(x).detach().cpu().numpy()[..., 1], 0)
+    return combine_patches_to_image(*_host_windows(img, patch_size, stain, device, forward))
 
 
 def _n_classes(model):
@@ -142,26 +139,18 @@ def _check_status(status, n_classes, what):
 def predict_array_classes(trainer, img, patch_size, device='cuda', stain=None):
     """``predict_array`` for a model of more than two classes -> (H, W) uint8 class map: every window's painted class indices
     (what ``trainer.model`` returns for C > 2) come to the host and vote (``combine_patches_to_classes(votes=True)``)."""
-    img = _stained(img, stain, device)
-    patches = divide_image_to_patches(img, patch_size)
-    predictions = []
-    with torch.no_grad():
-        for patch in patches:
-            input_, _ = trainer.preprocess(_to_tensor(patch, device))
-            predictions.append(trainer.model(input_).detach().cpu().numpy())              # (1, p, p) class indices
-    return combine_patches_to_classes(np.concatenate(predictions), img.shape[0], img.shape[1], _n_classes(trainer.model), votes=True)
+    def forward(x):
+        input_, _ = trainer.preprocess(x)
+        return trainer.model(input_).detach().cpu().numpy()                                # (1, p, p) class indices
+    return combine_patches_to_classes(*_host_windows(img, patch_size, stain, device, forward), _n_classes(trainer.model), votes=True)
 
 
 def pixel_predict_array_classes(model, img, patch_size, device='cuda', stain=None):
     """``pixel_predict_array`` for a model of more than two classes -> (H, W) uint8 class map: all C probabilities of every
     window are merged on the host, then the first maximum."""
-    img = _stained(img, stain, device)
-    patches = divide_image_to_patches(img, patch_size)
-    predictions = []
-    with torch.no_grad():
-        for patch in patches:
-            predictions.append(model(_to_tensor(patch, device)).detach().cpu().numpy()[np.newaxis])      # (1, p, p, C)
-    return combine_patches_to_classes(np.concatenate(predictions), img.shape[0], img.shape[1], _n_classes(model))
+    def forward(x):
+        return model(x).detach().cpu().numpy()[np.newaxis]                                 # (1, p, p, C)
+    return combine_patches_to_classes(*_host_windows(img, patch_size, stain, device, forward), _n_classes(model))
 
 
 def window_batches(n_windows, batch):
@@ -203,6 +192,24 @@ def _keep(dst, src, first, valid):
     _lib.call('wesup_copy', ops._p(dst[first]), ops._p(src), valid * row * 4, ops._stream())
 
 
+def _resident_windows(img, patch_size, batch, stain, device, forward, tail, keep=_keep):
+    """The device-resident walk: one upload, the lattice, ``batch`` windows per pass -- ``ops.window_gather`` into one reused
+    input, ``forward(x)`` -> (batch, p, p, *tail) fp32 under ``torch.no_grad()``, ``keep`` of the pass's valid windows.  Nothing
+    in it waits for the device.  Returns (the (N, p, p, *tail) device buffer of all windows, tops, lefts, H, W)."""
+    p = int(patch_size)
+    H, W = img.shape[:2]
+    tops, lefts = window_grid(H, W, p)
+    passes, batch = window_batches(len(tops) * len(lefts), batch)
+    img_d = _upload(img, device, stain)
+    kept = torch.empty(len(tops) * len(lefts), p, p, *tail, dtype=torch.float32, device=img_d.device)
+    x = torch.empty(batch, 3, p, p, dtype=torch.float32, device=img_d.device)
+    with torch.no_grad():
+        for first, valid in passes:
+            ops.window_gather(img_d, tops, lefts, p, first, batch, out=x)
+            keep(kept, forward(x), first, valid)
+    return kept, tops, lefts, H, W
+
+
 def predict_array_batched(trainer, img, patch_size, batch=4, device='cuda', stain=None):
     """``predict_array`` with the image resident on the device: one upload, ``batch`` windows per pass (``ops.window_gather``
     -> ``trainer.preprocess`` with the batched GPU SLIC -> ``trainer.model``), the painted probabilities of all windows kept
@@ -213,19 +220,11 @@ def predict_array_batched(trainer, img, patch_size, batch=4, device='cuda', stai
 
     A trainer with a CPU ``slic_fn`` still segments window by window on the host inside ``preprocess`` (one round trip per
     window); only the forward pass is batched then."""
-    p = int(patch_size)
-    H, W = img.shape[:2]
-    tops, lefts = window_grid(H, W, p)
-    passes, batch = window_batches(len(tops) * len(lefts), batch)
-    img_d = _upload(img, device, stain)
-    kept = torch.empty(len(tops) * len(lefts), p, p, 1, dtype=torch.float32, device=img_d.device)
-    x = torch.empty(batch, 3, p, p, dtype=torch.float32, device=img_d.device)
-    with torch.no_grad():
-        for first, valid in passes:
-            ops.window_gather(img_d, tops, lefts, p, first, batch, out=x)
-            input_, _ = trainer.preprocess(x)
-            _keep(kept, trainer.model(input_), first, valid)
-        merged = ops.window_merge(kept, tops, lefts, H, W, round_first=True)
+    def forward(x):
+        input_, _ = trainer.preprocess(x)
+        return trainer.model(input_)
+    kept, tops, lefts, H, W = _resident_windows(img, patch_size, batch, stain, device, forward, (1,))
+    merged = ops.window_merge(kept, tops, lefts, H, W, round_first=True)
     return merged.view(H, W).cpu().numpy()
 
 
@@ -233,19 +232,10 @@ def pixel_predict_array_batched(model, img, patch_size, batch=2, device='cuda', 
     """``pixel_predict_array`` with the image resident on the device: ``batch`` windows per
     ``WESUPPixelInference.forward_batch`` (mind its memory: ~3.6 GB per 464 x 464 window), class 1 of every window kept on
     the device, one ``ops.window_merge`` of the probabilities and one copy to the host (the caller rounds)."""
-    p = int(patch_size)
-    H, W = img.shape[:2]
-    tops, lefts = window_grid(H, W, p)
-    passes, batch = window_batches(len(tops) * len(lefts), batch)
-    img_d = _upload(img, device, stain)
-    kept = torch.empty(len(tops) * len(lefts), p, p, 1, dtype=torch.float32, device=img_d.device)
-    x = torch.empty(batch, 3, p, p, dtype=torch.float32, device=img_d.device)
-    with torch.no_grad():
-        for first, valid in passes:
-            ops.window_gather(img_d, tops, lefts, p, first, batch, out=x)
-            pred = model.forward_batch(x)                                 # (batch, p, p, C)
-            kept[first:first + valid, :, :, 0].copy_(pred[:valid, :, :, 1])     # a strided device copy, no arithmetic
-        merged = ops.window_merge(kept, tops, lefts, H, W, round_first=False)
+    def keep_class_1(kept, pred, first, valid):                           # pred (batch, p, p, C)
+        kept[first:first + valid, :, :, 0].copy_(pred[:valid, :, :, 1])         # a strided device copy, no arithmetic
+    kept, tops, lefts, H, W = _resident_windows(img, patch_size, batch, stain, device, model.forward_batch, (1,), keep_class_1)
+    merged = ops.window_merge(kept, tops, lefts, H, W, round_first=False)
     return merged.view(H, W).cpu().numpy()
 
 
@@ -253,21 +243,14 @@ def predict_array_classes_batched(trainer, img, patch_size, batch=4, device='cud
     """``predict_array_classes`` with the image resident on the device (``predict_array_batched`` for C > 2): the painted class
     indices of all windows kept in one (N, p, p) device buffer, one ``ops.window_merge_classes(votes=True)`` and ONE copy of the
     (H, W) uint8 map to the host.  Equal to ``predict_array_classes`` bit for bit at ``batch=1``."""
-    p = int(patch_size)
-    H, W = img.shape[:2]
-    tops, lefts = window_grid(H, W, p)
-    passes, batch = window_batches(len(tops) * len(lefts), batch)
-    img_d = _upload(img, device, stain)
-    kept = torch.empty(len(tops) * len(lefts), p, p, dtype=torch.float32, device=img_d.device)
-    x = torch.empty(batch, 3, p, p, dtype=torch.float32, device=img_d.device)
-    with torch.no_grad():
-        for first, valid in passes:
-            ops.window_gather(img_d, tops, lefts, p, first, batch, out=x)
-            input_, _ = trainer.preprocess(x)
-            _keep(kept, trainer.model(input_), first, valid)
-        merged, status = ops.window_merge_classes(kept, tops, lefts, H, W, n_classes=_n_classes(trainer.model), votes=True)
+    def forward(x):
+        input_, _ = trainer.preprocess(x)
+        return trainer.model(input_)
+    C = _n_classes(trainer.model)
+    kept, tops, lefts, H, W = _resident_windows(img, patch_size, batch, stain, device, forward, ())
+    merged, status = ops.window_merge_classes(kept, tops, lefts, H, W, n_classes=C, votes=True)
     merged = merged.cpu().numpy()
-    _check_status(status, _n_classes(trainer.model), 'predict_array_classes_batched')      # (behind the copy: no wait of its own)
+    _check_status(status, C, 'predict_array_classes_batched')            # (behind the copy: no wait of its own)
     return merged
 
 
@@ -275,20 +258,19 @@ def pixel_predict_array_classes_batched(model, img, patch_size, batch=2, device=
     """``pixel_predict_array_classes`` with the image resident on the device: the (p, p, C) probabilities of every window kept on
     the device, one ``ops.window_merge_classes`` (the fp64 means per class live in registers: no (H, W, C) tensor) and one copy
     of the (H, W) uint8 map to the host."""
-    p = int(patch_size)
-    H, W = img.shape[:2]
-    C = _n_classes(model)
-    tops, lefts = window_grid(H, W, p)
-    passes, batch = window_batches(len(tops) * len(lefts), batch)
-    img_d = _upload(img, device, stain)
-    kept = torch.empty(len(tops) * len(lefts), p, p, C, dtype=torch.float32, device=img_d.device)
-    x = torch.empty(batch, 3, p, p, dtype=torch.float32, device=img_d.device)
-    with torch.no_grad():
-        for first, valid in passes:
-            ops.window_gather(img_d, tops, lefts, p, first, batch, out=x)
-            _keep(kept, model.forward_batch(x).contiguous(), first, valid)             # (batch, p, p, C)
-        merged, _ = ops.window_merge_classes(kept, tops, lefts, H, W)          # (probabilities: nothing comes in as an index)
+    def forward(x):
+        return model.forward_batch(x).contiguous()                        # (batch, p, p, C)
+    kept, tops, lefts, H, W = _resident_windows(img, patch_size, batch, stain, device, forward, (_n_classes(model),))
+    merged, _ = ops.window_merge_classes(kept, tops, lefts, H, W)         # (probabilities: nothing comes in as an index)
     return merged.cpu().numpy()
+
+
+def _form_kwargs(device, batch, stain):
+    """The keywords of a form: ``batch`` only for the device-resident ones, ``stain`` only when there is one."""
+    kw = {'device': device} if batch is None else {'batch': batch, 'device': device}
+    if stain is not None:                                   # (--stain-normalize: fitted once per image, applied on the device)
+        kw['stain'] = stain
+    return kw
 
 
 def predict(trainer, img_path, patch_size, device='cuda', batch=None, stain=None):
@@ -296,14 +278,10 @@ def predict(trainer, img_path, patch_size, device='cuda', batch=None, stain=None
     than two classes gives the uint8 class map of the ``_classes`` forms."""
     from PIL import Image
     img = np.asarray(Image.open(img_path).convert('RGB'))
-    kw = {} if stain is None else {'stain': stain}          # (--stain-normalize: fitted once per image, applied on the device)
-    if _n_classes(getattr(trainer, 'model', None)) > 2:
-        if batch is None:
-            return predict_array_classes(trainer, img, patch_size, device=device, **kw)
-        return predict_array_classes_batched(trainer, img, patch_size, batch=batch, device=device, **kw)
-    if batch is None:
-        return predict_array(trainer, img, patch_size, device=device, **kw)
-    return predict_array_batched(trainer, img, patch_size, batch=batch, device=device, **kw)
+    C = _n_classes(getattr(trainer, 'model', None))
+    form = {(False, True): predict_array, (False, False): predict_array_batched,
+            (True, True): predict_array_classes, (True, False): predict_array_classes_batched}[C > 2, batch is None]
+    return form(trainer, img, patch_size, **_form_kwargs(device, batch, stain))
 
 
 def save_predictions(predictions, img_paths, output_dir='predictions', n_classes=2):
@@ -338,22 +316,14 @@ def pixel_infer(model, data_dir, patch_size, output_dir=None, device='cuda', bat
     model.eval()
     data_dir = Path(data_dir).expanduser()
     img_paths = sorted((data_dir / 'images').iterdir())
-    predictions = []
     C = _n_classes(model)
-    kw = {} if stain is None else {'stain': stain}
+    form = {(False, True): pixel_predict_array, (False, False): pixel_predict_array_batched,
+            (True, True): pixel_predict_array_classes, (True, False): pixel_predict_array_classes_batched}[C > 2, batch is None]
+    kw = _form_kwargs(device, batch, stain)
+    predictions = []
     for path in img_paths:
-        img = np.asarray(Image.open(path).convert('RGB'))
-        if C > 2:
-            if batch is None:
-                predictions.append(pixel_predict_array_classes(model, img, patch_size, device=device, **kw))
-            else:
-                predictions.append(pixel_predict_array_classes_batched(model, img, patch_size, batch=batch, device=device, **kw))
-            continue
-        if batch is None:
-            merged = pixel_predict_array(model, img, patch_size, device=device, **kw)
-        else:
-            merged = pixel_predict_array_batched(model, img, patch_size, batch=batch, device=device, **kw)
-        predictions.append(merged.round())
+        merged = form(model, np.asarray(Image.open(path).convert('RGB')), patch_size, **kw)
+        predictions.append(merged if C > 2 else merged.round())
     if output_dir is not None:
         save_predictions(predictions, img_paths, output_dir, n_classes=C)
     return predictions

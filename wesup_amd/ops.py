@@ -1750,6 +1750,48 @@ def stain_apply(img, src_blocks, dst_blocks, jitter=None, keep_residual=0.0, io=
     return out[0] if squeeze else out
 
 
+# ---------------------------------------------------------------- the inference tools' wrappers below: shared argument checks
+def _out(out, shape, dtype, device, name):
+    """The output of a wrapper: a new ``shape`` tensor of ``dtype`` on ``device``, or the caller's buffer, checked to be one."""
+    shape = tuple(shape)
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    _chk(out, dtype, 'out')
+    if tuple(out.shape) != shape or out.device != device:
+        raise _lib.WesupHipError(f'{name}: out {tuple(out.shape)} on {out.device}, expected {shape}')
+    return out
+
+
+def _image_u8(img, name):
+    """(H, W) of an (H,W,3) image tensor (its dtype and device are the caller's ``_chk``: a lattice is checked first)."""
+    if not isinstance(img, torch.Tensor) or img.dim() != 3 or img.shape[-1] != 3:
+        raise _lib.WesupHipError(f'{name}: expected an (H,W,3) uint8 image')
+    return img.shape[0], img.shape[1]
+
+
+def _plane_stride(t, name):
+    """The element stride of a view that is dense but for one constant step between its elements, such as ``pred[..., 1]`` of a
+    (..., C) prediction, read in place by the kernels (a size-1 dimension's stride means nothing)."""
+    dims = [(n, s) for n, s in zip(t.shape, t.stride()) if n > 1]
+    stride = expect = dims[-1][1] if dims else 1
+    for n, s in reversed(dims):
+        if s != expect or stride < 1:
+            raise _lib.WesupHipError(f'{name} strides {t.stride()} for shape {tuple(t.shape)}')
+        expect *= n
+    return stride
+
+
+def _classes_of(pred, n_classes, indexed, name):
+    """C of a class-map entry.  ``indexed``: pred holds class indices and ``n_classes`` says how many there are; otherwise C is
+    pred's last dimension, and an ``n_classes`` given besides must agree with it."""
+    if indexed and n_classes is None:
+        raise _lib.WesupHipError(f'{name}: class indices need n_classes')
+    C = _chk_classes(n_classes if indexed else pred.shape[-1], name)
+    if n_classes is not None and int(n_classes) != C:
+        raise _lib.WesupHipError(f'{name}: pred {tuple(pred.shape)} for {n_classes} classes')
+    return C
+
+
 # ---------------------------------------------------------------- window inference on large images (csrc/tiles.hip)
 _lattice_cache = {}    # (device, axis positions) -> int32 device tensor: an image size meets the same few lattices again and again
 
@@ -1788,19 +1830,15 @@ def window_gather(img_u8_hwc, tops, lefts, p, first, count, out=None):
     infer_tile.window_grid (host integer sequences; checked here, their device copies are cached) -> (count,3,p,p) fp32 in
     [0, 1], the row-major windows ``first .. first + count - 1``, bit-equal to infer_tile._to_tensor.  Indices past the last
     window repeat it (the padding of a ragged final batch)."""
-    if not isinstance(img_u8_hwc, torch.Tensor) or img_u8_hwc.dim() != 3 or img_u8_hwc.shape[-1] != 3:
-        raise _lib.WesupHipError('window_gather: expected an (H,W,3) uint8 image')
-    H, W, _ = img_u8_hwc.shape
+    H, W = _image_u8(img_u8_hwc, 'window_gather')
     first, count, p = int(first), int(count), int(p)
     if first < 0 or count < 1:
         raise _lib.WesupHipError(f'window_gather: windows [{first}, {first} + {count})')
     tops_d, lefts_d = _lattice(tops, lefts, H, W, p, img_u8_hwc.device)
     _chk(img_u8_hwc, torch.uint8, 'img')
-    if out is None:
-        out = torch.empty(count, 3, p, p, dtype=torch.float32, device=img_u8_hwc.device)
-    _chk(out, name='out')
-    if out.shape != (count, 3, p, p) or out.device != img_u8_hwc.device or out.data_ptr() % 16:
-        raise _lib.WesupHipError(f'window_gather: out {tuple(out.shape)} on {out.device}, expected {(count, 3, p, p)}')
+    out = _out(out, (count, 3, p, p), torch.float32, img_u8_hwc.device, 'window_gather')
+    if out.data_ptr() % 16:
+        raise _lib.WesupHipError('window_gather: out is not 16-byte aligned')
     tok = _tbegin('window_gather')
     _lib.call('wesup_window_gather', _p(img_u8_hwc), _p(tops_d), _p(lefts_d), _p(out), H, W, tops_d.numel(), lefts_d.numel(), p,
               first, count, _stream())
@@ -1824,12 +1862,7 @@ def window_merge(pred, tops, lefts, H, W, round_first=False, out=None):
     if N != tops_d.numel() * lefts_d.numel():
         raise _lib.WesupHipError(f'window_merge: {N} windows for a lattice of {tops_d.numel()} x {lefts_d.numel()}')
     _chk(pred, name='pred')
-    shape = (H, W) if flat else (H, W, C)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float64, device=pred.device)
-    _chk(out, torch.float64, 'out')
-    if out.shape != shape or out.device != pred.device:
-        raise _lib.WesupHipError(f'window_merge: out {tuple(out.shape)} on {out.device}, expected {shape}')
+    out = _out(out, (H, W) if flat else (H, W, C), torch.float64, pred.device, 'window_merge')
     tok = _tbegin('window_merge')
     _lib.call('wesup_window_merge', _p(pred), _p(tops_d), _p(lefts_d), _p(out), H, W, C, tops_d.numel(), lefts_d.numel(), p,
               int(bool(round_first)), _stream())
@@ -1841,18 +1874,12 @@ def window_merge(pred, tops, lefts, H, W, round_first=False, out=None):
 def image_resize_u8(img_u8_hwc, h, w, out=None):
     """to_tensor + F.interpolate(mode='bilinear', align_corners=True) of pixel_infer.py:40,46 in one pass: img (H,W,3) uint8 on
     the device -> (1,3,h,w) fp32, ``img / 255.f`` resampled (at the image's own size: ``img / 255.f`` bit for bit)."""
-    if not isinstance(img_u8_hwc, torch.Tensor) or img_u8_hwc.dim() != 3 or img_u8_hwc.shape[-1] != 3:
-        raise _lib.WesupHipError('image_resize_u8: expected an (H,W,3) uint8 image')
+    H, W = _image_u8(img_u8_hwc, 'image_resize_u8')
     _chk(img_u8_hwc, torch.uint8, 'img')
-    H, W, _ = img_u8_hwc.shape
     h, w = int(h), int(w)
     if h < 1 or w < 1:
         raise _lib.WesupHipError(f'image_resize_u8: target size {h} x {w}')
-    if out is None:
-        out = torch.empty(1, 3, h, w, dtype=torch.float32, device=img_u8_hwc.device)
-    _chk(out, name='out')
-    if out.shape != (1, 3, h, w) or out.device != img_u8_hwc.device:
-        raise _lib.WesupHipError(f'image_resize_u8: out {tuple(out.shape)} on {out.device}, expected {(1, 3, h, w)}')
+    out = _out(out, (1, 3, h, w), torch.float32, img_u8_hwc.device, 'image_resize_u8')
     _lib.call('wesup_image_resize_u8', _p(img_u8_hwc), _p(out), H, W, h, w, _stream())
     return out
 
@@ -1864,9 +1891,9 @@ def plane_resize_acc(src, out, alpha=1.0, accumulate=False):
     if not isinstance(src, torch.Tensor) or not src.is_cuda or src.dtype != torch.float32 or src.dim() != 2 or out.dim() != 2:
         raise _lib.WesupHipError('plane_resize_acc: expected 2-D float32 CUDA/HIP planes')
     h, w = src.shape
-    stride = src.stride(1) if w > 1 else (src.stride(0) if h > 1 else 1)      # (a size-1 dimension's stride means nothing)
-    if stride < 1 or (h > 1 and src.stride(0) != w * stride) or src.device != out.device:
-        raise _lib.WesupHipError(f'plane_resize_acc: src strides {src.stride()} for shape {tuple(src.shape)}')
+    stride = _plane_stride(src, 'plane_resize_acc: src')
+    if src.device != out.device:
+        raise _lib.WesupHipError(f'plane_resize_acc: src on {src.device}, out on {out.device}')
     H, W = out.shape
     _lib.call('wesup_plane_resize_acc', _p(src), _p(out), h, w, H, W, stride, float(alpha), int(bool(accumulate)), _stream())
     return out
@@ -1909,18 +1936,13 @@ def patch_gather_resize(img_u8_hwc, p, h, w, first, count, align_corners=False, 
     ``patch / 255.f`` resized bilinearly to (h, w): ``F.interpolate(mode='bilinear')`` of infer.py, or with ``align_corners`` the
     resize of pixel_infer.py (ops.image_resize_u8 of the patch, bit for bit, where the patch lies inside the slide).  Indices
     past the last patch repeat it (the padding of a ragged final batch).  ``out``: a buffer reused across passes."""
-    if not isinstance(img_u8_hwc, torch.Tensor) or img_u8_hwc.dim() != 3 or img_u8_hwc.shape[-1] != 3:
-        raise _lib.WesupHipError('patch_gather_resize: expected an (H,W,3) uint8 image')
+    H, W = _image_u8(img_u8_hwc, 'patch_gather_resize')
     _chk(img_u8_hwc, torch.uint8, 'img')
-    H, W, p, first, count = _patch_lattice(img_u8_hwc.shape[0], img_u8_hwc.shape[1], p, first, count, 'patch_gather_resize')
+    H, W, p, first, count = _patch_lattice(H, W, p, first, count, 'patch_gather_resize')
     h, w = int(h), int(w)
     if h < 1 or w < 1:
         raise _lib.WesupHipError(f'patch_gather_resize: target size {h} x {w}')
-    if out is None:
-        out = torch.empty(count, 3, h, w, dtype=torch.float32, device=img_u8_hwc.device)
-    _chk(out, name='out')
-    if out.shape != (count, 3, h, w) or out.device != img_u8_hwc.device:
-        raise _lib.WesupHipError(f'patch_gather_resize: out {tuple(out.shape)} on {out.device}, expected {(count, 3, h, w)}')
+    out = _out(out, (count, 3, h, w), torch.float32, img_u8_hwc.device, 'patch_gather_resize')
     tok = _tbegin('patch_gather_resize')
     _lib.call('wesup_patch_gather_resize', _p(img_u8_hwc), _p(out), H, W, p, h, w, int(bool(align_corners)), first, count,
               _stream())
@@ -1943,10 +1965,9 @@ def patch_scatter_u8(pred, out, p, first, mode=0):
     H, W, p, first, count = _patch_lattice(out.shape[0], out.shape[1], p, first, count, 'patch_scatter_u8')
     if h < 1 or w < 1:
         raise _lib.WesupHipError(f'patch_scatter_u8: pred {tuple(pred.shape)}')
-    stride = pred.stride(2) if w > 1 else (pred.stride(1) // w if h > 1 else (pred.stride(0) // (h * w) if count > 1 else 1))
-    if stride < 1 or (h > 1 and pred.stride(1) != w * stride) or (count > 1 and pred.stride(0) != h * w * stride) or \
-            pred.device != out.device:
-        raise _lib.WesupHipError(f'patch_scatter_u8: pred strides {pred.stride()} for shape {tuple(pred.shape)}')
+    stride = _plane_stride(pred, 'patch_scatter_u8: pred')
+    if pred.device != out.device:
+        raise _lib.WesupHipError(f'patch_scatter_u8: pred on {pred.device}, out on {out.device}')
     tok = _tbegin('patch_scatter_u8')
     _lib.call('wesup_patch_scatter_u8', _p(pred), _p(out), H, W, p, h, w, stride, int(mode), first, count, _stream())
     _tend(tok, 4.0 * count * h * w + 1.0 * count * p * p)
@@ -1960,11 +1981,7 @@ def mask_scores(S, G, negative=False, out=None):
     _chk(S, torch.uint8, 'S'); _chk(G, torch.uint8, 'G')
     if S.shape != G.shape or S.numel() < 1 or S.device != G.device:
         raise _lib.WesupHipError(f'mask_scores: maps {tuple(S.shape)} and {tuple(G.shape)}')
-    if out is None:
-        out = torch.empty(4, dtype=torch.int64, device=S.device)
-    _chk(out, torch.int64, 'out')
-    if out.shape != (4,) or out.device != S.device:
-        raise _lib.WesupHipError(f'mask_scores: out {tuple(out.shape)} on {out.device}, expected (4,)')
+    out = _out(out, (4,), torch.int64, S.device, 'mask_scores')
     tok = _tbegin('mask_scores')
     _lib.call('wesup_mask_scores', _p(S), _p(G), _p(out), S.numel(), int(bool(negative)), _stream())
     _tend(tok, 2.0 * S.numel())
@@ -2000,11 +2017,7 @@ def window_merge_classes(pred, tops, lefts, H, W, n_classes=None, votes=False, o
     if not isinstance(pred, torch.Tensor) or pred.dim() != (3 if votes else 4):
         raise _lib.WesupHipError('window_merge_classes: expected (N,p,p,C) probabilities, or (N,p,p) class indices with votes=True')
     N, p, p2 = pred.shape[:3]
-    if votes and n_classes is None:
-        raise _lib.WesupHipError('window_merge_classes: votes=True needs n_classes')
-    C = _chk_classes(n_classes if votes else pred.shape[3], 'window_merge_classes')
-    if n_classes is not None and int(n_classes) != C:
-        raise _lib.WesupHipError(f'window_merge_classes: pred {tuple(pred.shape)} for {n_classes} classes')
+    C = _classes_of(pred, n_classes, votes, 'window_merge_classes')
     H, W = int(H), int(W)
     if p != p2:
         raise _lib.WesupHipError(f'window_merge_classes: pred {tuple(pred.shape)}')
@@ -2012,11 +2025,7 @@ def window_merge_classes(pred, tops, lefts, H, W, n_classes=None, votes=False, o
     if N != tops_d.numel() * lefts_d.numel():
         raise _lib.WesupHipError(f'window_merge_classes: {N} windows for a lattice of {tops_d.numel()} x {lefts_d.numel()}')
     _chk(pred, name='pred')
-    if out is None:
-        out = torch.empty(H, W, dtype=torch.uint8, device=pred.device)
-    _chk(out, torch.uint8, 'out')
-    if out.shape != (H, W) or out.device != pred.device:
-        raise _lib.WesupHipError(f'window_merge_classes: out {tuple(out.shape)} on {out.device}, expected {(H, W)}')
+    out = _out(out, (H, W), torch.uint8, pred.device, 'window_merge_classes')
     status = _status(status, pred.device, 'window_merge_classes')
     tok = _tbegin('window_merge_classes')
     _lib.call('wesup_window_merge_classes', _p(pred), _p(tops_d), _p(lefts_d), _p(out), _p(status), H, W, C, tops_d.numel(),
@@ -2048,12 +2057,7 @@ def class_argmax_u8(src, out=None):
     if src.dim() < 2 or src.numel() < 1:
         raise _lib.WesupHipError(f'class_argmax_u8: src {tuple(src.shape)}: expected (..., C)')
     C = _chk_classes(src.shape[-1], 'class_argmax_u8')
-    shape = tuple(src.shape[:-1])
-    if out is None:
-        out = torch.empty(shape, dtype=torch.uint8, device=src.device)
-    _chk(out, torch.uint8, 'out')
-    if tuple(out.shape) != shape or out.device != src.device:
-        raise _lib.WesupHipError(f'class_argmax_u8: out {tuple(out.shape)} on {out.device}, expected {shape}')
+    out = _out(out, src.shape[:-1], torch.uint8, src.device, 'class_argmax_u8')
     n = src.numel() // C
     tok = _tbegin('class_argmax_u8')
     _lib.call('wesup_class_argmax_u8', _p(src), _p(out), n, C, _stream())
@@ -2074,11 +2078,7 @@ def patch_scatter_classes_u8(pred, out, p, first, n_classes=None, mode=0, status
     if pred.dim() != (3 if mode == 0 else 4) or out.dim() != 2 or pred.device != out.device:
         raise _lib.WesupHipError('patch_scatter_classes_u8: expected (count,h,w) class indices (mode 0) or (count,h,w,C) '
                                  'probabilities (mode 1) and an (H,W) uint8 map on one device')
-    if mode == 0 and n_classes is None:
-        raise _lib.WesupHipError('patch_scatter_classes_u8: mode 0 needs n_classes')
-    C = _chk_classes(n_classes if mode == 0 else pred.shape[3], 'patch_scatter_classes_u8')
-    if n_classes is not None and int(n_classes) != C:
-        raise _lib.WesupHipError(f'patch_scatter_classes_u8: pred {tuple(pred.shape)} for {n_classes} classes')
+    C = _classes_of(pred, n_classes, mode == 0, 'patch_scatter_classes_u8')
     count, h, w = pred.shape[:3]
     H, W, p, first, count = _patch_lattice(out.shape[0], out.shape[1], p, first, count, 'patch_scatter_classes_u8')
     if h < 1 or w < 1:
@@ -2099,11 +2099,7 @@ def label_confusion(S, G, n_classes, out=None, status=None):
     C = _chk_classes(n_classes, 'label_confusion')
     if S.shape != G.shape or S.numel() < 1 or S.device != G.device:
         raise _lib.WesupHipError(f'label_confusion: maps {tuple(S.shape)} and {tuple(G.shape)}')
-    if out is None:
-        out = torch.empty(C, C, dtype=torch.int64, device=S.device)
-    _chk(out, torch.int64, 'conf')
-    if out.shape != (C, C) or out.device != S.device:
-        raise _lib.WesupHipError(f'label_confusion: conf {tuple(out.shape)} on {out.device}, expected {(C, C)}')
+    out = _out(out, (C, C), torch.int64, S.device, 'label_confusion')
     status = _status(status, S.device, 'label_confusion')
     tok = _tbegin('label_confusion')
     _lib.call('wesup_label_confusion', _p(S), _p(G), _p(out), _p(status), S.numel(), C, _stream())

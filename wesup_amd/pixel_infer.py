@@ -54,16 +54,16 @@ def image_paths(data_root):
     return sorted((Path(data_root).expanduser() / 'images').iterdir())
 
 
-def pixel_predict(model, img_u8_hwc, scales=(0.5,), device='cuda', full_maps=False, stain=None):
-    """(H, W, 3) uint8 image -> (H, W) fp32 class-1 probability averaged over ``scales`` (pixel_infer.py:40-53; the caller
-    rounds).  One upload; per scale the down-resize, the model and the up-resize into the running mean
-    (``alpha = 1 / len(scales)``: no pass of its own for the mean); one copy to the host."""
+def _scale_loop(name, model, img_u8_hwc, scales, device, full_maps, stain, tail, accumulate):
+    """The walk over the scales: one upload; per scale the down-resize, the model and ``accumulate(pred (h, w, C), mean, alpha,
+    i > 0)`` into the running mean (``alpha = 1 / len(scales)``: no pass of its own for the mean).  Returns the (H, W, *tail) fp32
+    mean on the device."""
     scales = tuple(scales)
     if not scales:
-        raise ValueError('pixel_predict: no scales')
+        raise ValueError(f'{name}: no scales')
     img_d = _upload(img_u8_hwc, device, stain)
     H, W = img_d.shape[:2]
-    mean = torch.empty(H, W, dtype=torch.float32, device=img_d.device)
+    mean = torch.empty(H, W, *tail, dtype=torch.float32, device=img_d.device)
     with torch.no_grad():
         for i, scale in enumerate(scales):
             h, w = target_size(H, W, scale)
@@ -71,30 +71,26 @@ def pixel_predict(model, img_u8_hwc, scales=(0.5,), device='cuda', full_maps=Fal
                 raise ValueError(f'scale {scale} leaves nothing of a {H} x {W} image')
             x = ops.image_resize_u8(img_d, h, w)
             pred = model(x) if full_maps else model.forward_per_resolution(x)[0]          # (h, w, C)
-            ops.plane_resize_acc(pred[..., 1], mean, alpha=1.0 / len(scales), accumulate=i > 0)
-    return mean.cpu().numpy()
+            accumulate(pred, mean, 1.0 / len(scales), i > 0)
+    return mean
+
+
+def pixel_predict(model, img_u8_hwc, scales=(0.5,), device='cuda', full_maps=False, stain=None):
+    """(H, W, 3) uint8 image -> (H, W) fp32 class-1 probability averaged over ``scales`` (pixel_infer.py:40-53; the caller
+    rounds).  Per scale class 1 is resized back into the running mean (``ops.plane_resize_acc``); one copy to the host."""
+    def accumulate(pred, mean, alpha, more):
+        ops.plane_resize_acc(pred[..., 1], mean, alpha=alpha, accumulate=more)
+    return _scale_loop('pixel_predict', model, img_u8_hwc, scales, device, full_maps, stain, (), accumulate).cpu().numpy()
 
 
 def pixel_predict_classes(model, img_u8_hwc, scales=(0.5,), device='cuda', full_maps=False, stain=None):
     """``pixel_predict`` for a model of more than two classes: (H, W, 3) uint8 image -> (H, W) uint8 class map.  Per scale all C
     probabilities are resized back in one pass into one (H, W, C) running mean (``ops.planes_resize_acc``, every plane the
     arithmetic of ``plane_resize_acc``), then the first maximum per pixel (``ops.class_argmax_u8``) and one copy to the host."""
-    scales = tuple(scales)
-    if not scales:
-        raise ValueError('pixel_predict_classes: no scales')
-    img_d = _upload(img_u8_hwc, device, stain)
-    H, W = img_d.shape[:2]
-    mean = torch.empty(H, W, model.n_classes, dtype=torch.float32, device=img_d.device)
-    with torch.no_grad():
-        for i, scale in enumerate(scales):
-            h, w = target_size(H, W, scale)
-            if h < 1 or w < 1:
-                raise ValueError(f'scale {scale} leaves nothing of a {H} x {W} image')
-            x = ops.image_resize_u8(img_d, h, w)
-            pred = model(x) if full_maps else model.forward_per_resolution(x)[0]          # (h, w, C)
-            ops.planes_resize_acc(pred.contiguous(), mean, alpha=1.0 / len(scales), accumulate=i > 0)
-        classes = ops.class_argmax_u8(mean)
-    return classes.cpu().numpy()
+    def accumulate(pred, mean, alpha, more):
+        ops.planes_resize_acc(pred.contiguous(), mean, alpha=alpha, accumulate=more)
+    mean = _scale_loop('pixel_predict_classes', model, img_u8_hwc, scales, device, full_maps, stain, (model.n_classes,), accumulate)
+    return ops.class_argmax_u8(mean).cpu().numpy()
 
 
 def main(data_root, checkpoint=None, output_dir=None, scales=(0.5,), device=None, full_maps=False, stain_normalize=None):
@@ -120,11 +116,10 @@ def main(data_root, checkpoint=None, output_dir=None, scales=(0.5,), device=None
         img = np.asarray(Image.open(path).convert('RGB'))
         out = output_dir / output_name(path.name)
         if model.n_classes > 2:                      # the class indices themselves, no x 255 (infer.save_predictions)
-            Image.fromarray(pixel_predict_classes(model, img, scales, device=device, full_maps=full_maps, **kw)).save(out, format='PNG')
-            written.append(out)
-            continue
-        prob = pixel_predict(model, img, scales, device=device, full_maps=full_maps, **kw)
-        Image.fromarray(prob.round().astype('uint8') * 255).save(out, format='PNG')
+            pred = pixel_predict_classes(model, img, scales, device=device, full_maps=full_maps, **kw)
+        else:
+            pred = pixel_predict(model, img, scales, device=device, full_maps=full_maps, **kw).round().astype('uint8') * 255
+        Image.fromarray(pred).save(out, format='PNG')
         written.append(out)
     return written
 

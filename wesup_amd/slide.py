@@ -102,14 +102,18 @@ def postprocess(pred, threshold=1000, device=None):
     return (remove_small_regions(pred, threshold, device) * 255).astype(pred.dtype)
 
 
-def compute_metrics(predictions, gts, negative=False, log=print, device=None):
-    """test_dp2019_pipeline.py:100-111: the mean overall accuracy and the mean Dice of the pairs, both maps inverted first with
-    ``negative``; prints the reference's two lines and returns the two numbers."""
-    scores = [slide_scores(pred, gt, negative, device) for pred, gt in zip(predictions, gts)]
+def _log_means(scores, log):
+    """The mean accuracy and the mean Dice of per-slide ``(accuracy, dice)`` pairs, as floats, behind the reference's two lines."""
     acc, dsc = np.mean([s[0] for s in scores]), np.mean([s[1] for s in scores])
     log('Accuracy:', acc)
     log('Dice:', dsc)
     return float(acc), float(dsc)
+
+
+def compute_metrics(predictions, gts, negative=False, log=print, device=None):
+    """test_dp2019_pipeline.py:100-111: the mean overall accuracy and the mean Dice of the pairs, both maps inverted first with
+    ``negative``; prints the reference's two lines and returns the two numbers."""
+    return _log_means([slide_scores(pred, gt, negative, device) for pred, gt in zip(predictions, gts)], log)
 
 
 # ------------------------------------------------------------------------------------------------ device-resident path
@@ -122,6 +126,24 @@ def _resident(img_u8, device, stain=None):
     return _upload(img_u8, device, stain)
 
 
+def _patch_walk(img_d, p, size, batch, keep_on_device, align_corners, forward, paste):
+    """The walk over the patches of a resident slide: the lattice, per pass of ``batch`` patches ``ops.patch_gather_resize`` to
+    ``size`` into one reused input -> ``forward(x)`` -> ``paste(the predictions of the pass's valid patches, out, first)`` into the
+    (H, W) uint8 map; nothing in it waits for the device.  Returns the map on the host, or the device tensor with
+    ``keep_on_device``."""
+    h, w = size
+    H, W = img_d.shape[:2]
+    n_h, n_w = patch_grid(H, W, p)
+    passes, batch = window_batches(n_h * n_w, batch)
+    out = torch.empty(H, W, dtype=torch.uint8, device=img_d.device)            # (the lattice covers every pixel)
+    x = torch.empty(batch, 3, h, w, dtype=torch.float32, device=img_d.device)
+    with torch.no_grad():
+        for first, valid in passes:
+            ops.patch_gather_resize(img_d, p, h, w, first, batch, align_corners=align_corners, out=x)
+            paste(forward(x)[:valid], out, first)
+    return out if keep_on_device else out.cpu().numpy()
+
+
 def slide_predict(trainer, img_u8, patch_size=PATCH_SIZE, input_size=INPUT_SIZE, batch=4, device='cuda', keep_on_device=False,
                   stain=None):
     """Superpixel prediction of a whole (H, W, 3) uint8 slide -> (H, W) uint8 map in {0, 255}: what the reference gets from
@@ -132,25 +154,23 @@ def slide_predict(trainer, img_u8, patch_size=PATCH_SIZE, input_size=INPUT_SIZE,
     differently and a pixel whose probability sits at 0.5 can turn (tests/test_slide_gpu.py).  A model of more than two classes
     gives the (H, W) uint8 map of class indices (``ops.patch_scatter_classes_u8``)."""
     p = int(patch_size)
-    h, w = (int(s) for s in input_size)
+    size = tuple(int(s) for s in input_size)
     img_d = _resident(img_u8, device, stain)
-    H, W = img_d.shape[:2]
-    n_h, n_w = patch_grid(H, W, p)
-    passes, batch = window_batches(n_h * n_w, batch)
-    out = torch.empty(H, W, dtype=torch.uint8, device=img_d.device)            # (the lattice covers every pixel)
-    x = torch.empty(batch, 3, h, w, dtype=torch.float32, device=img_d.device)
     C = _n_classes(trainer.model)
-    status = torch.zeros(1, dtype=torch.int32, device=img_d.device) if C > 2 else None
-    with torch.no_grad():
-        for first, valid in passes:
-            ops.patch_gather_resize(img_d, p, h, w, first, batch, align_corners=False, out=x)
-            input_, _ = trainer.preprocess(x)
-            if C > 2:                                # the painted class indices, pasted as they are
-                ops.patch_scatter_classes_u8(trainer.model(input_)[:valid], out, p, first, n_classes=C, mode=0, status=status)
-            else:
-                ops.patch_scatter_u8(trainer.model(input_)[:valid], out, p, first, mode=0)
-    result = out if keep_on_device else out.cpu().numpy()
-    if status is not None:                           # one word over all passes, read once, behind the map
+
+    def forward(x):
+        input_, _ = trainer.preprocess(x)
+        return trainer.model(input_)
+    if C > 2:                                        # the painted class indices, pasted as they are
+        status = torch.zeros(1, dtype=torch.int32, device=img_d.device)
+
+        def paste(pred, out, first):
+            ops.patch_scatter_classes_u8(pred, out, p, first, n_classes=C, mode=0, status=status)
+    else:
+        def paste(pred, out, first):
+            ops.patch_scatter_u8(pred, out, p, first, mode=0)
+    result = _patch_walk(img_d, p, size, batch, keep_on_device, False, forward, paste)
+    if C > 2:                                        # one word over all passes, read once, behind the map
         _check_status(status, C, 'slide_predict')
     return result
 
@@ -163,27 +183,27 @@ def slide_pixel_predict(model, img_u8, patch_size=PATCH_SIZE, scale=PIXEL_SCALE,
     (bilinear back to the patch, round, paste).  A model of more than two classes gives the map of class indices: all C
     planes bilinear back to the patch, the first maximum pasted (``ops.patch_scatter_classes_u8``)."""
     p = int(patch_size)
-    h, w = target_size(p, p, scale)
-    if h < 1 or w < 1:
+    size = target_size(p, p, scale)
+    if min(size) < 1:
         raise ValueError(f'scale {scale} leaves nothing of a {p} x {p} patch')
     img_d = _resident(img_u8, device, stain)
-    H, W = img_d.shape[:2]
-    n_h, n_w = patch_grid(H, W, p)
-    passes, batch = window_batches(n_h * n_w, batch)
-    out = torch.empty(H, W, dtype=torch.uint8, device=img_d.device)
-    x = torch.empty(batch, 3, h, w, dtype=torch.float32, device=img_d.device)
-    C = _n_classes(model)
-    # (mode 1 takes probabilities: nothing comes in as an index and the word is never set -- one for all passes, not read)
-    status = torch.zeros(1, dtype=torch.int32, device=img_d.device) if C > 2 else None
-    with torch.no_grad():
-        for first, valid in passes:
-            ops.patch_gather_resize(img_d, p, h, w, first, batch, align_corners=True, out=x)
-            probs = model.forward_per_resolution(x)                             # (batch, h, w, C)
-            if C > 2:                                # all C planes resized back, the first maximum pasted
-                ops.patch_scatter_classes_u8(probs[:valid], out, p, first, mode=1, status=status)
-            else:
-                ops.patch_scatter_u8(probs[:valid, :, :, 1], out, p, first, mode=1)
-    return out if keep_on_device else out.cpu().numpy()
+    if _n_classes(model) > 2:                        # all C planes resized back, the first maximum pasted
+        # (mode 1 takes probabilities: nothing comes in as an index and the word is never set -- one for all passes, not read)
+        status = torch.zeros(1, dtype=torch.int32, device=img_d.device)
+
+        def paste(probs, out, first):                # probs (valid, h, w, C)
+            ops.patch_scatter_classes_u8(probs, out, p, first, mode=1, status=status)
+    else:
+        def paste(probs, out, first):
+            ops.patch_scatter_u8(probs[:, :, :, 1], out, p, first, mode=1)
+    return _patch_walk(img_d, p, size, batch, keep_on_device, True, model.forward_per_resolution, paste)
+
+
+def _resident_u8(a, device):
+    """A map for the scores on ``device``: a tensor moved there, anything else uploaded as uint8."""
+    if isinstance(a, torch.Tensor):
+        return a.to(device).contiguous()
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(a).astype(np.uint8, copy=False))).to(device)
 
 
 def slide_class_scores(pred, gt, n_classes, device=None):
@@ -199,12 +219,7 @@ def slide_class_scores(pred, gt, n_classes, device=None):
         conf = M.confusion(pred.cpu() if isinstance(pred, torch.Tensor) else pred, gt.cpu() if isinstance(gt, torch.Tensor) else gt, C)
     else:
         device = pred.device if on_device else device
-
-        def resident(a):
-            if isinstance(a, torch.Tensor):
-                return a.to(device).contiguous()
-            return torch.from_numpy(np.ascontiguousarray(np.asarray(a).astype(np.uint8, copy=False))).to(device)
-        table, status = ops.label_confusion(resident(pred), resident(gt), C)
+        table, status = ops.label_confusion(_resident_u8(pred, device), _resident_u8(gt, device), C)
         conf = table.cpu().numpy()
         if int(status.cpu()) != 0:
             raise ValueError(f'class index outside [0, {C})')
@@ -222,12 +237,7 @@ def slide_scores(pred_u8, gt_u8, negative=False, device=None):
             P, G = 255 - P, 255 - G
         return float(accuracy(P, G)), float(dice(P, G))
     device = pred_u8.device if on_device else device
-
-    def resident(a):
-        if isinstance(a, torch.Tensor):
-            return a.to(device).contiguous()
-        return torch.from_numpy(np.ascontiguousarray(np.asarray(a).astype(np.uint8, copy=False))).to(device)
-    P, G = resident(pred_u8), resident(gt_u8)
+    P, G = _resident_u8(pred_u8, device), _resident_u8(gt_u8, device)
     eq, inter, sum_s, sum_g = (int(v) for v in ops.mask_scores(P, G, negative).cpu().tolist())
     return eq / P.numel(), 2 * inter / (sum_g + sum_s + 1e-7)
 
@@ -276,10 +286,7 @@ def score_directory(output_dir, gt_dir, log=print, device=None, n_classes=2):
         if not preds:
             return {}
         scores = [slide_class_scores(_read_classes(p), _read_classes(g), n_classes, device) for p, g in zip(preds, gts)]
-        acc, dsc = float(np.mean([s[0] for s in scores])), float(np.mean([s[1] for s in scores]))
-        log('Accuracy:', acc)
-        log('Dice:', dsc)
-        return {'all': (acc, dsc)}
+        return {'all': _log_means(scores, log)}
     pos_pred, neg_pred = split_stems(Path(output_dir).glob('*.png'))
     pos_gt, neg_gt = split_stems(Path(gt_dir).glob('*.png'))
     result = {}
