@@ -6,9 +6,12 @@
 // TPAMI 2012) with skimage's parameterisation:
 //   1. sRGB -> CIE Lab (D65), colours divided by the compactness m;
 //   2. cluster centres on a regular grid: step = round(sqrt(HW/n)), first centre at floor(sqrt(HW/n)/2);
-//   3. max_iter rounds of { every pixel takes the nearest centre among those whose 2S x 2S window holds it,
-//      D^2 = |lab/m - c_lab/m|^2 + (dy^2 + dx^2)/S^2, ties to the lower centre index; centres move to the mean of
-//      their members };  sums are 64-bit fixed point, so the result does not depend on the order of the atomics;
+//   3. max_iter rounds of { every pixel takes the nearest centre among ALL those whose 2S x 2S window (around the
+//      centre's current position) holds it, D^2 = |lab/m - c_lab/m|^2 + (dy^2 + dx^2)/S^2, ties to the lower centre
+//      index; a pixel inside no window takes the centre of its home grid cell and counts in that centre's sums;
+//      centres move to the mean of their members };  sums are 64-bit fixed point, so the result does not depend on
+//      the order of the atomics.  The search visits the grid cells within slic_radius() of the pixel's home cell:
+//      3 while no centre is 1.5 S from its home, more once one has drifted (the update kernel keeps the bound);
 //   4. connectivity: 4-connected components of the label image by lock-free union-find (root = first pixel in
 //      raster order); components smaller than min_size_factor * HW/n are absorbed by the component of the pixel
 //      left of (else above) their first pixel; surviving components are renumbered 0..K-1 in raster order of their
@@ -56,29 +59,34 @@ __global__ void slic_init_kernel(const float4* __restrict__ lab, float* __restri
     o[0] = (float)y; o[1] = (float)x; o[2] = c.x; o[3] = c.y; o[4] = c.z;
 }
 
-// nearest centre among the 7x7 grid neighbourhood whose 2S window contains the pixel; accumulates fixed-point sums
-__global__ void slic_assign_kernel(const float4* __restrict__ lab, const float* __restrict__ cen,
-                                   int32_t* __restrict__ label, long long* __restrict__ sums, SlicGrid g, int B,
-                                   int accumulate) {
-    const long HW = (long)g.H * g.W;
-    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= B * HW) return;
-    const int b = idx / HW;
-    const int p = idx - (long)b * HW;
-    const int y = p / g.W, x = p - y * g.W;
+// Which grid cells hold the candidates of a pixel.  A pixel is at most S/2 from the home position of its home cell (towards
+// the inside of the grid; pixels outside the first / last row of centres are further from every other centre, not nearer).  A
+// centre whose window holds the pixel is at most 2S from it, and at most drift from its own home.  So its cell is at most
+// 2.5 + drift / S cells from the pixel's home cell: 3 cells while every drift is below 1.5 S.  slic_update_kernel keeps, per
+// image, the largest whole number of cells beyond 3 that any centre's drift has asked for so far (0 in most runs); the
+// assignment kernels search 3 + that many cells, which makes the search exact for any drift.  A radius larger than needed
+// only visits centres whose window test fails, so it never changes a label.
+__device__ __forceinline__ int slic_extra_cells(float qy, float qx, int k, const SlicGrid& g) {
+    const float hy = (float)(g.start + (k / g.gx) * g.step), hx = (float)(g.start + (k % g.gx) * g.step);
+    const float drift = fmaxf(fabsf(qy - hy), fabsf(qx - hx)) / (float)g.step;
+    return max((int)floorf(drift + 2.5f + 1e-3f) - 3, 0);
+}
+
+// nearest centre among the (2R+1) x (2R+1) grid neighbourhood whose 2S window contains the pixel; accumulates fixed-point
+// sums in global memory
+__device__ __forceinline__ void slic_assign_pixel(const float4* __restrict__ lab, const float* __restrict__ cen,
+                                                  int32_t* __restrict__ label, long long* __restrict__ sums,
+                                                  const SlicGrid& g, int b, int y, int x, int R, int accumulate) {
     const int Kc = g.gy * g.gx;
+    const long idx = ((long)b * g.H + y) * g.W + x;
     const float4 c = lab[idx];
     const int cy = min(max((y - g.start + g.step / 2) / g.step, 0), g.gy - 1);
     const int cx = min(max((x - g.start + g.step / 2) / g.step, 0), g.gx - 1);
     const float S = (float)g.step, inv_s2 = 1.f / (S * S), win = 2.f * S;
     float best = 3.0e38f;
     int bk = -1;
-    for (int dy = -3; dy <= 3; ++dy) {          // 7x7 grid cells: a centre within 2S of the pixel is at most 3 cells away
-        const int ky = cy + dy;
-        if (ky < 0 || ky >= g.gy) continue;
-        for (int dx = -3; dx <= 3; ++dx) {
-            const int kx = cx + dx;
-            if (kx < 0 || kx >= g.gx) continue;
+    for (int ky = max(cy - R, 0); ky <= min(cy + R, g.gy - 1); ++ky) {      // slic_extra_cells: no other cell can hold a candidate
+        for (int kx = max(cx - R, 0); kx <= min(cx + R, g.gx - 1); ++kx) {
             const int k = ky * g.gx + kx;
             const float* q = cen + ((long)b * Kc + k) * 5;
             const float ddy = (float)y - q[0], ddx = (float)x - q[1];
@@ -88,7 +96,7 @@ __global__ void slic_assign_kernel(const float4* __restrict__ lab, const float* 
             if (d < best) { best = d; bk = k; }          // ascending k: ties keep the lower centre index
         }
     }
-    if (bk < 0) bk = cy * g.gx + cx;
+    if (bk < 0) bk = cy * g.gx + cx;                     // inside no window: the home cell's centre
     label[idx] = bk;
     if (accumulate) {
         long long* s = sums + ((long)b * Kc + bk) * 6;
@@ -100,17 +108,31 @@ __global__ void slic_assign_kernel(const float4* __restrict__ lab, const float* 
         atomicAdd((unsigned long long*)&s[5], 1ull);
     }
 }
+__global__ void slic_assign_kernel(const float4* __restrict__ lab, const float* __restrict__ cen,
+                                   int32_t* __restrict__ label, long long* __restrict__ sums,
+                                   const int* __restrict__ extra, SlicGrid g, int B, int accumulate) {
+    const long HW = (long)g.H * g.W;
+    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= B * HW) return;
+    const int b = idx / HW;
+    const int p = idx - (long)b * HW;
+    const int y = p / g.W;
+    slic_assign_pixel(lab, cen, label, sums, g, b, y, p - y * g.W, 3 + extra[b], accumulate);
+}
 // The same assignment, one block per 16 x 16 pixel tile (round 4).  The per-pixel form above sends six 64-bit atomics per pixel
 // to HBM-side memory (55 M of them per segmentation of a 4 x 480 x 480 batch: 4.3 ms).  A tile's pixels can only choose among
-// the centres of the grid cells within three cells of the tile (<= 13 x 13 for a grid step >= 3): those centres are staged in
-// LDS, the pixels accumulate their fixed-point contributions there with LDS atomics, and the block adds one value per
-// (centre, field) it touched to the global sums -- integer sums, so the result is bit-identical to the per-pixel form whatever
-// the grouping.  Candidates are visited in the same ascending-centre order (ties keep the lower index).
+// the centres of the grid cells within the search radius of the tile (three cells while no centre has drifted 1.5 S from its
+// home: <= 13 x 13 for a grid step >= 3): those centres are staged in LDS, the pixels accumulate their fixed-point contributions
+// there with LDS atomics, and the block adds one value per (centre, field) it touched to the global sums -- integer sums, so the
+// result is bit-identical to the per-pixel form whatever the grouping.  Candidates are visited in the same ascending-centre
+// order (ties keep the lower index).  Once drift has widened the radius so far that a tile's table would exceed SLIC_MAXC, the
+// block takes the per-pixel form (centres and sums in global memory) for that launch.
 #define SLIC_TILE 16
 #define SLIC_MAXC 176
 __global__ __launch_bounds__(256) void slic_assign_tile_kernel(const float4* __restrict__ lab, const float* __restrict__ cen,
                                                                 int32_t* __restrict__ label, long long* __restrict__ sums,
-                                                                const SlicGrid g, int accumulate) {
+                                                                const int* __restrict__ extra, const SlicGrid g,
+                                                                int accumulate) {
     __shared__ float scen[SLIC_MAXC][5];
     __shared__ unsigned long long ssum[SLIC_MAXC][6];
     const int b = blockIdx.z, tid = threadIdx.x;
@@ -118,9 +140,15 @@ __global__ __launch_bounds__(256) void slic_assign_tile_kernel(const float4* __r
     const int ty1 = min(ty0 + SLIC_TILE, g.H) - 1, tx1 = min(tx0 + SLIC_TILE, g.W) - 1;
     const int Kc = g.gy * g.gx;
     auto cell = [&](int v, int n) { return min(max((v - g.start + g.step / 2) / g.step, 0), n - 1); };
-    const int cy_lo = max(cell(ty0, g.gy) - 3, 0), cy_hi = min(cell(ty1, g.gy) + 3, g.gy - 1);
-    const int cx_lo = max(cell(tx0, g.gx) - 3, 0), cx_hi = min(cell(tx1, g.gx) + 3, g.gx - 1);
-    const int ncx = cx_hi - cx_lo + 1, nc = (cy_hi - cy_lo + 1) * ncx;      // <= SLIC_MAXC (the host checked the step)
+    const int R = 3 + extra[b];                                             // block-uniform
+    const int cy_lo = max(cell(ty0, g.gy) - R, 0), cy_hi = min(cell(ty1, g.gy) + R, g.gy - 1);
+    const int cx_lo = max(cell(tx0, g.gx) - R, 0), cx_hi = min(cell(tx1, g.gx) + R, g.gx - 1);
+    const int ncx = cx_hi - cx_lo + 1, nc = (cy_hi - cy_lo + 1) * ncx;      // <= SLIC_MAXC at R == 3 (the host checked the step)
+    if (nc > SLIC_MAXC) {                                                   // widened by drift beyond the table: per-pixel form
+        const int y = ty0 + (tid >> 4), x = tx0 + (tid & 15);
+        if (y < g.H && x < g.W) slic_assign_pixel(lab, cen, label, sums, g, b, y, x, R, accumulate);
+        return;
+    }
     for (int i = tid; i < nc * 5; i += 256) {
         const int c = i / 5, f = i - c * 5;
         const int k = (cy_lo + c / ncx) * g.gx + cx_lo + c % ncx;
@@ -136,12 +164,8 @@ __global__ __launch_bounds__(256) void slic_assign_tile_kernel(const float4* __r
         const float S = (float)g.step, inv_s2 = 1.f / (S * S), win = 2.f * S;
         float best = 3.0e38f;
         int bl = -1;
-        for (int dy = -3; dy <= 3; ++dy) {
-            const int ky = cy + dy;
-            if (ky < 0 || ky >= g.gy) continue;
-            for (int dx = -3; dx <= 3; ++dx) {
-                const int kx = cx + dx;
-                if (kx < 0 || kx >= g.gx) continue;
+        for (int ky = max(cy - R, 0); ky <= min(cy + R, g.gy - 1); ++ky) {
+            for (int kx = max(cx - R, 0); kx <= min(cx + R, g.gx - 1); ++kx) {
                 const int l = (ky - cy_lo) * ncx + (kx - cx_lo);
                 const float* q = scen[l];
                 const float ddy = (float)y - q[0], ddx = (float)x - q[1];
@@ -171,19 +195,25 @@ __global__ __launch_bounds__(256) void slic_assign_tile_kernel(const float4* __r
         atomicAdd((unsigned long long*)&sums[((long)b * Kc + k) * 6 + f], ssum[c][f]);
     }
 }
-__global__ void slic_update_kernel(float* __restrict__ cen, long long* __restrict__ sums, int total) {
+// centres move to the mean of their members (a centre without members stays); extra[b] keeps the search radius beyond 3 cells
+// that the drift of any centre of image b has asked for (slic_extra_cells)
+__global__ void slic_update_kernel(float* __restrict__ cen, long long* __restrict__ sums, int* __restrict__ extra,
+                                   const SlicGrid g, int total) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= total) return;
     long long* s = sums + (long)idx * 6;
     const long long n = s[5];
     if (n > 0) {
         float* o = cen + (long)idx * 5;
+        const int Kc = g.gy * g.gx;
         const double inv = 1.0 / (double)n;
         o[0] = (float)((double)s[0] * inv);
         o[1] = (float)((double)s[1] * inv);
         o[2] = (float)((double)s[2] * inv / SLIC_FIX);
         o[3] = (float)((double)s[3] * inv / SLIC_FIX);
         o[4] = (float)((double)s[4] * inv / SLIC_FIX);
+        const int e = slic_extra_cells(o[0], o[1], idx % Kc, g);
+        if (e > 0) atomicMax(&extra[idx / Kc], e);
     }
 #pragma unroll
     for (int k = 0; k < 6; ++k) s[k] = 0;
@@ -348,7 +378,7 @@ extern "C" size_t wesup_slic_workspace_bytes(int B, int H, int W, int n_segments
     size_t b = 0;
     b += align_up(B * HW * 16, 256);            // lab
     b += align_up(B * Kc * 5 * 4, 256);         // centres
-    b += align_up(B * Kc * 6 * 8, 256);         // fixed-point sums
+    b += align_up(B * Kc * 6 * 8 + B * 4, 256); // fixed-point sums, then the search radius beyond 3 cells per image
     b += 6 * align_up(B * HW * 4, 256);         // centre label, parent, size, target, final_root / is_root, newid
     b += align_up(B * nblk * 4, 256);           // block sums
     return b;
@@ -370,7 +400,8 @@ extern "C" int wesup_slic(const float* img_nchw, int32_t* labels, int32_t* n_lab
     char* w = (char*)ws;
     float4* lab = (float4*)w;            w += align_up((size_t)B * HW * 16, 256);
     float* cen = (float*)w;              w += align_up((size_t)B * Kc * 5 * 4, 256);
-    long long* sums = (long long*)w;     w += align_up((size_t)B * Kc * 6 * 8, 256);
+    long long* sums = (long long*)w;     w += align_up((size_t)B * Kc * 6 * 8 + (size_t)B * 4, 256);
+    int* extra = (int*)(sums + (size_t)B * Kc * 6);      // zeroed with the sums; only ever raised by slic_update_kernel
     const size_t plane = align_up((size_t)B * HW * 4, 256);
     int32_t* clabel = (int32_t*)w;       w += plane;
     int* parent = (int*)w;               w += plane;
@@ -385,15 +416,16 @@ extern "C" int wesup_slic(const float* img_nchw, int32_t* labels, int32_t* n_lab
     const unsigned pb = (unsigned)((tot + 255) / 256);
     WESUP_LAUNCH(slic_lab_kernel, dim3(pb), dim3(256), 0, st, img_nchw, lab, B, HW, 1.f / compactness);
     WESUP_LAUNCH(slic_init_kernel, dim3(ceil_div(B * Kc, 256)), dim3(256), 0, st, lab, cen, g, B);
-    if (wesup_fill_words_(sums, 0u, ((size_t)B * Kc * 6 * 8) / 4, st) != WESUP_OK) return WESUP_ERR_LAUNCH;
-    // tile form when the candidate centres of a 16 x 16 tile fit its LDS table: (15 / step + 2 + 6)^2 <= SLIC_MAXC
+    if (wesup_fill_words_(sums, 0u, ((size_t)B * Kc * 6 * 8) / 4 + (size_t)B, st) != WESUP_OK) return WESUP_ERR_LAUNCH;
+    // tile form when the candidate centres of a 16 x 16 tile fit its LDS table at the radius of 3 cells that holds without
+    // drift: (15 / step + 2 + 6)^2 <= SLIC_MAXC
     const int span = (SLIC_TILE - 1) / g.step + 2 + 6;
     const bool tiled = span * span <= SLIC_MAXC && B <= 65535;
     const dim3 tgrid(ceil_div(W, SLIC_TILE), ceil_div(H, SLIC_TILE), B);
     for (int it = 0; it < max_iter; ++it) {
-        if (tiled) WESUP_LAUNCH(slic_assign_tile_kernel, tgrid, dim3(256), 0, st, lab, cen, clabel, sums, g, 1);
-        else WESUP_LAUNCH(slic_assign_kernel, dim3(pb), dim3(256), 0, st, lab, cen, clabel, sums, g, B, 1);
-        WESUP_LAUNCH(slic_update_kernel, dim3(ceil_div(B * Kc, 256)), dim3(256), 0, st, cen, sums, B * Kc);
+        if (tiled) WESUP_LAUNCH(slic_assign_tile_kernel, tgrid, dim3(256), 0, st, lab, cen, clabel, sums, extra, g, 1);
+        else WESUP_LAUNCH(slic_assign_kernel, dim3(pb), dim3(256), 0, st, lab, cen, clabel, sums, extra, g, B, 1);
+        WESUP_LAUNCH(slic_update_kernel, dim3(ceil_div(B * Kc, 256)), dim3(256), 0, st, cen, sums, extra, g, B * Kc);
     }
     if (!enforce_connectivity) {
         // raw k-means labels: ids are centre indices (not necessarily all used)
