@@ -391,7 +391,9 @@ int wesup_slic(const float* img_nchw, int32_t* labels, int32_t* n_labels, int B,
                void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------ head, loss, optimiser (K7/K10/K11/K13)
- * classifier Linear(D,2)+Softmax(dim=1) (models/wesup.py:229-232,292) */
+ * classifier Linear(D,2)+Softmax(dim=1) (models/wesup.py:229-232,292).  The two-class entries of this block run the kernels of the
+ * _c entries below, instantiated for C = 2 (csrc/loss.hip); wesup_classifier_fwd alone takes any D > 0 (beyond D = 8191, where
+ * Wc | bc no longer fit 64 KiB of LDS, its kernel reads them from global memory). */
 int wesup_classifier_fwd(const float* feat, const float* Wc, const float* bc, float* pred, int R, int D, void* stream);
 /* given dpred: dfeat[R][D] (masked by feat > 0: fc_layers' last ReLU), dWc[2][D], dbc[2] */
 size_t wesup_classifier_bwd_workspace_bytes(int R, int D);
@@ -419,7 +421,9 @@ int wesup_loss_bwd(const float* pred, const float* y_all, const int32_t* n_sp, c
  * wesup_head_bwd  = wesup_loss_fwd (terms only) + wesup_loss_bwd + the first kernel of wesup_classifier_bwd: terms (B, 8),
  *                   dpred (B*Kmax, 2), dfeat (B*Kmax, D); Kmax % 64 == 0, C == 2; ws as wesup_classifier_bwd_workspace_bytes.
  * wesup_classifier_bwd_finish: dWc (2, D), dbc (2) from the partial sums wesup_head_bwd left in ws -- on any stream behind it
- *                   (models/wesup.py:66-139,229-232,492-531). */
+ *                   (models/wesup.py:66-139,229-232,492-531).
+ * wesup_head_fwd takes labels of any width C > 0 and writes two columns of pred; wesup_head_bwd, wesup_classifier_bwd,
+ * wesup_classifier_bwd_workspace_bytes and wesup_classifier_bwd_finish are their _c forms called with C = 2. */
 int wesup_head_fwd(const float* feat, const float* Wc, const float* bc, float* pred, const float* sp_labels,
                    const int32_t* n_sp, const int32_t* n_l, float threshold, int enable, float* y_all, int32_t* src_idx,
                    float* max_sim, int B, int Kmax, int D, int C, void* stream);
@@ -428,8 +432,10 @@ int wesup_head_bwd(const float* feat, const float* Wc, const float* pred, const 
                    float* dfeat, int B, int Kmax, int D, int C, void* ws, size_t ws_bytes, void* stream);
 int wesup_classifier_bwd_finish(const void* ws, size_t ws_bytes, float* dWc, float* dbc, int R, int D, void* stream);
 /* ------------------------------------------------------------------ the C-way head, 2 <= C <= WESUP_MAX_CLASSES
- * New entries beside the two-class ones above, which keep their kernels: the two-class step's launch list and bits do not move.
- * Outside the range of C every entry returns WESUP_ERR_INVALID.  Called with C = 2 each reproduces its two-class entry bit for bit.
+ * One kernel body per operation: called with C = 2 an entry launches the instantiation with the class count as a compile-time
+ * constant (prop_kernel, head_bwd_kernel, classifier_bwd_reduce: the two-class step's launch list does not move, and its bits are
+ * pinned to the last commit with two-class kernels of its own by tests/golden/head_two_class_bits.json), with more classes the one
+ * with the run-time count.  Outside the range of C every entry returns WESUP_ERR_INVALID.
  * wesup_classifier_fwd_c: pred (R, C) = softmax(feat (R, D) . Wc (C, D)^T + bc): logits by fmaf in ascending k, the maximum
  *   subtracted, exponentials summed in ascending class order, one reciprocal.  A streaming kernel (pixel inference runs it with
  *   R = B*H*W): Wc / bc in LDS once per block, rows as float4 where D % 4 == 0, logits in registers; D <= 512.

@@ -22,8 +22,9 @@ of this docstring.
 
 Which case reaches which branch (ids as pytest prints them):
 
-  prop_kernel / prop_c_kernel (wesup_propagate: C = 2, 3, 16 through prop_kernel; wesup_head_fwd: prop_kernel with the two-class tail;
-  wesup_head_fwd_c: prop_c_kernel).  Every case is a batch of 60 images, one per (n_l, n_sp - n_l) of
+  prop_kernel / prop_c_kernel, one body (wesup_propagate: C = 2, 3, 16 through prop_kernel; ops.head_fwd calls wesup_head_fwd_c:
+  prop_kernel with the two-class tail at C = 2, prop_c_kernel with cls_row beyond).  Every case is a batch of 60 images, one per
+  (n_l, n_sp - n_l) of
   {0, 1, 15, 16, 17, 63, 64, 65, 255, 256, 257, 513} x {0, 1, 5, 16, 40}, plus the image of planted ties from D = 32 on:
     no labelled row (nl <= 0: early return)          n_l = 0, every n_sp - n_l
     no unlabelled row / block wholly labelled        n_sp - n_l = 0; every block below n_l - 16
@@ -42,7 +43,8 @@ Which case reaches which branch (ids as pytest prints them):
     D = 150                                          test_too_wide_features_are_refused_on_the_host: return code only, nothing launched
     the raised limit inside a whole training step    test_a_model_of_64_features_trains_a_step_like_the_oracle (WESUP(D=64) against the oracle)
     enable = 0                                       every case (second half of test_propagation_against_fp64)
-  loss_fwd_kernel / loss_bwd_kernel / head_bwd_kernel / head_bwd_c_kernel: B = 6, Kmax = 640, n_sp = 0, 1, 255, 256, 257, 600 (no trip,
+  loss_fwd_kernel / loss_bwd_kernel / head_bwd_kernel / head_bwd_c_kernel (head_bwd_body<2> at C = 2, <0> beyond): B = 6,
+    Kmax = 640, n_sp = 0, 1, 255, 256, 257, 600 (no trip,
     part of one, one less than / exactly / one more than a trip of 256 threads, three trips), n_l = 0 | part | n_sp (patterns A, B),
     all-zero labelled rows, an image without any pseudo label, the six clamp-edge predictions in a labelled and an unlabelled row,
     garbage beyond n_sp; the fused launches bit for bit against the unfused ones on the same inputs; one NaN (test_nan_...)
@@ -253,7 +255,8 @@ def _same_bits(a, b):
 
 
 def _fused_equals_unfused(ops, c, m, pred, y_all, terms, dloss, dpred):
-    """wesup_head_bwd / wesup_head_bwd_c (+ the finish) on the same inputs: terms, dpred, dfeat, dWc, dbc bit for bit what loss_fwd,
+    """wesup_head_bwd_c (+ the finish; head_bwd_kernel at C = 2, head_bwd_c_kernel beyond) on the same inputs: terms, dpred, dfeat,
+    dWc, dbc bit for bit what loss_fwd,
     loss_bwd and classifier_bwd give -- the fp64 result of the unfused entries covers the fused ones."""
     d = dev()
     B, Kmax, C, D = hc.LOSS_B, hc.LOSS_KMAX, c['C'], hc.LOSS_D

@@ -1095,7 +1095,7 @@ def test_head_in_two_launches_equals_the_six_it_replaces_bit_for_bit(ops, seed, 
     assert torch.equal(terms2, terms) and torch.equal(dpred2, dpred) and torch.equal(dfeat2, dfeat)
     assert torch.equal(dWc2, dWc) and torch.equal(dbc2, dbc)
     assert float(dpred.abs().max()) > 0 and float(dfeat.abs().max()) > 0
-    assert not ops.head_bwd_supported(100, 2) and not ops.head_bwd_supported(64, 3)
+    assert ops.head_supported(64, 2) and not ops.head_supported(100, 2) and not ops.head_supported(64, 1)
 
 
 def test_cross_entropy_generic(ops):

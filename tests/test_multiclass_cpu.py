@@ -69,7 +69,7 @@ def test_buffer_table_sizes_sp_pred_by_the_class_count():
     assert by_name['cls_part'].shape == (max(ops.classifier_bwd_bytes(B * Kmax, 32, 3), 256),)
     assert ops.classifier_bwd_bytes(B * Kmax, 32, 3) == (B * Kmax // 64) * (3 * 32 + 3) * 4
     assert ops.classifier_bwd_bytes(B * Kmax, 32, 2) == ops._lib.load().wesup_classifier_bwd_workspace_bytes(B * Kmax, 32)
-    assert ops.head_c_supported(64, 3) and not ops.head_c_supported(100, 3) and not ops.head_bwd_supported(64, 3)
+    assert ops.head_supported(64, 3) and ops.head_supported(64, 2) and not ops.head_supported(100, 3) and not ops.head_supported(64, 17)
 
 
 def test_confusion_metrics_on_hand_made_tables():

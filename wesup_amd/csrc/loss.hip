@@ -18,124 +18,14 @@ __device__ __forceinline__ float block_sum256(float v, float* sh) {
     return r;
 }
 
-// ------------------------------------------------------------------ classifier Linear(D,2) + Softmax(dim=1)
-__global__ void classifier_fwd_kernel(const float* __restrict__ feat, const float* __restrict__ Wc,
-                                      const float* __restrict__ bc, float* __restrict__ pred, int R, int D) {
-    const int r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= R) return;
-    float z0 = bc[0], z1 = bc[1];
-    const float* f = feat + (long)r * D;
-    for (int k = 0; k < D; ++k) {
-        const float v = f[k];
-        z0 = fmaf(v, Wc[k], z0);
-        z1 = fmaf(v, Wc[D + k], z1);
-    }
-    const float m = fmaxf(z0, z1);
-    const float e0 = expf(z0 - m), e1 = expf(z1 - m);
-    const float inv = 1.f / (e0 + e1);
-    pred[2 * r] = e0 * inv;
-    pred[2 * r + 1] = e1 * inv;
-}
-extern "C" int wesup_classifier_fwd(const float* feat, const float* Wc, const float* bc, float* pred, int R, int D,
-                                    void* stream) {
-    if (!feat || !Wc || !bc || !pred || R <= 0 || D <= 0) return WESUP_ERR_INVALID;
-    WESUP_LAUNCH(classifier_fwd_kernel, dim3(ceil_div(R, 256)), dim3(256), 0, (hipStream_t)stream, feat, Wc, bc, pred,
-                       R, D);
-    WESUP_CHECK_LAUNCH();
-    return WESUP_OK;
-}
-
-// backward: dz = p * (dp - sum_c dp_c p_c); dfeat = (dz . Wc + extra) masked by feat > 0; partial dWc/dbc per 64 rows
-#define CLS_ROWS 64
-// The two sums of two products below are written with their one fused multiply-add spelled out: left to the compiler
-// (-ffp-contract=fast) either product may become the addend, and classifier_bwd_kernel and head_bwd_kernel -- which must agree
-// bit for bit -- are contracted separately.
-__device__ __forceinline__ void cls_dz(float p0, float p1, float d0, float d1, float& a, float& b) {
-    const float s = fmaf(d1, p1, d0 * p0);
-    a = p0 * (d0 - s);
-    b = p1 * (d1 - s);
-}
-__device__ __forceinline__ float cls_dfeat(float dz0, float dz1, float w0, float w1) { return fmaf(dz1, w1, dz0 * w0); }
-__global__ void classifier_bwd_kernel(const float* __restrict__ feat, const float* __restrict__ Wc,
-                                      const float* __restrict__ pred, const float* __restrict__ dpred,
-                                      const float* __restrict__ extra, float* __restrict__ dfeat,
-                                      float* __restrict__ part, int R, int D) {
-    __shared__ float dz[CLS_ROWS][2];
-    const int r0 = blockIdx.x * CLS_ROWS;
-    const int tid = threadIdx.x;                      // 256 threads
-    if (tid < CLS_ROWS) {
-        const int r = r0 + tid;
-        float a = 0.f, b = 0.f;
-        if (r < R) {
-            const float p0 = pred[2 * r], p1 = pred[2 * r + 1];
-            const float d0 = dpred[2 * r], d1 = dpred[2 * r + 1];
-            cls_dz(p0, p1, d0, d1, a, b);
-        }
-        dz[tid][0] = a;
-        dz[tid][1] = b;
-    }
-    __syncthreads();
-    // dfeat
-    for (int e = tid; e < CLS_ROWS * D; e += 256) {
-        const int rr = e / D, k = e - rr * D;
-        const int r = r0 + rr;
-        if (r < R) {
-            float g = cls_dfeat(dz[rr][0], dz[rr][1], Wc[k], Wc[D + k]);
-            if (extra) g += extra[(long)r * D + k];
-            dfeat[(long)r * D + k] = feat[(long)r * D + k] > 0.f ? g : 0.f;
-        }
-    }
-    // partial dWc[c][k] (2*D entries) and dbc[c] (2 entries) for this block of rows
-    float* pout = part + (long)blockIdx.x * (2 * D + 2);
-    for (int e = tid; e < 2 * D + 2; e += 256) {
-        float s = 0.f;
-        if (e < 2 * D) {
-            const int c = e / D, k = e - c * D;
-            for (int rr = 0; rr < CLS_ROWS; ++rr) {
-                const int r = r0 + rr;
-                if (r < R) s = fmaf(dz[rr][c], feat[(long)r * D + k], s);
-            }
-        } else {
-            const int c = e - 2 * D;
-            for (int rr = 0; rr < CLS_ROWS; ++rr) s += dz[rr][c];
-        }
-        pout[e] = s;
-    }
-}
-__global__ void classifier_bwd_reduce(const float* __restrict__ part, float* __restrict__ dWc, float* __restrict__ dbc,
-                                      int nblk, int D) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= 2 * D + 2) return;
-    float s = 0.f;
-    for (int b = 0; b < nblk; ++b) s += part[(long)b * (2 * D + 2) + e];
-    if (e < 2 * D) dWc[e] = s;
-    else dbc[e - 2 * D] = s;
-}
-extern "C" size_t wesup_classifier_bwd_workspace_bytes(int R, int D) {
-    if (R <= 0 || D <= 0) return 0;
-    return (size_t)ceil_div(R, CLS_ROWS) * (2 * D + 2) * sizeof(float);
-}
-extern "C" int wesup_classifier_bwd(const float* feat, const float* Wc, const float* pred, const float* dpred,
-                                    const float* dfeat_extra, float* dfeat, float* dWc, float* dbc, int R, int D,
-                                    void* ws, size_t ws_bytes, void* stream) {
-    if (!feat || !Wc || !pred || !dpred || !dfeat || !dWc || !dbc || !ws || R <= 0 || D <= 0) return WESUP_ERR_INVALID;
-    if (ws_bytes < wesup_classifier_bwd_workspace_bytes(R, D)) return WESUP_ERR_WORKSPACE;
-    const int nblk = ceil_div(R, CLS_ROWS);
-    hipStream_t st = (hipStream_t)stream;
-    WESUP_LAUNCH(classifier_bwd_kernel, dim3(nblk), dim3(256), 0, st, feat, Wc, pred, dpred, dfeat_extra, dfeat,
-                       (float*)ws, R, D);
-    WESUP_LAUNCH(classifier_bwd_reduce, dim3(ceil_div(2 * D + 2, 64)), dim3(64), 0, st, (const float*)ws, dWc, dbc,
-                       nblk, D);
-    WESUP_CHECK_LAUNCH();
-    return WESUP_OK;
-}
-
 // ------------------------------------------------------------------ classifier Linear(D,C) + Softmax(dim=1), 2 <= C <= WESUP_MAX_CLASSES
-// The two-class kernels above stay as they are (the step's launch list and bits at C = 2 do not move); these are reached for a
-// classifier of more than two classes, and reproduce the two-class entries bit for bit when called with C = 2.
+// One body per operation.  Two classes -- the training step -- are instantiated with the class count as a compile-time constant
+// (cls_row<2, .>, the <2> forms of the backward bodies), more classes with the run-time count; the two-class entries call the _c
+// entries with C = 2, which launch the two-class instantiations.
 // One row: logits by fmaf in ascending k, the maximum subtracted, the exponentials summed in ascending class order, one
 // reciprocal.  The logits live in registers: z[] is indexed by unrolled constants only, CMAX >= C bounds it at compile time.
-// W: [C][D] and bias [C], in LDS (classifier_fwd_c_kernel) or global memory (prop_body's tail) -- the arithmetic is the same.
+// W: [C][D] and bias [C], in LDS (classifier_fwd_c_kernel) or global memory (its form for a table beyond the LDS, and prop_body's
+// tail) -- the arithmetic is the same.
 template <int CMAX, bool VEC4>
 __device__ __forceinline__ void cls_row(const float* __restrict__ f, const float* W, const float* bias, float* __restrict__ out,
                                         int D, int C, bool st4_ok = false) {
@@ -188,18 +78,24 @@ __device__ __forceinline__ void cls_row(const float* __restrict__ f, const float
 }
 // Streaming form (pixel inference runs it with R = B*H*W): Wc and bc staged in LDS once per block (every lane reads the same
 // address: a broadcast), a thread per row, rows read as float4 where D % 4 == 0, at most 2048 blocks that stride over the rows.
-template <int CMAX, bool VEC4>
+// LDS = false: no staging, cls_row reads Wc / bc themselves (a table larger than the LDS a kernel gets without asking).
+template <int CMAX, bool VEC4, bool LDS = true>
 __global__ __launch_bounds__(256) void classifier_fwd_c_kernel(const float* __restrict__ feat, const float* __restrict__ Wc,
                                                                const float* __restrict__ bc, float* __restrict__ pred, int R,
                                                                int D, int C, int st4_ok) {
     extern __shared__ __align__(16) float shw[];                  // [C][D] | [C]
-    for (int e = threadIdx.x; e < C * D; e += 256) shw[e] = Wc[e];
-    if (threadIdx.x < C) shw[C * D + threadIdx.x] = bc[threadIdx.x];
-    __syncthreads();
-    for (long r = (long)blockIdx.x * 256 + threadIdx.x; r < R; r += (long)gridDim.x * 256)
-        cls_row<CMAX, VEC4>(feat + r * D, shw, shw + C * D, pred + r * C, D, C, st4_ok != 0);
+    if constexpr (LDS) {
+        for (int e = threadIdx.x; e < C * D; e += 256) shw[e] = Wc[e];
+        if (threadIdx.x < C) shw[C * D + threadIdx.x] = bc[threadIdx.x];
+        __syncthreads();
+    }
+    for (long r = (long)blockIdx.x * 256 + threadIdx.x; r < R; r += (long)gridDim.x * 256) {
+        if constexpr (LDS) cls_row<CMAX, VEC4>(feat + r * D, shw, shw + C * D, pred + r * C, D, C, st4_ok != 0);
+        else cls_row<CMAX, false>(feat + r * D, Wc, bc, pred + r * C, D, C, st4_ok != 0);
+    }
 }
 #define CLS_C_MAX_D 512                             // (C * D + C floats of LDS: 32 KB at C = 16)
+#define CLS_LDS_DEFAULT (64 * 1024)                 // (the dynamic LDS a kernel gets without asking)
 static inline bool cls_c_range(int C) { return C >= 2 && C <= WESUP_MAX_CLASSES; }
 template <int CMAX>
 static int classifier_fwd_c_launch(const float* feat, const float* Wc, const float* bc, float* pred, int R, int D, int C,
@@ -207,13 +103,21 @@ static int classifier_fwd_c_launch(const float* feat, const float* Wc, const flo
     const bool vec = (D % 4 == 0) && (((uintptr_t)feat & 15) == 0);
     const int st4_ok = (C % 4 == 0) && (((uintptr_t)pred & 15) == 0);
     const int blocks = min(ceil_div(R, 256), 2048);
-    const size_t lds = (size_t)(C * D + C) * sizeof(float);
-    if (vec)
+    const size_t lds = ((size_t)C * D + C) * sizeof(float);
+    if (CMAX == 2 && lds > CLS_LDS_DEFAULT)         // D >= 8192: wesup_classifier_fwd alone takes any D, the _c entry D <= 512
+        WESUP_LAUNCH((classifier_fwd_c_kernel<2, false, false>), dim3(blocks), dim3(256), 0, st, feat, Wc, bc, pred, R, D, C, st4_ok);
+    else if (vec)
         WESUP_LAUNCH((classifier_fwd_c_kernel<CMAX, true>), dim3(blocks), dim3(256), lds, st, feat, Wc, bc, pred, R, D, C, st4_ok);
     else
         WESUP_LAUNCH((classifier_fwd_c_kernel<CMAX, false>), dim3(blocks), dim3(256), lds, st, feat, Wc, bc, pred, R, D, C, st4_ok);
     WESUP_CHECK_LAUNCH();
     return WESUP_OK;
+}
+// two classes, any D > 0 (models/wesup.py:229-232,292)
+extern "C" int wesup_classifier_fwd(const float* feat, const float* Wc, const float* bc, float* pred, int R, int D,
+                                    void* stream) {
+    if (!feat || !Wc || !bc || !pred || R <= 0 || D <= 0) return WESUP_ERR_INVALID;
+    return classifier_fwd_c_launch<2>(feat, Wc, bc, pred, R, D, 2, (hipStream_t)stream);
 }
 extern "C" int wesup_classifier_fwd_c(const float* feat, const float* Wc, const float* bc, float* pred, int R, int D, int C,
                                       void* stream) {
@@ -226,38 +130,41 @@ extern "C" int wesup_classifier_fwd_c(const float* feat, const float* Wc, const 
 }
 
 // backward, C classes: dz_c = p_c (dp_c - sum_j dp_j p_j); dfeat = (sum_c dz_c Wc[c][k] + extra) masked by feat > 0; partial
-// dWc / dbc per 64 rows, reduced in fixed order.  The class sums are written as cls_dz / cls_dfeat write theirs: the first
-// product, then fmaf in ascending class order -- the unfused kernel, the fused one (head_bwd_c_kernel) and, at C = 2, the
-// two-class kernels agree bit for bit.  No per-thread array: a row's dpred waits in its LDS row of dz.
+// dWc / dbc per 64 rows, reduced in fixed order.  The class sums are written with their fused multiply-adds spelled out: the
+// first product, then fmaf in ascending class order.  Left to the compiler (-ffp-contract=fast) either product of a sum of two
+// may become the addend, and the instantiations -- unfused and fused (head_bwd_body), two classes and C -- which must agree bit
+// for bit, are contracted separately.  No per-thread array: a row's dpred waits in its LDS row of dz.
+// CT: the class count where it is a compile-time constant (2: the training step), 0: the run-time C.  CT sizes a row of dz.
+#define CLS_ROWS 64
+static constexpr int cls_dz_width(int CT) { return CT ? CT : WESUP_MAX_CLASSES; }
 __device__ __forceinline__ void cls_dz_row(const float* __restrict__ p, float* dzrow, int C) {
     float s = dzrow[0] * p[0];
     for (int c = 1; c < C; ++c) s = fmaf(dzrow[c], p[c], s);
     for (int c = 0; c < C; ++c) dzrow[c] = p[c] * (dzrow[c] - s);
 }
-// dfeat of the block's rows and the block's partial sums, from dz[CLS_ROWS][WESUP_MAX_CLASSES] in LDS (behind a __syncthreads)
-__device__ __forceinline__ void cls_bwd_c_tail(const float* __restrict__ feat, const float* __restrict__ Wc,
-                                               const float* __restrict__ extra, float* __restrict__ dfeat,
-                                               float* __restrict__ pout, const float (*dz)[WESUP_MAX_CLASSES], long r0, long R,
-                                               int D, int C) {
+// dfeat of the block's rows and the block's partial sums, from dz[CLS_ROWS][cls_dz_width(CT)] in LDS (behind a __syncthreads).
+// nrow: how many of the block's CLS_ROWS rows exist (their dz beyond is zero); a constant where the caller knows it, so that the
+// loops over the rows carry no test and their loads go out together.
+template <int CT>
+__device__ __forceinline__ void cls_bwd_tail(const float* __restrict__ feat, const float* __restrict__ Wc,
+                                             const float* __restrict__ extra, float* __restrict__ dfeat,
+                                             float* __restrict__ part, const float (*dz)[cls_dz_width(CT)], long r0, int nrow, int D,
+                                             int C) {
     const int tid = threadIdx.x;
-    for (int e = tid; e < CLS_ROWS * D; e += 256) {
+    float* pout = part + (long)blockIdx.x * (C * D + C);
+    for (int e = tid; e < nrow * D; e += 256) {
         const int rr = e / D, k = e - rr * D;
         const long r = r0 + rr;
-        if (r < R) {
-            float g = dz[rr][0] * Wc[k];
-            for (int c = 1; c < C; ++c) g = fmaf(dz[rr][c], Wc[c * D + k], g);
-            if (extra) g += extra[r * D + k];
-            dfeat[r * D + k] = feat[r * D + k] > 0.f ? g : 0.f;
-        }
+        float g = dz[rr][0] * Wc[k];
+        for (int c = 1; c < C; ++c) g = fmaf(dz[rr][c], Wc[c * D + k], g);
+        if (extra) g += extra[r * D + k];
+        dfeat[r * D + k] = feat[r * D + k] > 0.f ? g : 0.f;
     }
     for (int e = tid; e < C * D + C; e += 256) {
         float s = 0.f;
         if (e < C * D) {
             const int c = e / D, k = e - c * D;
-            for (int rr = 0; rr < CLS_ROWS; ++rr) {
-                const long r = r0 + rr;
-                if (r < R) s = fmaf(dz[rr][c], feat[r * D + k], s);
-            }
+            for (int rr = 0; rr < nrow; ++rr) s = fmaf(dz[rr][c], feat[(r0 + rr) * D + k], s);
         } else {
             const int c = e - C * D;
             for (int rr = 0; rr < CLS_ROWS; ++rr) s += dz[rr][c];
@@ -265,11 +172,13 @@ __device__ __forceinline__ void cls_bwd_c_tail(const float* __restrict__ feat, c
         pout[e] = s;
     }
 }
+template <int CT>
 __global__ __launch_bounds__(256) void classifier_bwd_c_kernel(const float* __restrict__ feat, const float* __restrict__ Wc,
                                                                const float* __restrict__ pred, const float* __restrict__ dpred,
                                                                const float* __restrict__ extra, float* __restrict__ dfeat,
-                                                               float* __restrict__ part, int R, int D, int C) {
-    __shared__ float dz[CLS_ROWS][WESUP_MAX_CLASSES];
+                                                               float* __restrict__ part, int R, int D, int C_rt) {
+    __shared__ float dz[CLS_ROWS][cls_dz_width(CT)];
+    const int C = CT ? CT : C_rt;
     const long r0 = (long)blockIdx.x * CLS_ROWS;
     const int tid = threadIdx.x;
     if (tid < CLS_ROWS) {
@@ -282,16 +191,32 @@ __global__ __launch_bounds__(256) void classifier_bwd_c_kernel(const float* __re
         }
     }
     __syncthreads();
-    cls_bwd_c_tail(feat, Wc, extra, dfeat, part + (long)blockIdx.x * (C * D + C), dz, r0, R, D, C);
+    cls_bwd_tail<CT>(feat, Wc, extra, dfeat, part, dz, r0, (int)min((long)CLS_ROWS, R - r0), D, C);
 }
-__global__ void classifier_bwd_c_reduce(const float* __restrict__ part, float* __restrict__ dWc, float* __restrict__ dbc,
-                                        int nblk, int D, int C) {
+// dWc / dbc: the blocks' partial sums added in ascending block order.  (Two plain kernels: the recorded two-class step names
+// classifier_bwd_reduce.)
+__device__ __forceinline__ void cls_reduce(const float* __restrict__ part, float* __restrict__ dWc, float* __restrict__ dbc,
+                                           int nblk, int D, int C) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= C * D + C) return;
     float s = 0.f;
     for (int b = 0; b < nblk; ++b) s += part[(long)b * (C * D + C) + e];
     if (e < C * D) dWc[e] = s;
     else dbc[e - C * D] = s;
+}
+__global__ void classifier_bwd_reduce(const float* __restrict__ part, float* __restrict__ dWc, float* __restrict__ dbc,
+                                      int nblk, int D) {
+    cls_reduce(part, dWc, dbc, nblk, D, 2);
+}
+__global__ void classifier_bwd_c_reduce(const float* __restrict__ part, float* __restrict__ dWc, float* __restrict__ dbc,
+                                        int nblk, int D, int C) {
+    cls_reduce(part, dWc, dbc, nblk, D, C);
+}
+static void cls_reduce_launch(const void* ws, float* dWc, float* dbc, int R, int D, int C, hipStream_t st) {
+    const dim3 grid(ceil_div(C * D + C, 64));
+    const int nblk = ceil_div(R, CLS_ROWS);
+    if (C == 2) WESUP_LAUNCH(classifier_bwd_reduce, grid, dim3(64), 0, st, (const float*)ws, dWc, dbc, nblk, D);
+    else WESUP_LAUNCH(classifier_bwd_c_reduce, grid, dim3(64), 0, st, (const float*)ws, dWc, dbc, nblk, D, C);
 }
 extern "C" size_t wesup_classifier_bwd_c_workspace_bytes(int R, int D, int C) {
     if (R <= 0 || D <= 0 || !cls_c_range(C)) return 0;
@@ -303,13 +228,20 @@ extern "C" int wesup_classifier_bwd_c(const float* feat, const float* Wc, const 
     if (!feat || !Wc || !pred || !dpred || !dfeat || !dWc || !dbc || !ws || R <= 0 || D <= 0 || !cls_c_range(C))
         return WESUP_ERR_INVALID;
     if (ws_bytes < wesup_classifier_bwd_c_workspace_bytes(R, D, C)) return WESUP_ERR_WORKSPACE;
-    const int nblk = ceil_div(R, CLS_ROWS);
+    const dim3 grid(ceil_div(R, CLS_ROWS));
     hipStream_t st = (hipStream_t)stream;
-    WESUP_LAUNCH(classifier_bwd_c_kernel, dim3(nblk), dim3(256), 0, st, feat, Wc, pred, dpred, dfeat_extra, dfeat, (float*)ws, R,
-                 D, C);
-    WESUP_LAUNCH(classifier_bwd_c_reduce, dim3(ceil_div(C * D + C, 64)), dim3(64), 0, st, (const float*)ws, dWc, dbc, nblk, D, C);
+    if (C == 2) WESUP_LAUNCH(classifier_bwd_c_kernel<2>, grid, dim3(256), 0, st, feat, Wc, pred, dpred, dfeat_extra, dfeat, (float*)ws, R, D, C);
+    else WESUP_LAUNCH(classifier_bwd_c_kernel<0>, grid, dim3(256), 0, st, feat, Wc, pred, dpred, dfeat_extra, dfeat, (float*)ws, R, D, C);
+    cls_reduce_launch(ws, dWc, dbc, R, D, C, st);
     WESUP_CHECK_LAUNCH();
     return WESUP_OK;
+}
+// two classes: the _c entries with C = 2
+extern "C" size_t wesup_classifier_bwd_workspace_bytes(int R, int D) { return wesup_classifier_bwd_c_workspace_bytes(R, D, 2); }
+extern "C" int wesup_classifier_bwd(const float* feat, const float* Wc, const float* pred, const float* dpred,
+                                    const float* dfeat_extra, float* dfeat, float* dWc, float* dbc, int R, int D,
+                                    void* ws, size_t ws_bytes, void* stream) {
+    return wesup_classifier_bwd_c(feat, Wc, pred, dpred, dfeat_extra, dfeat, dWc, dbc, R, D, 2, ws, ws_bytes, stream);
 }
 
 // ------------------------------------------------------------------ label propagation (models/wesup.py:99-139)
@@ -355,28 +287,30 @@ __device__ __forceinline__ void prop_body(float* sh, const float* __restrict__ f
         src_idx[(long)b * Kmax + i_blk + tid] = -1;
         max_sim[(long)b * Kmax + i_blk + tid] = 0.f;
     }
-    // wesup_head_fwd: the classifier + softmax of this block's rows rides along (classifier_fwd_kernel's arithmetic, row by row:
-    // a launch of its own on the chain between the fc layers and the loss otherwise)
-    if constexpr (GENERIC) {
-        // wesup_head_fwd_c: classifier_fwd_c_kernel's arithmetic (cls_row), C columns per row
-        if (pred && tid < PROP_ROWS && i_blk + tid < Kmax) {
-            const long r = (long)b * Kmax + i_blk + tid;
-            cls_row<WESUP_MAX_CLASSES, false>(feat + r * D, Wc, bc, pred + r * C, D, C);
-        }
-    } else if (pred && tid < PROP_ROWS && i_blk + tid < Kmax) {
+    // wesup_head_fwd / wesup_head_fwd_c: the classifier + softmax of this block's rows rides along (classifier_fwd_c_kernel's
+    // arithmetic, cls_row: a launch of its own on the chain between the fc layers and the loss otherwise).  prop_kernel writes two
+    // columns per row whatever the label width C, prop_c_kernel C columns.
+    // prop_kernel's tail is cls_row<2, false> typed out, the one two-class body that is kept: as a call the compiler schedules its
+    // end with one more s_nop, the propagation loops behind it start 4 bytes later and wesup_head_fwd takes 2.5 % longer at the
+    // step's shape (Measured).  Its bits are held to cls_row's by the fused-against-unfused tests.
+    if (pred && tid < PROP_ROWS && i_blk + tid < Kmax) {
         const long r = (long)b * Kmax + i_blk + tid;
-        float z0 = bc[0], z1 = bc[1];
-        const float* f = feat + r * D;
-        for (int k = 0; k < D; ++k) {
-            const float v = f[k];
-            z0 = fmaf(v, Wc[k], z0);
-            z1 = fmaf(v, Wc[D + k], z1);
+        if constexpr (GENERIC) {
+            cls_row<WESUP_MAX_CLASSES, false>(feat + r * D, Wc, bc, pred + r * C, D, C);
+        } else {
+            float z0 = bc[0], z1 = bc[1];
+            const float* f = feat + r * D;
+            for (int k = 0; k < D; ++k) {
+                const float v = f[k];
+                z0 = fmaf(v, Wc[k], z0);
+                z1 = fmaf(v, Wc[D + k], z1);
+            }
+            const float m = fmaxf(z0, z1);
+            const float e0 = expf(z0 - m), e1 = expf(z1 - m);
+            const float inv = 1.f / (e0 + e1);
+            pred[2 * r] = e0 * inv;
+            pred[2 * r + 1] = e1 * inv;
         }
-        const float m = fmaxf(z0, z1);
-        const float e0 = expf(z0 - m), e1 = expf(z1 - m);
-        const float inv = 1.f / (e0 + e1);
-        pred[2 * r] = e0 * inv;
-        pred[2 * r + 1] = e1 * inv;
     }
     // rows of this block that take part in the propagation: unlabelled and present (uniform per block)
     if (!enable || nl <= 0 || i_blk + PROP_ROWS <= nl || i_blk >= ns) return;
@@ -462,16 +396,23 @@ __global__ __launch_bounds__(256) void prop_c_kernel(const float* __restrict__ f
     extern __shared__ float sh[];
     prop_body<true>(sh, feat, sp_labels, n_sp, n_l, thr, enable, y_all, src_idx, max_sim, Kmax, D, C, Wc, bc, pred);
 }
-// what the three entries below do about that size before they launch: WESUP_ERR_INVALID beyond the CU's LDS, the kernel's
-// dynamic-LDS limit raised (once per kernel) where the default does not hold it
+// The launch of the four entries below.  About that size first: WESUP_ERR_INVALID beyond the CU's LDS, the kernel's dynamic-LDS
+// limit raised (once per kernel) where the default does not hold it.
 template <bool GENERIC>
-static int prop_lds_ready(size_t lds) {
+static int prop_launch(const float* feat, const float* Wc, const float* bc, float* pred, const float* sp_labels,
+                       const int32_t* n_sp, const int32_t* n_l, float threshold, int enable, float* y_all, int32_t* src_idx,
+                       float* max_sim, int B, int Kmax, int D, int C, void* stream) {
+    constexpr auto kernel = GENERIC ? prop_c_kernel : prop_kernel;
+    const size_t lds = prop_lds_bytes(D);
     if (lds > PROP_LDS_MAX) return WESUP_ERR_INVALID;
     if (lds > PROP_LDS_DEFAULT) {
-        static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(GENERIC ? prop_c_kernel : prop_kernel),
+        static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
                                                            hipFuncAttributeMaxDynamicSharedMemorySize, PROP_LDS_MAX);
         if (attr != hipSuccess) return WESUP_ERR_LAUNCH;
     }
+    WESUP_LAUNCH(kernel, dim3(ceil_div(Kmax, PROP_ROWS), B), dim3(256), lds, (hipStream_t)stream, feat, sp_labels, n_sp, n_l,
+                 threshold, enable, y_all, src_idx, max_sim, Kmax, D, C, Wc, bc, pred);
+    WESUP_CHECK_LAUNCH();
     return WESUP_OK;
 }
 extern "C" int wesup_propagate(const float* feat, const float* sp_labels, const int32_t* n_sp, const int32_t* n_l,
@@ -480,29 +421,29 @@ extern "C" int wesup_propagate(const float* feat, const float* sp_labels, const 
     if (!feat || !sp_labels || !n_sp || !n_l || !y_all || !src_idx || !max_sim || B <= 0 || Kmax <= 0 || D <= 0 ||
         D > WESUP_HEAD_MAX_D || C <= 0)
         return WESUP_ERR_INVALID;
-    hipStream_t st = (hipStream_t)stream;
-    const size_t lds = prop_lds_bytes(D);
-    if (const int rc = prop_lds_ready<false>(lds); rc != WESUP_OK) return rc;
-    WESUP_LAUNCH(prop_kernel, dim3(ceil_div(Kmax, PROP_ROWS), B), dim3(256), lds, st, feat, sp_labels, n_sp, n_l, threshold,
-                 enable, y_all, src_idx, max_sim, Kmax, D, C, (const float*)nullptr, (const float*)nullptr, (float*)nullptr);
-    WESUP_CHECK_LAUNCH();
-    return WESUP_OK;
+    return prop_launch<false>(feat, nullptr, nullptr, nullptr, sp_labels, n_sp, n_l, threshold, enable, y_all, src_idx, max_sim, B,
+                              Kmax, D, C, stream);
 }
-// classifier + softmax (wesup_classifier_fwd) and label propagation (wesup_propagate) of the same features in ONE launch: both
-// read feat, neither reads the other's result.  pred (B*Kmax, 2).  Bit-identical to the two entries.
+// classifier + softmax (wesup_classifier_fwd_c) and label propagation (wesup_propagate) of the same features in ONE launch: both
+// read feat, neither reads the other's result.  Bit-identical to the two entries.  wesup_head_fwd: pred (B*Kmax, 2), labels of any
+// width C; wesup_head_fwd_c: pred (B*Kmax, C), and prop_kernel again where C = 2.
 extern "C" int wesup_head_fwd(const float* feat, const float* Wc, const float* bc, float* pred, const float* sp_labels,
                               const int32_t* n_sp, const int32_t* n_l, float threshold, int enable, float* y_all,
                               int32_t* src_idx, float* max_sim, int B, int Kmax, int D, int C, void* stream) {
     if (!feat || !Wc || !bc || !pred || !sp_labels || !n_sp || !n_l || !y_all || !src_idx || !max_sim || B <= 0 || Kmax <= 0 ||
         D <= 0 || D > WESUP_HEAD_MAX_D || C <= 0)
         return WESUP_ERR_INVALID;
-    hipStream_t st = (hipStream_t)stream;
-    const size_t lds = prop_lds_bytes(D);
-    if (const int rc = prop_lds_ready<false>(lds); rc != WESUP_OK) return rc;
-    WESUP_LAUNCH(prop_kernel, dim3(ceil_div(Kmax, PROP_ROWS), B), dim3(256), lds, st, feat, sp_labels, n_sp, n_l, threshold,
-                 enable, y_all, src_idx, max_sim, Kmax, D, C, Wc, bc, pred);
-    WESUP_CHECK_LAUNCH();
-    return WESUP_OK;
+    return prop_launch<false>(feat, Wc, bc, pred, sp_labels, n_sp, n_l, threshold, enable, y_all, src_idx, max_sim, B, Kmax, D, C,
+                              stream);
+}
+extern "C" int wesup_head_fwd_c(const float* feat, const float* Wc, const float* bc, float* pred, const float* sp_labels,
+                                const int32_t* n_sp, const int32_t* n_l, float threshold, int enable, float* y_all,
+                                int32_t* src_idx, float* max_sim, int B, int Kmax, int D, int C, void* stream) {
+    if (!feat || !Wc || !bc || !pred || !sp_labels || !n_sp || !n_l || !y_all || !src_idx || !max_sim || B <= 0 || Kmax <= 0 ||
+        D <= 0 || D > WESUP_HEAD_MAX_D || !cls_c_range(C))
+        return WESUP_ERR_INVALID;
+    return (C == 2 ? prop_launch<false> : prop_launch<true>)(feat, Wc, bc, pred, sp_labels, n_sp, n_l, threshold, enable, y_all,
+                                                             src_idx, max_sim, B, Kmax, D, C, stream);
 }
 
 // ------------------------------------------------------------------ loss (models/wesup.py:66-96, 492-531)
@@ -604,24 +545,23 @@ extern "C" int wesup_loss_bwd(const float* pred, const float* y_all, const int32
     return WESUP_OK;
 }
 
-// Loss, its gradient and the classifier's backward in ONE launch (wesup_loss_fwd + wesup_loss_bwd + wesup_classifier_bwd's first
+// Loss, its gradient and the classifier's backward in ONE launch (wesup_loss_fwd + wesup_loss_bwd + wesup_classifier_bwd_c's first
 // kernel: three launches on the chain between the fc layers' forward and backward).  A block owns CLS_ROWS = 64 rows of one image
 // (Kmax % 64 == 0).  The per-image sums the gradient needs are a reduction over the whole image: every block of an image forms
 // them ITSELF, with loss_fwd_kernel's loop and tree -- the same numbers in every block, no hand-off between blocks; the image's
-// first block writes them to terms.  Then dpred of the block's rows (loss_bwd_kernel's expression) and classifier_bwd_kernel's
-// body on them.  Two classes (the classifier is Linear(D, 2)).  Bit-identical to the three entries.
-__global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__ feat, const float* __restrict__ Wc,
-                                                       const float* __restrict__ pred, const float* __restrict__ y_all,
-                                                       const int32_t* __restrict__ n_sp, const int32_t* __restrict__ n_l,
-                                                       const float* __restrict__ dloss, float eps, float prop_weight,
-                                                       float* __restrict__ terms, float* __restrict__ dpred,
-                                                       float* __restrict__ dfeat, float* __restrict__ part, int B, int Kmax,
-                                                       int D) {
-    constexpr int C = 2;
-    __shared__ float sh[256];
-    __shared__ float dz[CLS_ROWS][2];
+// first block writes them to terms.  Then dpred of the block's rows (loss_bwd_kernel's expression) and classifier_bwd_c_kernel's
+// body on them.  Bit-identical to the three entries.  (The body of head_bwd_kernel, CT = 2, and of head_bwd_c_kernel, CT = 0.)
+template <int CT>
+__device__ __forceinline__ void head_bwd_body(float* sh, float (*dz)[cls_dz_width(CT)], const float* __restrict__ feat,
+                                              const float* __restrict__ Wc, const float* __restrict__ pred,
+                                              const float* __restrict__ y_all, const int32_t* __restrict__ n_sp,
+                                              const int32_t* __restrict__ n_l, const float* __restrict__ dloss, float eps,
+                                              float prop_weight, float* __restrict__ terms, float* __restrict__ dpred,
+                                              float* __restrict__ dfeat, float* __restrict__ part, int B, int Kmax, int D,
+                                              int C_rt) {
+    const int C = CT ? CT : C_rt;
     const int tid = threadIdx.x;
-    const int r0 = blockIdx.x * CLS_ROWS;                 // first row (of B * Kmax) of this block
+    const int r0 = blockIdx.x * CLS_ROWS;                 // first row (of B * Kmax, an int) of this block
     const int b = r0 / Kmax, i0 = r0 - b * Kmax;
     const int ns = n_sp[b], nl = n_l[b];
     float sup = 0.f, supc = 0.f, pro = 0.f, proc = 0.f, plab = 0.f;
@@ -652,85 +592,36 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__
     if (tid < CLS_ROWS) {
         const int r = i0 + tid;                           // row inside the image (< Kmax)
         const long gr = (long)r0 + tid;
-        float g0 = 0.f, g1 = 0.f;
-        const float p0 = pred[2 * gr], p1 = pred[2 * gr + 1];
+        float coef = 0.f;
         if (r < ns) {
-            float coef;
             if (r < nl) coef = (supc > 0.f) ? 1.f / supc : 0.f;
             else coef = (nl < ns && proc > 0.f) ? prop_weight / proc : 0.f;
-            if (p0 >= eps && p0 <= 1.f - eps) g0 = dloss[0] * (1.f / (float)B) * coef * (-y_all[2 * gr] / p0);
-            if (p1 >= eps && p1 <= 1.f - eps) g1 = dloss[0] * (1.f / (float)B) * coef * (-y_all[2 * gr + 1] / p1);
         }
-        dpred[2 * gr] = g0;
-        dpred[2 * gr + 1] = g1;
-        float a, bq;
-        cls_dz(p0, p1, g0, g1, a, bq);
-        dz[tid][0] = a;
-        dz[tid][1] = bq;
+        // (p and y of every class are read whatever the tests say, and dpred is stored behind the loop: the loads of a row go out
+        // together, not one round trip to memory after the other)
+        for (int c = 0; c < C; ++c) {
+            const float p = pred[gr * C + c], y = y_all[gr * C + c];
+            const float g = dloss[0] * (1.f / (float)B) * coef * (-y / p);
+            dz[tid][c] = (r < ns && p >= eps && p <= 1.f - eps) ? g : 0.f;
+        }
+        for (int c = 0; c < C; ++c) dpred[gr * C + c] = dz[tid][c];
+        cls_dz_row(pred + gr * C, dz[tid], C);
     }
     __syncthreads();
-    for (int e = tid; e < CLS_ROWS * D; e += 256) {
-        const int rr = e / D, k = e - rr * D;
-        const long r = (long)r0 + rr;
-        const float g = cls_dfeat(dz[rr][0], dz[rr][1], Wc[k], Wc[D + k]);
-        dfeat[r * D + k] = feat[r * D + k] > 0.f ? g : 0.f;
-    }
-    float* pout = part + (long)blockIdx.x * (2 * D + 2);
-    for (int e = tid; e < 2 * D + 2; e += 256) {
-        float s = 0.f;
-        if (e < 2 * D) {
-            const int c = e / D, k = e - c * D;
-            for (int rr = 0; rr < CLS_ROWS; ++rr) s = fmaf(dz[rr][c], feat[((long)r0 + rr) * D + k], s);
-        } else {
-            const int c = e - 2 * D;
-            for (int rr = 0; rr < CLS_ROWS; ++rr) s += dz[rr][c];
-        }
-        pout[e] = s;
-    }
+    cls_bwd_tail<CT>(feat, Wc, nullptr, dfeat, part, dz, r0, CLS_ROWS, D, C);   // (Kmax % CLS_ROWS == 0: every row exists)
 }
-// ws: wesup_classifier_bwd_workspace_bytes(B * Kmax, D); it holds the per-block partial sums of the classifier's weight gradient
-// until wesup_classifier_bwd_finish adds them up (any stream behind this launch: nothing on the way to the fc layers' gradients
-// reads dWc / dbc).
-extern "C" int wesup_head_bwd(const float* feat, const float* Wc, const float* pred, const float* y_all, const int32_t* n_sp,
-                              const int32_t* n_l, const float* dloss, float eps, float prop_weight, float* terms, float* dpred,
-                              float* dfeat, int B, int Kmax, int D, int C, void* ws, size_t ws_bytes, void* stream) {
-    if (!feat || !Wc || !pred || !y_all || !n_sp || !n_l || !dloss || !terms || !dpred || !dfeat || !ws || B <= 0 || Kmax <= 0 ||
-        (Kmax % CLS_ROWS) || D <= 0 || C != 2)
-        return WESUP_ERR_INVALID;
-    const int R = B * Kmax;
-    if (ws_bytes < wesup_classifier_bwd_workspace_bytes(R, D)) return WESUP_ERR_WORKSPACE;
-    WESUP_LAUNCH(head_bwd_kernel, dim3(R / CLS_ROWS), dim3(256), 0, (hipStream_t)stream, feat, Wc, pred, y_all, n_sp, n_l, dloss,
-                 eps, prop_weight, terms, dpred, dfeat, (float*)ws, B, Kmax, D);
-    WESUP_CHECK_LAUNCH();
-    return WESUP_OK;
+// (plain kernels under the names a recorded step holds)
+__global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__ feat, const float* __restrict__ Wc,
+                                                       const float* __restrict__ pred, const float* __restrict__ y_all,
+                                                       const int32_t* __restrict__ n_sp, const int32_t* __restrict__ n_l,
+                                                       const float* __restrict__ dloss, float eps, float prop_weight,
+                                                       float* __restrict__ terms, float* __restrict__ dpred,
+                                                       float* __restrict__ dfeat, float* __restrict__ part, int B, int Kmax,
+                                                       int D) {
+    __shared__ float sh[256];
+    __shared__ float dz[CLS_ROWS][2];
+    head_bwd_body<2>(sh, dz, feat, Wc, pred, y_all, n_sp, n_l, dloss, eps, prop_weight, terms, dpred, dfeat, part, B, Kmax, D, 2);
 }
-extern "C" int wesup_classifier_bwd_finish(const void* ws, size_t ws_bytes, float* dWc, float* dbc, int R, int D, void* stream) {
-    if (!ws || !dWc || !dbc || R <= 0 || D <= 0) return WESUP_ERR_INVALID;
-    if (ws_bytes < wesup_classifier_bwd_workspace_bytes(R, D)) return WESUP_ERR_WORKSPACE;
-    WESUP_LAUNCH(classifier_bwd_reduce, dim3(ceil_div(2 * D + 2, 64)), dim3(64), 0, (hipStream_t)stream, (const float*)ws, dWc,
-                 dbc, ceil_div(R, CLS_ROWS), D);
-    WESUP_CHECK_LAUNCH();
-    return WESUP_OK;
-}
-
-// The C-class forms of the two fused head launches (2 <= C <= WESUP_MAX_CLASSES), bit-identical to the separate entries at the
-// same C.  wesup_head_fwd_c = wesup_classifier_fwd_c + wesup_propagate (prop_c_kernel: prop_kernel with cls_row as its tail).
-extern "C" int wesup_head_fwd_c(const float* feat, const float* Wc, const float* bc, float* pred, const float* sp_labels,
-                                const int32_t* n_sp, const int32_t* n_l, float threshold, int enable, float* y_all,
-                                int32_t* src_idx, float* max_sim, int B, int Kmax, int D, int C, void* stream) {
-    if (!feat || !Wc || !bc || !pred || !sp_labels || !n_sp || !n_l || !y_all || !src_idx || !max_sim || B <= 0 || Kmax <= 0 ||
-        D <= 0 || D > WESUP_HEAD_MAX_D || !cls_c_range(C))
-        return WESUP_ERR_INVALID;
-    hipStream_t st = (hipStream_t)stream;
-    const size_t lds = prop_lds_bytes(D);
-    if (const int rc = prop_lds_ready<true>(lds); rc != WESUP_OK) return rc;
-    WESUP_LAUNCH(prop_c_kernel, dim3(ceil_div(Kmax, PROP_ROWS), B), dim3(256), lds, st, feat, sp_labels, n_sp, n_l, threshold,
-                 enable, y_all, src_idx, max_sim, Kmax, D, C, Wc, bc, pred);
-    WESUP_CHECK_LAUNCH();
-    return WESUP_OK;
-}
-// wesup_head_bwd_c = wesup_loss_fwd (terms only) + wesup_loss_bwd + the first kernel of wesup_classifier_bwd_c: head_bwd_kernel
-// with C columns per row (its comment above holds word for word).
 __global__ __launch_bounds__(256) void head_bwd_c_kernel(const float* __restrict__ feat, const float* __restrict__ Wc,
                                                          const float* __restrict__ pred, const float* __restrict__ y_all,
                                                          const int32_t* __restrict__ n_sp, const int32_t* __restrict__ n_l,
@@ -740,55 +631,11 @@ __global__ __launch_bounds__(256) void head_bwd_c_kernel(const float* __restrict
                                                          int D, int C) {
     __shared__ float sh[256];
     __shared__ float dz[CLS_ROWS][WESUP_MAX_CLASSES];
-    const int tid = threadIdx.x;
-    const long r0 = (long)blockIdx.x * CLS_ROWS;          // first row (of B * Kmax) of this block
-    const int b = (int)(r0 / Kmax), i0 = (int)(r0 - (long)b * Kmax);
-    const int ns = n_sp[b], nl = n_l[b];
-    float sup = 0.f, supc = 0.f, pro = 0.f, proc = 0.f, plab = 0.f;
-    for (int r = tid; r < ns; r += 256) {
-        float ys;
-        const float ce = ce_row(pred + ((long)b * Kmax + r) * C, y_all + ((long)b * Kmax + r) * C, C, eps, &ys);
-        if (r < nl) {
-            sup += ce;
-            supc += (ys > 0.f) ? 1.f : 0.f;
-        } else {
-            pro += ce;
-            proc += (ys > 0.f) ? 1.f : 0.f;
-            plab += ys;
-        }
-    }
-    sup = block_sum256(sup, sh);
-    supc = block_sum256(supc, sh);
-    pro = block_sum256(pro, sh);
-    proc = block_sum256(proc, sh);
-    plab = block_sum256(plab, sh);
-    if (tid == 0 && i0 == 0) {
-        float l = (supc > 0.f) ? sup / supc : 0.f;
-        if (nl < ns && proc > 0.f) l += prop_weight * (pro / proc);
-        float* t = terms + (long)b * 8;
-        t[0] = sup; t[1] = supc; t[2] = pro; t[3] = proc; t[4] = plab; t[5] = l; t[6] = 0.f; t[7] = 0.f;
-    }
-    // dpred of the block's rows (loss_bwd_kernel's expression), then dz
-    if (tid < CLS_ROWS) {
-        const int r = i0 + tid;                           // row inside the image (< Kmax)
-        const long gr = r0 + tid;
-        float coef = 0.f;
-        if (r < ns) {
-            if (r < nl) coef = (supc > 0.f) ? 1.f / supc : 0.f;
-            else coef = (nl < ns && proc > 0.f) ? prop_weight / proc : 0.f;
-        }
-        for (int c = 0; c < C; ++c) {
-            const float p = pred[gr * C + c];
-            float g = 0.f;
-            if (r < ns && p >= eps && p <= 1.f - eps) g = dloss[0] * (1.f / (float)B) * coef * (-y_all[gr * C + c] / p);
-            dpred[gr * C + c] = g;
-            dz[tid][c] = g;
-        }
-        cls_dz_row(pred + gr * C, dz[tid], C);
-    }
-    __syncthreads();
-    cls_bwd_c_tail(feat, Wc, nullptr, dfeat, part + (long)blockIdx.x * (C * D + C), dz, r0, (long)B * Kmax, D, C);
+    head_bwd_body<0>(sh, dz, feat, Wc, pred, y_all, n_sp, n_l, dloss, eps, prop_weight, terms, dpred, dfeat, part, B, Kmax, D, C);
 }
+// ws: wesup_classifier_bwd_c_workspace_bytes(B * Kmax, D, C); it holds the per-block partial sums of the classifier's weight
+// gradient until wesup_classifier_bwd_c_finish adds them up (any stream behind this launch: nothing on the way to the fc layers'
+// gradients reads dWc / dbc).
 extern "C" int wesup_head_bwd_c(const float* feat, const float* Wc, const float* pred, const float* y_all, const int32_t* n_sp,
                                 const int32_t* n_l, const float* dloss, float eps, float prop_weight, float* terms, float* dpred,
                                 float* dfeat, int B, int Kmax, int D, int C, void* ws, size_t ws_bytes, void* stream) {
@@ -797,8 +644,14 @@ extern "C" int wesup_head_bwd_c(const float* feat, const float* Wc, const float*
         return WESUP_ERR_INVALID;
     const int R = B * Kmax;
     if (ws_bytes < wesup_classifier_bwd_c_workspace_bytes(R, D, C)) return WESUP_ERR_WORKSPACE;
-    WESUP_LAUNCH(head_bwd_c_kernel, dim3(R / CLS_ROWS), dim3(256), 0, (hipStream_t)stream, feat, Wc, pred, y_all, n_sp, n_l,
-                 dloss, eps, prop_weight, terms, dpred, dfeat, (float*)ws, B, Kmax, D, C);
+    const dim3 grid(R / CLS_ROWS);
+    hipStream_t st = (hipStream_t)stream;
+    if (C == 2)
+        WESUP_LAUNCH(head_bwd_kernel, grid, dim3(256), 0, st, feat, Wc, pred, y_all, n_sp, n_l, dloss, eps, prop_weight, terms,
+                     dpred, dfeat, (float*)ws, B, Kmax, D);
+    else
+        WESUP_LAUNCH(head_bwd_c_kernel, grid, dim3(256), 0, st, feat, Wc, pred, y_all, n_sp, n_l, dloss, eps, prop_weight, terms,
+                     dpred, dfeat, (float*)ws, B, Kmax, D, C);
     WESUP_CHECK_LAUNCH();
     return WESUP_OK;
 }
@@ -806,10 +659,20 @@ extern "C" int wesup_classifier_bwd_c_finish(const void* ws, size_t ws_bytes, fl
                                              void* stream) {
     if (!ws || !dWc || !dbc || R <= 0 || D <= 0 || !cls_c_range(C)) return WESUP_ERR_INVALID;
     if (ws_bytes < wesup_classifier_bwd_c_workspace_bytes(R, D, C)) return WESUP_ERR_WORKSPACE;
-    WESUP_LAUNCH(classifier_bwd_c_reduce, dim3(ceil_div(C * D + C, 64)), dim3(64), 0, (hipStream_t)stream, (const float*)ws, dWc,
-                 dbc, ceil_div(R, CLS_ROWS), D, C);
+    cls_reduce_launch(ws, dWc, dbc, R, D, C, (hipStream_t)stream);
     WESUP_CHECK_LAUNCH();
     return WESUP_OK;
+}
+// two classes: the _c entries with C = 2
+extern "C" int wesup_head_bwd(const float* feat, const float* Wc, const float* pred, const float* y_all, const int32_t* n_sp,
+                              const int32_t* n_l, const float* dloss, float eps, float prop_weight, float* terms, float* dpred,
+                              float* dfeat, int B, int Kmax, int D, int C, void* ws, size_t ws_bytes, void* stream) {
+    if (C != 2) return WESUP_ERR_INVALID;
+    return wesup_head_bwd_c(feat, Wc, pred, y_all, n_sp, n_l, dloss, eps, prop_weight, terms, dpred, dfeat, B, Kmax, D, 2, ws,
+                            ws_bytes, stream);
+}
+extern "C" int wesup_classifier_bwd_finish(const void* ws, size_t ws_bytes, float* dWc, float* dbc, int R, int D, void* stream) {
+    return wesup_classifier_bwd_c_finish(ws, ws_bytes, dWc, dbc, R, D, 2, stream);
 }
 
 // generic _cross_entropy on (n, C)

@@ -1115,7 +1115,7 @@ HEAD_MAX_D = _lib.HEAD_MAX_D         # WESUP_HEAD_MAX_D: propagate / head_fwd ta
 
 
 def classifier_fwd(feat, Wc, bc, out=None):
-    """softmax(feat . Wc^T + bc): (R, D) -> (R, C), C = Wc.shape[0].  Two classes: wesup_classifier_fwd, more: wesup_classifier_fwd_c."""
+    """softmax(feat . Wc^T + bc): (R, D) -> (R, C), C = Wc.shape[0] (wesup_classifier_fwd_c: D <= 512)."""
     _chk(feat, name='feat'); _chk(Wc, name='Wc'); _chk(bc, name='bc')
     R, D = feat.shape
     C = Wc.shape[0]
@@ -1123,33 +1123,17 @@ def classifier_fwd(feat, Wc, bc, out=None):
     if out is None:
         out = torch.empty(R, C, dtype=torch.float32, device=feat.device)
     assert out.numel() == R * C
-    if C == 2:
-        _lib.call('wesup_classifier_fwd', _p(feat), _p(Wc), _p(bc), _p(out), R, D, _stream())
-    else:
-        _lib.call('wesup_classifier_fwd_c', _p(feat), _p(Wc), _p(bc), _p(out), R, D, C, _stream())
-    return out
-
-
-def classifier_fwd_c(feat, Wc, bc, out=None):
-    """wesup_classifier_fwd_c for any 2 <= C <= MAX_CLASSES (classifier_fwd calls it for C > 2)."""
-    _chk(feat, name='feat'); _chk(Wc, name='Wc'); _chk(bc, name='bc')
-    R, D = feat.shape
-    C = Wc.shape[0]
-    assert Wc.shape == (C, D) and bc.numel() == C
-    if out is None:
-        out = torch.empty(R, C, dtype=torch.float32, device=feat.device)
     _lib.call('wesup_classifier_fwd_c', _p(feat), _p(Wc), _p(bc), _p(out), R, D, C, _stream())
     return out
 
 
 def classifier_bwd_bytes(R, D, C=2):
     """Bytes of the classifier's per-64-row partial sums of dWc / dbc."""
-    lib = _lib.load()
-    return lib.wesup_classifier_bwd_workspace_bytes(R, D) if C == 2 else lib.wesup_classifier_bwd_c_workspace_bytes(R, D, C)
+    return _lib.load().wesup_classifier_bwd_c_workspace_bytes(R, D, C)
 
 
-def classifier_bwd(feat, Wc, pred, dpred, dfeat_extra=None, dfeat=None, dWc=None, dbc=None, generic=False):
-    """Backward of classifier_fwd; C = Wc.shape[0].  generic: wesup_classifier_bwd_c also for two classes."""
+def classifier_bwd(feat, Wc, pred, dpred, dfeat_extra=None, dfeat=None, dWc=None, dbc=None):
+    """Backward of classifier_fwd; C = Wc.shape[0] (wesup_classifier_bwd_c)."""
     _chk(feat, name='feat'); _chk(pred, name='pred'); _chk(dpred, name='dpred')
     R, D = feat.shape
     C = Wc.shape[0]
@@ -1160,16 +1144,10 @@ def classifier_bwd(feat, Wc, pred, dpred, dfeat_extra=None, dfeat=None, dWc=None
     dfeat = torch.empty(R, D, dtype=torch.float32, device=dev) if dfeat is None else dfeat
     dWc = torch.empty(C, D, dtype=torch.float32, device=dev) if dWc is None else dWc
     dbc = torch.empty(C, dtype=torch.float32, device=dev) if dbc is None else dbc
-    if C == 2 and not generic:
-        nb = _lib.load().wesup_classifier_bwd_workspace_bytes(R, D)
-        ws = workspace(nb, dev, 'cls')
-        _lib.call('wesup_classifier_bwd', _p(feat), _p(Wc), _p(pred), _p(dpred), _p(dfeat_extra), _p(dfeat), _p(dWc), _p(dbc),
-                  R, D, _p(ws), nb, _stream())
-    else:
-        nb = _lib.load().wesup_classifier_bwd_c_workspace_bytes(R, D, C)
-        ws = workspace(nb, dev, 'cls')
-        _lib.call('wesup_classifier_bwd_c', _p(feat), _p(Wc), _p(pred), _p(dpred), _p(dfeat_extra), _p(dfeat), _p(dWc), _p(dbc),
-                  R, D, C, _p(ws), nb, _stream())
+    nb = classifier_bwd_bytes(R, D, C)
+    ws = workspace(nb, dev, 'cls')
+    _lib.call('wesup_classifier_bwd_c', _p(feat), _p(Wc), _p(pred), _p(dpred), _p(dfeat_extra), _p(dfeat), _p(dWc), _p(dbc),
+              R, D, C, _p(ws), nb, _stream())
     return dfeat, dWc, dbc
 
 
@@ -1219,7 +1197,7 @@ def loss_bwd(pred, y_all, meta, terms, dloss, eps, prop_weight, out=None):
 
 
 def head_fwd(feat, Wc, bc, pred, meta, threshold, enable=True, out=None):
-    """classifier_fwd + propagate in one launch (wesup_head_fwd; wesup_head_fwd_c for more than two classes): feat (B,Kmax,D) ->
+    """classifier_fwd + propagate in one launch (wesup_head_fwd_c): feat (B,Kmax,D) ->
     pred (B*Kmax,C) and (y_all, src_idx, max_sim)."""
     _chk(feat, name='feat'); _chk(Wc, name='Wc'); _chk(bc, name='bc'); _chk(pred, name='pred')
     B, Kmax, D = feat.shape
@@ -1229,23 +1207,19 @@ def head_fwd(feat, Wc, bc, pred, meta, threshold, enable=True, out=None):
     y_all, src, sim = out
     assert y_all.shape == (B, Kmax, meta.C) and src.shape == (B, Kmax) == sim.shape and src.dtype == torch.int32
     tok = _tbegin('propagate')
-    _lib.call('wesup_head_fwd' if C == 2 else 'wesup_head_fwd_c', _p(feat), _p(Wc), _p(bc), _p(pred), _p(meta.sp_labels), _p(meta.n_sp),
-              _p(meta.n_l), float(threshold), int(enable), _p(y_all), _p(src), _p(sim), B, Kmax, D, meta.C, _stream())
+    _lib.call('wesup_head_fwd_c', _p(feat), _p(Wc), _p(bc), _p(pred), _p(meta.sp_labels), _p(meta.n_sp), _p(meta.n_l),
+              float(threshold), int(enable), _p(y_all), _p(src), _p(sim), B, Kmax, D, meta.C, _stream())
     _tend(tok, 4.0 * B * Kmax * (D + 2 * meta.C + 2))
     return y_all, src, sim
 
 
-def head_bwd_supported(Kmax, C):
-    return Kmax % 64 == 0 and C == 2
-
-
-def head_c_supported(Kmax, C):
-    """The fused head launches for more than two classes (wesup_head_fwd_c / wesup_head_bwd_c)."""
-    return Kmax % 64 == 0 and 2 < C <= MAX_CLASSES
+def head_supported(Kmax, C):
+    """The fused head launches (wesup_head_fwd_c / wesup_head_bwd_c)."""
+    return Kmax % 64 == 0 and 2 <= C <= MAX_CLASSES
 
 
 def head_bwd_partials(R, D, device, C=2):
-    """The buffer wesup_head_bwd leaves the partial sums of dWc / dbc in and wesup_classifier_bwd_finish reads (on another stream,
+    """The buffer wesup_head_bwd_c leaves the partial sums of dWc / dbc in and wesup_classifier_bwd_c_finish reads (on another stream,
     launches later): owned by the caller -- the engine keeps one per buffer set -- never a shared grow-only workspace, which another
     tag's growth may replace between the two calls."""
     return torch.empty(max(int(classifier_bwd_bytes(R, D, C)), 256), dtype=torch.uint8, device=device)
@@ -1253,18 +1227,17 @@ def head_bwd_partials(R, D, device, C=2):
 
 def head_bwd(feat, Wc, pred, y_all, meta, dloss, eps, prop_weight, terms, dpred, dfeat, partials):
     """loss_fwd (terms) + loss_bwd (dpred) + the first kernel of classifier_bwd (dfeat, partial sums of dWc / dbc into ``partials``,
-    see head_bwd_partials) in one launch (wesup_head_bwd; wesup_head_bwd_c for more than two classes); classifier_bwd_finish adds
-    the partial sums up."""
+    see head_bwd_partials) in one launch (wesup_head_bwd_c); classifier_bwd_finish adds the partial sums up."""
     _chk(feat, name='feat'); _chk(pred, name='pred'); _chk(y_all, name='y_all'); _chk(dloss, name='dloss')
     _chk(partials, torch.uint8, 'partials')
     B, Kmax, C = y_all.shape
     R, D = feat.shape
     assert R == B * Kmax and pred.numel() == R * C and dpred.numel() == R * C and dfeat.shape == (R, D) and terms.shape == (B, 8)
-    assert Wc.shape == (C, D) and (head_bwd_supported(Kmax, C) or head_c_supported(Kmax, C)) and B == meta.B and Kmax == meta.Kmax
+    assert Wc.shape == (C, D) and head_supported(Kmax, C) and B == meta.B and Kmax == meta.Kmax
     nb = classifier_bwd_bytes(R, D, C)
     assert partials.numel() >= nb
-    _lib.call('wesup_head_bwd' if C == 2 else 'wesup_head_bwd_c', _p(feat), _p(Wc), _p(pred), _p(y_all), _p(meta.n_sp), _p(meta.n_l),
-              _p(dloss), float(eps), float(prop_weight), _p(terms), _p(dpred), _p(dfeat), B, Kmax, D, C, _p(partials), nb, _stream())
+    _lib.call('wesup_head_bwd_c', _p(feat), _p(Wc), _p(pred), _p(y_all), _p(meta.n_sp), _p(meta.n_l), _p(dloss), float(eps),
+              float(prop_weight), _p(terms), _p(dpred), _p(dfeat), B, Kmax, D, C, _p(partials), nb, _stream())
 
 
 def classifier_bwd_finish(partials, R, D, dWc, dbc):
@@ -1272,10 +1245,7 @@ def classifier_bwd_finish(partials, R, D, dWc, dbc):
     C = dWc.shape[0]
     nb = classifier_bwd_bytes(R, D, C)
     assert partials.numel() >= nb and dWc.shape == (C, D) and dbc.numel() == C
-    if C == 2:
-        _lib.call('wesup_classifier_bwd_finish', _p(partials), nb, _p(dWc), _p(dbc), R, D, _stream())
-    else:
-        _lib.call('wesup_classifier_bwd_c_finish', _p(partials), nb, _p(dWc), _p(dbc), R, D, C, _stream())
+    _lib.call('wesup_classifier_bwd_c_finish', _p(partials), nb, _p(dWc), _p(dbc), R, D, C, _stream())
 
 
 def cross_entropy_fwd(y_hat, y_true, eps, class_weights=None):

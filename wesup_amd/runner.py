@@ -378,12 +378,12 @@ class StepRunner:
             multi = red is not None and t.world_size > 1
             # One rank: the head of the step -- classifier, label propagation, loss, its gradient, the classifier's backward: six
             # launches on the chain between the fc layers' forward and backward -- in two (ops.head_fwd / head_bwd, bit-identical)
-            # (more than two classes: the same walk over the *_c entries -- ops.head_fwd / head_bwd / paint dispatch on the class
-            # count --, with the confusion table where the two-class walk forms the four segmentation sums)
+            # (more than two classes: the same walk -- the head entries take the class count, ops.paint dispatches on it --, with
+            # the confusion table where the two-class walk forms the four segmentation sums)
             Kmax_, C_ = st.y_all.shape[1], st.y_all.shape[2]
             if eng.n_classes != C_:
                 raise ValueError(f'the model has {eng.n_classes} classes, the masks of this batch have {C_}')
-            fuse = self.fuse_head and not multi and (ops.head_bwd_supported(Kmax_, C_) or ops.head_c_supported(Kmax_, C_))
+            fuse = self.fuse_head and not multi and ops.head_supported(Kmax_, C_)
             feats, sp_pred, pred = eng.forward(st.img, st.meta, train=True, need_paint=multi, head=not fuse)
             if want_seg and multi:
                 self._seg(st, pred)
