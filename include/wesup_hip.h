@@ -565,6 +565,20 @@ int wesup_window_gather(const uint8_t* img, const int32_t* tops, const int32_t* 
  * infer_tile.combine_patches_to_image bit for bit */
 int wesup_window_merge(const float* pred, const int32_t* tops, const int32_t* lefts, double* out, int H, int W, int C, int n_h,
                        int n_w, int p, int round_first, void* stream);
+/* Test-time augmentation over the views of a square window (infer_tile.apply_view / invert_view): view
+ * v = r + 4 f, a left-right mirror first when f, then r counter-clockwise quarter turns.  A view list comes by value: n_views
+ * and `views`, four bits per view, the first view in the lowest bits.  WESUP_ERR_INVALID without a launch for n_views outside
+ * 1 .. 8, an index above 7 or a repeated index, and for what the entries above refuse.
+ *
+ * wesup_window_gather_views: wesup_window_gather over the slots of windows x views -- slot s = first + n is window s / n_views
+ * under view views[s % n_views], a slot past the last repeats the last; out[n] is _to_tensor(apply_view(window, v)) bit for bit. */
+int wesup_window_gather_views(const uint8_t* img, const int32_t* tops, const int32_t* lefts, float* out, int H, int W, int n_h,
+                              int n_w, int p, int n_views, uint32_t views, int first, int count, void* stream);
+/* pred fp32 [n_h * n_w][n_views][p][p][C], every prediction in the space of its view -> out fp64 [H][W][C]: per covering window
+ * in ascending order its views in list order, each turned back (read through the inverse index), added as doubles onto 0.0 and
+ * divided once by covering windows x n_views: infer_tile.combine_views_to_image bit for bit; round_first as above */
+int wesup_window_merge_views(const float* pred, const int32_t* tops, const int32_t* lefts, double* out, int H, int W, int C,
+                             int n_h, int n_w, int p, int n_views, uint32_t views, int round_first, void* stream);
 
 /* ------------------------------------------------------------------ whole-image multi-scale pixel inference (csrc/pixel.hip)
  * pixel_infer.py:38-56 rescales an image by every factor of --scales (bilinear, align_corners=True), runs the pixel-wise
@@ -631,6 +645,12 @@ int wesup_mask_scores(const uint8_t* S, const uint8_t* G, int64_t* out4, long n,
  * window votes, the first maximum of the integer counts.  out uint8 [H][W]; *status is zeroed here. */
 int wesup_window_merge_classes(const float* pred, const int32_t* tops, const int32_t* lefts, uint8_t* out, int32_t* status, int H,
                                int W, int C, int n_h, int n_w, int p, int votes, void* stream);
+/* wesup_window_merge_classes over windows x views (wesup_window_merge_views' view list and order): pred fp32
+ * [n_h * n_w][n_views][p][p][C] probabilities (votes = 0) or [n_h * n_w][n_views][p][p] class indices (votes = 1: every
+ * (window, view) votes), each in the space of its view: infer_tile.combine_views_to_classes bit for bit */
+int wesup_window_merge_classes_views(const float* pred, const int32_t* tops, const int32_t* lefts, uint8_t* out, int32_t* status,
+                                     int H, int W, int C, int n_h, int n_w, int p, int n_views, uint32_t views, int votes,
+                                     void* stream);
 /* in fp32 [h][w][C] -> out fp32 [H][W][C] = (accumulate ? out : 0) + alpha * bilinear_ac(in): every plane c is
  * wesup_plane_resize_acc of in[..., c] (stride C) bit for bit; the four corner vectors are read once per pixel */
 int wesup_planes_resize_acc(const float* in, float* out, int h, int w, int H, int W, int C, float alpha, int accumulate,

@@ -155,6 +155,9 @@ _SIGS = {
     # window inference on large images (csrc/tiles.hip)
     'wesup_window_gather': (c_int, 'pppp' + 'iiiiiii' + 'p'),
     'wesup_window_merge': (c_int, 'pppp' + 'iiiiiii' + 'p'),
+    # ... over windows x views: n_views and the view word, four bits per view
+    'wesup_window_gather_views': (c_int, 'pppp' + 'iiiiiiiii' + 'p'),
+    'wesup_window_merge_views': (c_int, 'pppp' + 'iiiiiiiii' + 'p'),
     # whole-image multi-scale pixel inference (csrc/pixel.hip)
     'wesup_image_resize_u8': (c_int, 'pp' + 'iiii' + 'p'),
     'wesup_plane_resize_acc': (c_int, 'pp' + 'iiiii' + 'fi' + 'p'),
@@ -165,6 +168,7 @@ _SIGS = {
     'wesup_mask_scores': (c_int, 'ppp' + 'li' + 'p'),
     # class maps for more than two classes (csrc/classmap.hip)
     'wesup_window_merge_classes': (c_int, 'ppppp' + 'iiiiiii' + 'p'),
+    'wesup_window_merge_classes_views': (c_int, 'ppppp' + 'iiiiiiiii' + 'p'),
     'wesup_planes_resize_acc': (c_int, 'pp' + 'iiiii' + 'fi' + 'p'),
     'wesup_class_argmax_u8': (c_int, 'pp' + 'li' + 'p'),
     'wesup_patch_scatter_classes_u8': (c_int, 'ppp' + 'iiiiiiiii' + 'p'),

@@ -128,6 +128,68 @@ __global__ __launch_bounds__(CM_BLOCK) void cm_merge_kernel(const float* __restr
     }
 }
 
+// ---- 1v. cm_merge_kernel over windows x views: pred [N][V][p][p][C] or [N][V][p][p] in VIEW space.  The same
+// search, tests, registers and first maximum; every covering window (ascending) contributes its V views in list order, each read
+// through view_inverse (lattice.hpp) at an offset tested to lie in [0, p).  The divisor is the number of values, covering
+// windows x V: infer_tile.combine_views_to_classes bit for bit.
+template <int CMAX, bool VEC4, bool VOTES>
+__global__ __launch_bounds__(CM_BLOCK) void cm_merge_views_kernel(const float* __restrict__ pred, const int32_t* __restrict__ tops,
+                                                                  const int32_t* __restrict__ lefts, uint8_t* __restrict__ out,
+                                                                  int32_t* __restrict__ status, int H, int W, int C, int n_h,
+                                                                  int n_w, int p, int V, uint32_t views) {
+    const long total = (long)H * W;
+    for (long idx = (long)blockIdx.x * CM_BLOCK + threadIdx.x; idx < total; idx += (long)gridDim.x * CM_BLOCK) {
+        const int y = (int)(idx / W), x = (int)(idx - (long)y * W);
+        const Covering rows = covering(tops, n_h, y, p), cols = covering(lefts, n_w, x, p);
+        double acc[CMAX];
+        int votes[CMAX];
+#pragma unroll
+        for (int c = 0; c < CMAX; ++c) {
+            acc[c] = 0.0;
+            votes[c] = 0;
+        }
+        int cnt = 0;
+        bool bad = false;
+        for (int i = rows.i0; i < rows.i1; ++i) {
+            const int dy = y - tops[i];
+            if (dy < 0 || dy >= p) continue;         // (an unsorted lattice: never an address outside the window)
+            for (int j = cols.i0; j < cols.i1; ++j) {
+                const int dx = x - lefts[j];
+                if (dx < 0 || dx >= p) continue;
+                const long slot = (long)(i * n_w + j) * V;
+                for (int t = 0; t < V; ++t) {
+                    const ViewPixel q = view_inverse(view_at(views, t), p, dy, dx);
+                    if (!view_inside(q, p)) continue;
+                    const long at = ((slot + t) * p + q.y) * p + q.x;
+                    if constexpr (VOTES) {
+                        const float v = rintf(pred[at]);
+                        if (v >= 0.f && v < (float)C) {
+#pragma unroll
+                            for (int c = 0; c < CMAX; ++c)
+                                if (c < C) votes[c] += (v == (float)c) ? 1 : 0;
+                        } else bad = true;           // (a NaN lands here too)
+                    } else {
+                        load_classes<CMAX, VEC4>(pred + at * C, C, [&](int c, float v) { acc[c] += (double)v; });
+                    }
+                    ++cnt;
+                }
+            }
+        }
+        int cls;
+        if constexpr (VOTES) {
+            cls = first_max<CMAX>(votes, C);
+            if (bad) atomicOr(status, 1);
+        } else {
+            const double n = (double)cnt;
+#pragma unroll
+            for (int c = 0; c < CMAX; ++c)
+                if (c < C) acc[c] = acc[c] / n;
+            cls = first_max<CMAX>(acc, C);
+        }
+        out[idx] = (uint8_t)cls;
+    }
+}
+
 // ---- 2. resize: out[Y][X][c] = (accumulate ? out[Y][X][c] : 0) + alpha * bilinear_ac(in[..][..][c])(Y, X), every plane the
 // bits of px_plane_resize_kernel on in[..., c]: the same two functions (blend_plane_times, add_rounded_product: bilinear.hpp) state
 // the product by alpha and the add onto out as two roundings in both kernels.  One thread per output pixel: the coordinates and the
@@ -301,6 +363,27 @@ extern "C" int wesup_window_merge_classes(const float* pred, const int32_t* tops
     if (votes) WESUP_LAUNCH((cm_merge_kernel<CMAX, false, true>), grid, block, 0, st, pred, tops, lefts, out, status, H, W, C, n_h, \
                             n_w, p);                                                                                       \
     else WESUP_LAUNCH((cm_merge_kernel<CMAX, V, false>), grid, block, 0, st, pred, tops, lefts, out, status, H, W, C, n_h, n_w, p)
+    CM_DISPATCH(C, vec, CM_L);
+#undef CM_L
+    WESUP_CHECK_LAUNCH();
+    return WESUP_OK;
+}
+
+extern "C" int wesup_window_merge_classes_views(const float* pred, const int32_t* tops, const int32_t* lefts, uint8_t* out,
+                                                int32_t* status, int H, int W, int C, int n_h, int n_w, int p, int n_views,
+                                                uint32_t views, int votes, void* stream) {
+    if (!pred || !tops || !lefts || !out || !status || p < 1 || p > H || p > W || !cm_range(C) || n_h < 1 || n_w < 1 ||
+        !views_ok(n_views, views) || (long)n_h * n_w * n_views > 0x7fffffffl || (votes != 0 && votes != 1))
+        return WESUP_ERR_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    if (wesup_fill_words_(status, 0u, 1, st) != WESUP_OK) return WESUP_ERR_LAUNCH;
+    const dim3 grid(grid_stride_blocks((long)H * W, CM_BLOCK, CM_MAX_BLOCKS)), block(CM_BLOCK);
+    const bool vec = !votes && (C % 4 == 0) && aligned16(pred);
+#define CM_L(CMAX, V)                                                                                                            \
+    if (votes) WESUP_LAUNCH((cm_merge_views_kernel<CMAX, false, true>), grid, block, 0, st, pred, tops, lefts, out, status, H, W, C, \
+                            n_h, n_w, p, n_views, views);                                                                        \
+    else WESUP_LAUNCH((cm_merge_views_kernel<CMAX, V, false>), grid, block, 0, st, pred, tops, lefts, out, status, H, W, C, n_h, n_w, \
+                      p, n_views, views)
     CM_DISPATCH(C, vec, CM_L);
 #undef CM_L
     WESUP_CHECK_LAUNCH();

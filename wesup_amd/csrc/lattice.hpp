@@ -40,6 +40,45 @@ __device__ __forceinline__ PatchPixel patch_pixel(long idx, int p, int first, in
     return q;
 }
 
+// The eight views of a square p x p window (infer_tile.apply_view / invert_view): v = r + 4 f, a left-right mirror first when f,
+// then r counter-clockwise quarter turns.  A view list comes by value: n_views and one word of four bits per view, the first view
+// in the lowest bits.  views_ok: 1 <= n_views <= 8, every index below 8, none twice -- asked on the host, before a launch.
+#define WESUP_MAX_VIEWS 8
+static inline bool views_ok(int n_views, uint32_t views) {
+    if (n_views < 1 || n_views > WESUP_MAX_VIEWS) return false;
+    unsigned seen = 0;
+    for (int t = 0; t < n_views; ++t) {
+        const unsigned v = (views >> (4 * t)) & 15u;
+        if (v > 7u || (seen >> v) & 1u) return false;
+        seen |= 1u << v;
+    }
+    return true;
+}
+__device__ __forceinline__ int view_at(uint32_t views, int t) { return (int)((views >> (4 * t)) & 7u); }
+
+struct ViewPixel {
+    int y, x;
+};
+// forward: the pixel of the upright window that pixel (y, x) of view v shows -- apply_view(a, v)[y][x] = a[s.y][s.x]
+__device__ __forceinline__ ViewPixel view_source(int v, int p, int y, int x) {
+    const int r = v & 3, m = p - 1;
+    ViewPixel s;
+    s.y = r == 0 ? y : r == 1 ? x : r == 2 ? m - y : m - x;
+    s.x = r == 0 ? x : r == 1 ? m - y : r == 2 ? m - x : y;
+    if (v & 4) s.x = m - s.x;
+    return s;
+}
+// inverse: where pixel (y, x) of the upright window lies in view v -- invert_view(b, v)[y][x] = b[q.y][q.x]
+__device__ __forceinline__ ViewPixel view_inverse(int v, int p, int y, int x) {
+    const int r = v & 3, m = p - 1;
+    const int w = (v & 4) ? m - x : x;
+    ViewPixel q;
+    q.y = r == 0 ? y : r == 1 ? m - w : r == 2 ? m - y : w;
+    q.x = r == 0 ? w : r == 1 ? y : r == 2 ? m - w : m - y;
+    return q;
+}
+__device__ __forceinline__ bool view_inside(const ViewPixel q, int p) { return q.y >= 0 && q.y < p && q.x >= 0 && q.x < p; }
+
 // [i0, i1): the windows of one axis of a sorted window lattice that cover pos, 0 <= pos - tops[i] < p; n comparisons.  The caller
 // tests every offset again before it makes an address of it (an unsorted lattice gives wrong numbers, never a fault).
 struct Covering {

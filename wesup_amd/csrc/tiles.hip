@@ -90,6 +90,90 @@ __global__ __launch_bounds__(TL_BLOCK) void tl_merge_kernel(const float* __restr
     }
 }
 
+// ---- Views: the slot axis of a pass is windows x views, slot s = first + n is window s / V under view
+// views[s % V], the last slot repeated past the end.  out[n][c][y][x] = unit(window pixel view_source(v, y, x)): the bits of
+// _to_tensor(apply_view(window, v)).  tl_gather_kernel's thread shape -- VEC pixels along the OUTPUT's x, one VEC-wide store per
+// plane -- so the stores stay contiguous whatever the view; the reads of a thread's VEC pixels step along the image's x for an
+// even r (backwards under a half turn or a mirror) and along its y, one image row apart, for an odd r.  A source pixel is
+// tested to lie inside the window before it becomes an address, like everything else here.
+template <int VEC>
+__global__ __launch_bounds__(TL_BLOCK) void tl_gather_views_kernel(const uint8_t* __restrict__ img, const int32_t* __restrict__ tops,
+                                                                   const int32_t* __restrict__ lefts, float* __restrict__ out, int H,
+                                                                   int W, int n_h, int n_w, int p, int V, uint32_t views, int first,
+                                                                   int count) {
+    const int pv = p / VEC;
+    const long per_win = (long)p * pv;
+    const long total = (long)count * per_win;
+    const long plane = (long)p * p;
+    const int last = n_h * n_w * V - 1;
+    for (long idx = (long)blockIdx.x * TL_BLOCK + threadIdx.x; idx < total; idx += (long)gridDim.x * TL_BLOCK) {
+        const int n = (int)(idx / per_win);
+        const int r = (int)(idx - (long)n * per_win);
+        const int y = r / pv, x = (r - y * pv) * VEC;
+        int s = first + n;
+        s = s > last ? last : s;
+        const int k = s / V, v = view_at(views, s - k * V);
+        const int wi = k / n_w, wj = k - wi * n_w;
+        int top = tops[wi], left = lefts[wj];
+        top = top < 0 ? 0 : (top > H - p ? H - p : top);
+        left = left < 0 ? 0 : (left > W - p ? W - p : left);
+        const uint8_t* win = img + ((long)top * W + left) * 3;
+        float val[3][VEC];
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) {
+            const ViewPixel q = view_source(v, p, y, x + i);
+            const bool in = view_inside(q, p);
+            const uint8_t* src = win + ((long)q.y * W + q.x) * 3;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) val[c][i] = in ? byte_to_unit(src[c]) : 0.f;
+        }
+        float* dst = out + (long)n * 3 * plane + (long)y * p + x;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            if (VEC == 4) st4(dst + c * plane, make_float4(val[c][0], val[c][1], val[c][2], val[c][3]));
+            else dst[c * plane] = val[c][0];
+        }
+    }
+}
+
+// pred [N][V][p][p][C] in VIEW space -> out[y][x][c] = mean over the covering windows and their views, in fp64: tl_merge_kernel's
+// search and tests, then per covering window (ascending, row-major) its views in list order, each read through view_inverse at
+// an offset tested to lie in [0, p); added onto 0.0 and divided once by the number of values, covering windows x V -- the order
+// and the operations of infer_tile.combine_views_to_image, hence its result bit for bit.
+__global__ __launch_bounds__(TL_BLOCK) void tl_merge_views_kernel(const float* __restrict__ pred, const int32_t* __restrict__ tops,
+                                                                  const int32_t* __restrict__ lefts, double* __restrict__ out, int H,
+                                                                  int W, int C, int n_h, int n_w, int p, int V, uint32_t views,
+                                                                  int round_first) {
+    const long total = (long)H * W * C;
+    const long WC = (long)W * C;
+    for (long idx = (long)blockIdx.x * TL_BLOCK + threadIdx.x; idx < total; idx += (long)gridDim.x * TL_BLOCK) {
+        const int y = (int)(idx / WC);
+        const int r = (int)(idx - (long)y * WC);
+        const int x = r / C, c = r - x * C;
+        const Covering rows = covering(tops, n_h, y, p), cols = covering(lefts, n_w, x, p);
+        double acc = 0.0;
+        int cnt = 0;
+        for (int i = rows.i0; i < rows.i1; ++i) {
+            const int dy = y - tops[i];
+            if (dy < 0 || dy >= p) continue;         // (an unsorted lattice: never an address outside the window)
+            for (int j = cols.i0; j < cols.i1; ++j) {
+                const int dx = x - lefts[j];
+                if (dx < 0 || dx >= p) continue;
+                const long slot = (long)(i * n_w + j) * V;
+                for (int t = 0; t < V; ++t) {
+                    const ViewPixel q = view_inverse(view_at(views, t), p, dy, dx);
+                    if (!view_inside(q, p)) continue;
+                    float v = pred[(((slot + t) * p + q.y) * p + q.x) * C + c];
+                    if (round_first) v = rintf(v);   // half to even: torch.round / np.round
+                    acc += (double)v;
+                    ++cnt;
+                }
+            }
+        }
+        out[idx] = acc / (double)cnt;
+    }
+}
+
 }  // namespace
 
 extern "C" int wesup_window_gather(const uint8_t* img, const int32_t* tops, const int32_t* lefts, float* out, int H, int W,
@@ -117,6 +201,36 @@ extern "C" int wesup_window_merge(const float* pred, const int32_t* tops, const 
     hipStream_t st = (hipStream_t)stream;
     WESUP_LAUNCH(tl_merge_kernel, dim3(grid_stride_blocks((long)H * W * C, TL_BLOCK, TL_MAX_BLOCKS)), dim3(TL_BLOCK), 0, st, pred,
                  tops, lefts, out, H, W, C, n_h, n_w, p, round_first ? 1 : 0);
+    WESUP_CHECK_LAUNCH();
+    return WESUP_OK;
+}
+
+extern "C" int wesup_window_gather_views(const uint8_t* img, const int32_t* tops, const int32_t* lefts, float* out, int H, int W,
+                                         int n_h, int n_w, int p, int n_views, uint32_t views, int first, int count, void* stream) {
+    if (!img || !tops || !lefts || !out || p < 1 || p > H || p > W || n_h < 1 || n_w < 1 || first < 0 || count < 1 ||
+        !views_ok(n_views, views) || (long)n_h * n_w * n_views > 0x7fffffffl)
+        return WESUP_ERR_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    if (p % 4 == 0) {
+        WESUP_LAUNCH(tl_gather_views_kernel<4>, dim3(grid_stride_blocks((long)count * p * (p / 4), TL_BLOCK, TL_MAX_BLOCKS)),
+                     dim3(TL_BLOCK), 0, st, img, tops, lefts, out, H, W, n_h, n_w, p, n_views, views, first, count);
+    } else {
+        WESUP_LAUNCH(tl_gather_views_kernel<1>, dim3(grid_stride_blocks((long)count * p * p, TL_BLOCK, TL_MAX_BLOCKS)),
+                     dim3(TL_BLOCK), 0, st, img, tops, lefts, out, H, W, n_h, n_w, p, n_views, views, first, count);
+    }
+    WESUP_CHECK_LAUNCH();
+    return WESUP_OK;
+}
+
+extern "C" int wesup_window_merge_views(const float* pred, const int32_t* tops, const int32_t* lefts, double* out, int H, int W,
+                                        int C, int n_h, int n_w, int p, int n_views, uint32_t views, int round_first,
+                                        void* stream) {
+    if (!pred || !tops || !lefts || !out || p < 1 || p > H || p > W || C < 1 || n_h < 1 || n_w < 1 || !views_ok(n_views, views) ||
+        (long)n_h * n_w * n_views > 0x7fffffffl)
+        return WESUP_ERR_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    WESUP_LAUNCH(tl_merge_views_kernel, dim3(grid_stride_blocks((long)H * W * C, TL_BLOCK, TL_MAX_BLOCKS)), dim3(TL_BLOCK), 0, st,
+                 pred, tops, lefts, out, H, W, C, n_h, n_w, p, n_views, views, round_first ? 1 : 0);
     WESUP_CHECK_LAUNCH();
     return WESUP_OK;
 }

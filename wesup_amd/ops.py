@@ -1840,6 +1840,64 @@ def window_merge(pred, tops, lefts, H, W, round_first=False, out=None):
     return out
 
 
+def _view_word(views, name):
+    """A view list (infer_tile.VIEW_SETS: 1 .. 8 distinct indices in [0, 8), any order) -> (V, the word the entries take: four
+    bits per view, the first view in the lowest bits)."""
+    try:
+        views = [int(v) for v in views]
+    except (TypeError, ValueError):
+        raise _lib.WesupHipError(f'{name}: views {views!r}') from None
+    if not 1 <= len(views) <= 8 or len(set(views)) != len(views) or any(not 0 <= v < 8 for v in views):
+        raise _lib.WesupHipError(f'{name}: views {views}, expected 1 .. 8 distinct indices in [0, 8)')
+    return len(views), sum(v << (4 * t) for t, v in enumerate(views))
+
+
+def window_gather_views(img_u8_hwc, tops, lefts, p, views, first, count, out=None):
+    """``window_gather`` over the slots of windows x views: slot ``s`` is window ``s // V`` under view ``views[s % V]``
+    (infer_tile.apply_view) -> (count,3,p,p) fp32, the slots ``first .. first + count - 1``, each bit-equal to
+    ``_to_tensor(apply_view(window, v))``.  Slots past the last one repeat it."""
+    H, W = _image_u8(img_u8_hwc, 'window_gather_views')
+    first, count, p = int(first), int(count), int(p)
+    if first < 0 or count < 1:
+        raise _lib.WesupHipError(f'window_gather_views: slots [{first}, {first} + {count})')
+    V, word = _view_word(views, 'window_gather_views')
+    tops_d, lefts_d = _lattice(tops, lefts, H, W, p, img_u8_hwc.device)
+    _chk(img_u8_hwc, torch.uint8, 'img')
+    out = _out(out, (count, 3, p, p), torch.float32, img_u8_hwc.device, 'window_gather_views')
+    if out.data_ptr() % 16:
+        raise _lib.WesupHipError('window_gather_views: out is not 16-byte aligned')
+    tok = _tbegin('window_gather_views')
+    _lib.call('wesup_window_gather_views', _p(img_u8_hwc), _p(tops_d), _p(lefts_d), _p(out), H, W, tops_d.numel(), lefts_d.numel(),
+              p, V, word, first, count, _stream())
+    _tend(tok, 15.0 * count * p * p)                  # 3 bytes in, 3 floats out per slot pixel
+    return out
+
+
+def window_merge_views(pred, views, tops, lefts, H, W, round_first=False, out=None):
+    """Mean over the covering windows and their views: pred (N,V,p,p,C) or (N,V,p,p) fp32, every prediction in the space of its
+    view, for ALL N = len(tops) * len(lefts) windows (row-major) -> (H,W,C) / (H,W) fp64, equal to
+    infer_tile.combine_views_to_image bit for bit; ``round_first`` as in ``window_merge``."""
+    if not isinstance(pred, torch.Tensor) or pred.dim() not in (4, 5):
+        raise _lib.WesupHipError('window_merge_views: expected (N,V,p,p) or (N,V,p,p,C) predictions')
+    flat = pred.dim() == 4
+    N, Vp, p, p2 = pred.shape[:4]
+    C = 1 if flat else pred.shape[4]
+    H, W = int(H), int(W)
+    V, word = _view_word(views, 'window_merge_views')
+    if p != p2 or C < 1 or Vp != V:
+        raise _lib.WesupHipError(f'window_merge_views: pred {tuple(pred.shape)} for {V} views')
+    tops_d, lefts_d = _lattice(tops, lefts, H, W, p, pred.device)
+    if N != tops_d.numel() * lefts_d.numel():
+        raise _lib.WesupHipError(f'window_merge_views: {N} windows for a lattice of {tops_d.numel()} x {lefts_d.numel()}')
+    _chk(pred, name='pred')
+    out = _out(out, (H, W) if flat else (H, W, C), torch.float64, pred.device, 'window_merge_views')
+    tok = _tbegin('window_merge_views')
+    _lib.call('wesup_window_merge_views', _p(pred), _p(tops_d), _p(lefts_d), _p(out), H, W, C, tops_d.numel(), lefts_d.numel(), p,
+              V, word, int(bool(round_first)), _stream())
+    _tend(tok, 4.0 * N * V * p * p * C + 8.0 * H * W * C)
+    return out
+
+
 # ---------------------------------------------------------------- whole-image multi-scale pixel inference (csrc/pixel.hip)
 def image_resize_u8(img_u8_hwc, h, w, out=None):
     """to_tensor + F.interpolate(mode='bilinear', align_corners=True) of pixel_infer.py:40,46 in one pass: img (H,W,3) uint8 on
@@ -2001,6 +2059,33 @@ def window_merge_classes(pred, tops, lefts, H, W, n_classes=None, votes=False, o
     _lib.call('wesup_window_merge_classes', _p(pred), _p(tops_d), _p(lefts_d), _p(out), _p(status), H, W, C, tops_d.numel(),
               lefts_d.numel(), p, int(votes), _stream())
     _tend(tok, 4.0 * N * p * p * (1 if votes else C) + 1.0 * H * W)
+    return out, status
+
+
+def window_merge_classes_views(pred, views, tops, lefts, H, W, n_classes=None, votes=False, out=None, status=None):
+    """``window_merge_classes`` over windows x views -> (out (H,W) uint8, status (1,) int32), equal to
+    infer_tile.combine_views_to_classes bit for bit.  ``votes=False``: pred (N,V,p,p,C) fp32 probabilities; ``votes=True``: pred
+    (N,V,p,p) fp32 class indices and ``n_classes``, every (window, view) votes.  Every prediction is in the space of its view."""
+    votes = bool(votes)
+    if not isinstance(pred, torch.Tensor) or pred.dim() != (4 if votes else 5):
+        raise _lib.WesupHipError('window_merge_classes_views: expected (N,V,p,p,C) probabilities, or (N,V,p,p) class indices with '
+                                 'votes=True')
+    N, Vp, p, p2 = pred.shape[:4]
+    C = _classes_of(pred, n_classes, votes, 'window_merge_classes_views')
+    H, W = int(H), int(W)
+    V, word = _view_word(views, 'window_merge_classes_views')
+    if p != p2 or Vp != V:
+        raise _lib.WesupHipError(f'window_merge_classes_views: pred {tuple(pred.shape)} for {V} views')
+    tops_d, lefts_d = _lattice(tops, lefts, H, W, p, pred.device)
+    if N != tops_d.numel() * lefts_d.numel():
+        raise _lib.WesupHipError(f'window_merge_classes_views: {N} windows for a lattice of {tops_d.numel()} x {lefts_d.numel()}')
+    _chk(pred, name='pred')
+    out = _out(out, (H, W), torch.uint8, pred.device, 'window_merge_classes_views')
+    status = _status(status, pred.device, 'window_merge_classes_views')
+    tok = _tbegin('window_merge_classes_views')
+    _lib.call('wesup_window_merge_classes_views', _p(pred), _p(tops_d), _p(lefts_d), _p(out), _p(status), H, W, C, tops_d.numel(),
+              lefts_d.numel(), p, V, word, int(votes), _stream())
+    _tend(tok, 4.0 * N * V * p * p * (1 if votes else C) + 1.0 * H * W)
     return out, status
 
 
