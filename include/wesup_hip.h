@@ -37,7 +37,7 @@ extern "C" {
  * LDS limit once; a wider D is WESUP_ERR_INVALID and nothing is launched. */
 #define WESUP_HEAD_MAX_D 149
 
-/* flags for wesup_gemm_nt */
+/* flags for wesup_gemm_nt.  Order: result = relu_in(A) . B^T + bias; MASK; ACCUM adds the old C; RELU_OUT clamps what is stored */
 #define WESUP_RELU_IN 1    /* A := max(A, 0) while loading */
 #define WESUP_RELU_OUT 2   /* C := max(C, 0) */
 #define WESUP_ACCUM 4      /* C += result */

@@ -141,8 +141,12 @@ def test_freeze_backbone():
 def test_buffer_cache_is_bounded_over_changing_shapes():
     """Multi-scale training meets a new (H, W, superpixel count) almost every iteration: the engine keeps the buffers
     of the most recent shapes only, so device memory stays bounded instead of growing by a buffer set per shape."""
+    import gc
     from oracle import wesup_oracle as orc
     from wesup_amd import synth
+    # torch.cuda.memory_allocated() below counts the whole process: the trainers of earlier tests are cyclic garbage with gigabytes
+    # of buffers, and a collection that happens to fall between two of the measurements would read as a change of this engine's
+    gc.collect()
     trainer = make_trainer(orc.make_weights(2, feat_scale=0.05))
     trainer.model._ensure_engine()
     eng = trainer.model.engine

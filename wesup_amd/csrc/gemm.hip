@@ -388,7 +388,7 @@ __global__ __launch_bounds__(NW * 64, MINB) void gemm_nt_kernel(const NtParams p
                 if (m >= p.M) break;
                 float4 v = ld4(Cs + rr * LDC + 4 * cq);
                 v.x += bv.x; v.y += bv.y; v.z += bv.z; v.w += bv.w;
-                if (relu_out) v = relu4(v);
+                if (relu_out && !accum) v = relu4(v);      // (commutes with the mask; with ACCUM it comes after the sum, below)
                 if (use_mask) {
                     const float4 mk = ld4(p.mask + (long)m * p.ldmask + n);
                     v.x = mk.x > 0.f ? v.x : 0.f;
@@ -400,6 +400,7 @@ __global__ __launch_bounds__(NW * 64, MINB) void gemm_nt_kernel(const NtParams p
                 if (accum) {
                     const float4 o = ld4(c);
                     v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w;
+                    if (relu_out) v = relu4(v);            // C := max(C, 0) applies to what is stored (include/wesup_hip.h)
                 }
                 st4s(c, v, nt);
                 if (p.C2) st4s(p.C2 + (long)m * p.ldc + n, relu4(v), nt);
@@ -453,7 +454,6 @@ __global__ __launch_bounds__(256) void nt_fixup_kernel(const NtParams p) {
         const float4 bv = ld4(p.bias + n);
         v.x += bv.x; v.y += bv.y; v.z += bv.z; v.w += bv.w;
     }
-    if (p.flags & WESUP_RELU_OUT) v = relu4(v);
     if (p.flags & WESUP_MASK) {
         const float4 mk = ld4(p.mask + (long)m * p.ldmask + n);
         v.x = mk.x > 0.f ? v.x : 0.f;
@@ -466,6 +466,7 @@ __global__ __launch_bounds__(256) void nt_fixup_kernel(const NtParams p) {
         const float4 o = ld4(c);
         v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w;
     }
+    if (p.flags & WESUP_RELU_OUT) v = relu4(v);
     st4(c, v);
     if (p.C2) st4(p.C2 + (long)m * p.ldc + n, relu4(v));
 }
