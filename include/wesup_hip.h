@@ -534,6 +534,33 @@ int wesup_directed_hausdorff_sq(const int32_t* pairs, const int32_t* start_x, co
                                 const int32_t* bstart_y, const int32_t* bpix_y, int32_t* d2, int P, int H, int W, int LX, int LY,
                                 void* stream);
 
+/* ------------------------------------------------------------------ splitting touching objects (csrc/split.hip)
+ * Masks uint8 [B][H][W] (non-zero = foreground), label maps and distance maps int32 [B][H][W]; B, H, W <= 65535.  All integer,
+ * equal to the numpy restatement in wesup_amd/split.py bit for bit.  Every entry returns WESUP_ERR_INVALID for a null pointer, a
+ * non-positive or oversized shape, a short workspace and the argument ranges named below, on the host and before any launch.
+ *
+ * wesup_edt_sq: d2 = 0 on the background, elsewhere min(cap, squared Euclidean distance to the nearest background pixel of the same
+ * image); pixels outside the image are not background (scipy.ndimage.distance_transform_edt); 1 <= cap <= 65025. */
+#define WESUP_SPLIT_SEG 64   /* the row pass stages segments of this many pixels, WESUP_SPLIT_ROWS rows per block */
+#define WESUP_SPLIT_ROWS 4
+#define WESUP_SPLIT_TILE 32  /* the growth kernel's tile edge */
+#define WESUP_SPLIT_HALO 8   /* ... and its halo: the most rounds of one launch */
+size_t wesup_edt_sq_workspace_bytes(int B, int H, int W);
+int wesup_edt_sq(const uint8_t* mask, int32_t* d2, int B, int H, int W, int cap, void* ws, size_t ws_bytes, void* stream);
+/* `launches` launches of `rounds` synchronous growth rounds each (rounds even, 2 .. WESUP_SPLIT_HALO), the first of them round
+ * number first_round >= 1 (odd rounds look at the 4-neighbourhood, even rounds at the 8-neighbourhood): in a round every foreground
+ * pixel without a label takes the smallest positive label among its neighbours as they stood before the round.  seeds: any int32
+ * (labels up to 2^31 - 1), values <= 0 and values on the background count as no label; labels receives the map after the last
+ * launch (0 on the background).  seeds, labels and ws are three maps that share no byte with each other, with mask or with
+ * changed: anything else is WESUP_ERR_INVALID.  changed (one device word) is zeroed here before the last launch and set to 1 when a pixel took a label in that
+ * launch: 0 means the map is the fixed point (a launch holds a round of either kind), whatever the earlier launches did. */
+size_t wesup_label_grow_workspace_bytes(int B, int H, int W);
+int wesup_label_grow(const uint8_t* mask, const int32_t* seeds, int32_t* labels, int32_t* changed, int B, int H, int W,
+                     int first_round, int launches, int rounds, void* ws, size_t ws_bytes, void* stream);
+/* out = 0 on the background and where a pixel's label a > 0 has an 8-neighbour with a label 0 < b < a; 1 elsewhere.  out shares
+ * no byte with mask or labels */
+int wesup_label_cut(const uint8_t* mask, const int32_t* labels, uint8_t* out, int B, int H, int W, void* stream);
+
 /* ------------------------------------------------------------------ painted object comparisons (csrc/paint.hip)
  * wesup_object_match: tables [B][nS + 1][nG + 1] as wesup_contingency writes them (nS, nG: the maxima of the batch), nS_dev /
  * nG_dev [B]: each image's own object counts (wesup_cc_label's n_labels); cells outside an image's own counts are not read.

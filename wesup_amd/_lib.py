@@ -135,6 +135,12 @@ _SIGS = {
     'wesup_label_sort_workspace_bytes': (c_size_t, 'iiii'),
     'wesup_label_sort': (c_int, 'pppppp' + 'iiii' + 'pzp'),
     'wesup_directed_hausdorff_sq': (c_int, 'ppppppp' + 'iiiii' + 'p'),
+    # splitting touching objects: distance map, label growth, cut (csrc/split.hip)
+    'wesup_edt_sq_workspace_bytes': (c_size_t, 'iii'),
+    'wesup_edt_sq': (c_int, 'pp' + 'iiii' + 'pzp'),
+    'wesup_label_grow_workspace_bytes': (c_size_t, 'iii'),
+    'wesup_label_grow': (c_int, 'pppp' + 'iiiiii' + 'pzp'),
+    'wesup_label_cut': (c_int, 'ppp' + 'iii' + 'p'),
     # painted object comparisons (csrc/paint.hip)
     'wesup_object_match_workspace_bytes': (c_size_t, 'ii'),
     'wesup_object_match': (c_int, 'pppp' + 'iii' + 'pzp'),
@@ -226,6 +232,8 @@ SELECT_BLOCK = 256       # WESUP_SELECT_BLOCK
 SELECT_MAX_BLOCKS = 256  # WESUP_SELECT_MAX_BLOCKS
 SELECT_MAX_RANKS = 4     # WESUP_SELECT_MAX_RANKS
 STAIN_BLOCK = 16         # WESUP_STAIN_BLOCK: HE[3][2], pinv[2][3], maxC[2], n_tissue, valid
+SPLIT_SEG, SPLIT_ROWS = 64, 4      # WESUP_SPLIT_SEG, WESUP_SPLIT_ROWS: the distance map's row pass, 4 rows of 64 pixels per block
+SPLIT_TILE, SPLIT_HALO = 32, 8     # WESUP_SPLIT_TILE, WESUP_SPLIT_HALO: the growth kernel's tile edge and halo (rounds per launch)
 ABI_VERSION = 6          # include/wesup_hip.h; a stale libwesup_hip.so with other signatures must not be called
 
 _lib = None

@@ -79,11 +79,21 @@ def score(predictions, gts, binarize_gt=False, device=None):
     return rows, means
 
 
-def _evaluate_paths(pred_paths, gt_paths, new_pred_dir, csv_path, min_size, log, device):
+def split_objects(pred, radius, device=None):
+    """Separate touching objects of a post-processed prediction (split.split_objects, DESIGN.md 3.18) -> the same float64 {0, 1}
+    array as ``remove_small_regions`` returns."""
+    from . import split
+    return split.split_objects(np.asarray(pred) != 0, radius, device).astype(np.float64)
+
+
+def _evaluate_paths(pred_paths, gt_paths, new_pred_dir, csv_path, min_size, log, device, split_radius=None):
     """Post-process the predictions (0/255 images), optionally save them, score them against the ground truth as read, log the
-    five means and optionally write the per-image csv -> (rows, means, post-processed predictions)."""
+    five means and optionally write the per-image csv -> (rows, means, post-processed predictions).  With ``split_radius``
+    touching objects are separated after the small-region rule; the saved maps and the scores are those of the split maps."""
     from PIL import Image
     predictions = [remove_small_regions(_read_mask(p) / 255, min_size, device) for p in pred_paths]
+    if split_radius is not None:
+        predictions = [split_objects(p, split_radius, device) for p in predictions]
     gts = [_read_mask(p) for p in gt_paths]
     if new_pred_dir is not None:
         Path(new_pred_dir).mkdir(parents=True, exist_ok=True)
@@ -102,7 +112,8 @@ def _evaluate_paths(pred_paths, gt_paths, new_pred_dir, csv_path, min_size, log,
     return rows, means, predictions
 
 
-def evaluate_split(pred_dir, gt_dir, new_pred_dir=None, csv_path=None, min_size=MIN_REGION, log=print, device=None):
+def evaluate_split(pred_dir, gt_dir, new_pred_dir=None, csv_path=None, min_size=MIN_REGION, log=print, device=None,
+                   split_radius=None):
     """One test split: read predictions (0/255 images) and ground-truth object maps in sorted order, post-process,
     optionally save the new predictions and the per-image csv (columns of scripts/evaluate_glas.py:62-66)."""
     exts = ('*.bmp', '*.png')
@@ -110,10 +121,10 @@ def evaluate_split(pred_dir, gt_dir, new_pred_dir=None, csv_path=None, min_size=
     gt_paths = sorted(p for e in exts for p in Path(gt_dir).glob(e))
     if len(pred_paths) != len(gt_paths):
         raise ValueError(f'{len(pred_paths)} predictions in {pred_dir} but {len(gt_paths)} masks in {gt_dir}')
-    return _evaluate_paths(pred_paths, gt_paths, new_pred_dir, csv_path, min_size, log, device)[:2]
+    return _evaluate_paths(pred_paths, gt_paths, new_pred_dir, csv_path, min_size, log, device, split_radius)[:2]
 
 
-def evaluate_flat(pred_root, gt_dir, min_size=MIN_REGION_FLAT, log=print, device=None, csv_path=None):
+def evaluate_flat(pred_root, gt_dir, min_size=MIN_REGION_FLAT, log=print, device=None, csv_path=None, split_radius=None):
     """scripts/evaluate_crag.py and scripts/evaluate_pdl1.py (one script but for the ground-truth directory): the ``*.png``
     of ``pred_root`` against the ``*.png`` of ``gt_dir``, both sorted, the ground truth used as read; small regions and holes
     below ``min_size`` = 5000 pixels are removed, the post-processed maps go to ``<pred_root>-new/`` and the five means are
@@ -127,10 +138,10 @@ def evaluate_flat(pred_root, gt_dir, min_size=MIN_REGION_FLAT, log=print, device
     if len(pred_paths) != len(gt_paths):
         raise ValueError(f'{len(pred_paths)} predictions in {pred_root} but {len(gt_paths)} masks in {gt_dir}')
     new_root = pred_root.parent / (pred_root.name + '-new')
-    return _evaluate_paths(pred_paths, gt_paths, new_root, csv_path, min_size, log, device)
+    return _evaluate_paths(pred_paths, gt_paths, new_root, csv_path, min_size, log, device, split_radius)
 
 
-def evaluate_glas(pred_root, gt_root='~/data/GLAS_all', min_size=MIN_REGION, log=print, device=None):
+def evaluate_glas(pred_root, gt_root='~/data/GLAS_all', min_size=MIN_REGION, log=print, device=None, split_radius=None):
     """scripts/evaluate_glas.py: testA and testB under ``pred_root`` against ``gt_root/<split>/masks``; post-processed
     predictions go to ``<pred_root>-new/<split>``, per-image metrics to ``pred_root/<split>.csv``."""
     pred_root, gt_root = Path(pred_root).expanduser(), Path(gt_root).expanduser()
@@ -141,7 +152,7 @@ def evaluate_glas(pred_root, gt_root='~/data/GLAS_all', min_size=MIN_REGION, log
             continue
         log(title)
         result[split] = evaluate_split(pred_root / split, gt_root / split / 'masks', new_root / split,
-                                       pred_root / f'{split}.csv', min_size, log, device)[1]
+                                       pred_root / f'{split}.csv', min_size, log, device, split_radius)[1]
     return result
 
 
@@ -166,7 +177,7 @@ def test(ckpt_path, model_type='wesup', input_size=None, scales=(0.5,), device='
     return results_dir
 
 
-def main(argv=None):
+def build_parser():
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     ap.add_argument('pred_root', nargs='?')
     ap.add_argument('--gt-root', default='~/data/GLAS_all')
@@ -183,16 +194,26 @@ def main(argv=None):
     ap.add_argument('--data-root', default='~/data/GLAS_all')
     ap.add_argument('-d', '--device', default='cuda')
     ap.add_argument('--gpu-scoring', action='store_true', help='post-process and score on --device instead of the CPU')
-    a = ap.parse_args(argv)
+    ap.add_argument('--split-objects', type=int, metavar='R', dest='split_objects',
+                    help='separate touching objects after the small-region rule: seed radius in pixels, 1 .. 255 '
+                         '(wesup_amd/split.py; glas, crag and lusc)')
+    return ap
+
+
+def main(argv=None):
+    a = build_parser().parse_args(argv)
+    if a.split_objects is not None and not 1 <= a.split_objects <= 255:
+        raise SystemExit(f'--split-objects {a.split_objects}: expected 1 .. 255')
+    extra = {} if a.split_objects is None else {'split_radius': a.split_objects}      # (without the flag: the calls of before)
     if a.test:
         size = [int(s) for s in a.input_size.split(',')] if a.input_size else None
         test(a.checkpoint, a.model, size, tuple(float(s) for s in a.scales.split(',')), a.device, a.data_root)
     elif a.dataset == 'glas':
         evaluate_glas(a.pred_root, a.gt_root, MIN_REGION if a.min_size is None else a.min_size,
-                      device=a.device if a.gpu_scoring else None)
+                      device=a.device if a.gpu_scoring else None, **extra)
     else:
         evaluate_flat(a.pred_root, a.gt_dir or FLAT_GT_DIRS[a.dataset], MIN_REGION_FLAT if a.min_size is None else a.min_size,
-                      device=a.device if a.gpu_scoring else None)
+                      device=a.device if a.gpu_scoring else None, **extra)
 
 
 if __name__ == '__main__':

@@ -1417,6 +1417,89 @@ def binary_opening(mask, footprint):
     return binary_morph(mask, footprint, MORPH_OPEN)
 
 
+# ---------------------------------------------------------------- splitting touching objects (csrc/split.hip)
+GROW_ROUNDS = _lib.SPLIT_HALO     # rounds of one growth launch: the kernel's halo
+GROW_CADENCE = 4                  # growth launches per read-back of the changed word (measured: profiles/split_micro.txt)
+
+
+def edt_sq(mask, cap):
+    """Capped squared distance map: mask (H,W) / (B,H,W) uint8 -> int32 of the same shape, 0 on the background and elsewhere
+    min(cap, squared distance to the nearest background pixel of the same image); 1 <= cap <= 65025 (split.edt_sq_host)."""
+    m, squeeze = _mask3(mask)
+    B, H, W = m.shape
+    if not 1 <= int(cap) <= 255 * 255:
+        raise _lib.WesupHipError(f'edt_sq: cap {cap} (1 .. 65025)')
+    d2 = torch.empty(B, H, W, dtype=torch.int32, device=m.device)
+    nb = _lib.load().wesup_edt_sq_workspace_bytes(B, H, W)
+    ws = workspace(nb, m.device, 'regions')
+    _lib.call('wesup_edt_sq', _p(m), _p(d2), B, H, W, int(cap), _p(ws), nb, _stream())
+    return d2[0] if squeeze else d2
+
+
+def label_grow(mask, seeds, cadence=None, rounds=None, return_launches=False):
+    """Grow the positive labels of ``seeds`` (int32, any positive values) over the foreground of ``mask`` to the fixed point of
+    split.label_grow_host: mask, seeds (H,W) / (B,H,W) -> int32 labels of the same shape.  ``rounds`` synchronous rounds per
+    launch (even, at most GROW_ROUNDS), ``cadence`` launches between two read-backs of the changed word, which reports the last
+    launch of the group; growth stops after the first read-back of a launch that changed nothing.  Launches past the fixed point
+    change nothing, so neither knob changes the map."""
+    m, squeeze = _mask3(mask)
+    _chk(seeds, torch.int32, 'seeds')
+    if seeds.shape != mask.shape:
+        raise _lib.WesupHipError(f'label_grow: seeds {tuple(seeds.shape)} for a mask {tuple(mask.shape)}')
+    cadence = GROW_CADENCE if cadence is None else int(cadence)
+    rounds = GROW_ROUNDS if rounds is None else int(rounds)
+    if cadence < 1 or rounds < 2 or rounds > GROW_ROUNDS or rounds % 2:
+        raise _lib.WesupHipError(f'label_grow: cadence {cadence} (>= 1), rounds {rounds} (even, 2 .. {GROW_ROUNDS})')
+    B, H, W = m.shape
+    src = seeds.reshape(B, H, W)
+    bufs = [torch.empty(B, H, W, dtype=torch.int32, device=m.device) for _ in range(2)]
+    changed = torch.empty(1, dtype=torch.int32, device=m.device)
+    nb = _lib.load().wesup_label_grow_workspace_bytes(B, H, W)
+    ws = workspace(nb, m.device, 'regions')
+    launches = 0
+    while True:
+        dst = bufs[0] if src is not bufs[0] else bufs[1]
+        _lib.call('wesup_label_grow', _p(m), _p(src), _p(dst), _p(changed), B, H, W, 1 + launches * rounds, cadence, rounds,
+                  _p(ws), nb, _stream())
+        launches += cadence
+        src = dst
+        if int(changed.item()) == 0:
+            break
+    out = src[0] if squeeze else src
+    return (out, launches) if return_launches else out
+
+
+def label_cut(mask, labels):
+    """mask uint8, labels int32 (H,W) / (B,H,W) -> uint8 {0,1}: 0 on the background and where a pixel's label a > 0 has an
+    8-neighbour with a label 0 < b < a (split.label_cut_host)."""
+    m, squeeze = _mask3(mask)
+    _chk(labels, torch.int32, 'labels')
+    if labels.shape != mask.shape:
+        raise _lib.WesupHipError(f'label_cut: labels {tuple(labels.shape)} for a mask {tuple(mask.shape)}')
+    B, H, W = m.shape
+    out = torch.empty_like(m)
+    _lib.call('wesup_label_cut', _p(m), _p(labels), _p(out), B, H, W, _stream())
+    return out[0] if squeeze else out
+
+
+def split_objects(mask, radius, return_labels=False):
+    """Separate touching objects of a binary mask (H,W) / (B,H,W) uint8 -> uint8 {0,1}: the components of {edt_sq >= radius^2}
+    are the seeds (cc_label), their labels grow over the mask (label_grow) and a one-pixel cut is taken where two labels meet
+    (label_cut); 1 <= radius <= 255, radius 1 is the identity.  Equal to split.split_objects bit for bit.  A seed pixel is never
+    cut while different seeds lie more than 3 pixels apart; two cores closer than that lose a pixel of the larger label (the cut
+    still separates them)."""
+    radius = int(radius)
+    if not 1 <= radius <= 255:
+        raise _lib.WesupHipError(f'split_objects: radius {radius} (1 .. 255)')
+    _mask3(mask)
+    r2 = radius * radius
+    core = (edt_sq(mask, r2) >= r2).to(torch.uint8)
+    seeds, _ = cc_label(core)
+    labels = label_grow(mask, seeds)
+    out = label_cut(mask, labels)
+    return (out, labels) if return_labels else out
+
+
 def contingency(S, G, nS, nG):
     """Label maps S, G (H,W) / (B,H,W) int32 with labels in [0, nS] / [0, nG] -> (B, nS+1, nG+1) int32 pixel counts (the batch
     axis only for batched input).  Raises when a label lies outside the table or the table would exceed
