@@ -96,7 +96,18 @@ int wesup_appearance(const uint8_t* img_hwc, const float* params, uint8_t* out_h
 /* ------------------------------------------------------------------ VGG16 3x3 convs (K1/K2/K12)
  * replaces torchvision VGG16 Conv2d(k=3,pad=1)+ReLU (models/wesup.py:199,279) and its autograd.
  * y is the PRE-ReLU output (the hook taps it, models/wesup.py:246-253); the next
- * layer applies ReLU while loading (relu_in).  x has Cin channels (4 for the image). */
+ * layer applies ReLU while loading (relu_in).  x has Cin channels (4 for the image).
+ * Arguments of the direct entries (wesup_conv3x3_fwd, _fwd_side, _dgrad, _wgrad); anything else is WESUP_ERR_INVALID and
+ * nothing is launched:
+ *   - the channel count of the output tensor (Cout forward, Cin for dgrad) is a multiple of 4, that of the input tensor
+ *     4 (the image) or a power of two >= 32; wgrad: Cout a multiple of 32;
+ *   - x, w, y, y_relu, bias, dy, mask_src, dx, side_w, side_bias, side_out and the wgrad workspace are 16-byte aligned
+ *     (dw_kcrs and db: 4-byte);
+ *   - B*H*W * max(Cin, Cout) < 2^31 (wgrad: B*H*W < 2^31);
+ *   - the kernels find a pixel's (image, row, column) by multiply-high divisions by W and H (csrc/common.hpp, FastDiv:
+ *     m = ceil(2^40 / d), exact for n*d <= 2^40 and n*m < 2^64), so B*H*W * W <= 2^40, B*H * H <= 2^40 and
+ *     (B*H*W - 1) * ceil(2^40 / W) < 2^64, (B*H - 1) * ceil(2^40 / H) < 2^64 -- the last two bind only when B*H or B
+ *     reaches 2^24. */
 /* ws (optional, may be NULL): room for the partial accumulator tiles of the stream-K blocks that balance a short last
  * round of tiles over all block slots; without it the plain tiling is used.  Size for (Cin -> Cout); for dgrad ask
  * with the channel counts swapped.  One workspace per stream that may run concurrently. */

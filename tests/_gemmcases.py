@@ -107,20 +107,21 @@ def ntbb_route(nbatch, M, N, K):
 
 
 # ---------------------------------------------------------------- TN family
-TnPlan = namedtuple('TnPlan', 'tile tiles_m tiles_n S k_per_split')
+TnPlan = namedtuple('TnPlan', 'tile tiles_m tiles_n S k_per_split taps', defaults=(1,))
 
 
-def plan_tn(M, N, K, nbatch=1):
+def plan_tn(M, N, K, nbatch=1, taps=1):
+    """taps: the nine taps of a direct conv3x3 weight gradient ride in grid.x and count as tiles, exactly where nbatch does."""
     big = M >= 128 and N >= 128
     ks = cdiv(K, BK)
     if big:
-        t128 = cdiv(M, 128) * cdiv(N, 128) * nbatch
+        t128 = cdiv(M, 128) * cdiv(N, 128) * taps * nbatch
         ms = 32 if ks // 8 > 32 else (ks // 8 if ks // 8 > 0 else 1)
         if t128 * ms < 384:
             big = False
     tile = 128 if big else 64
     tiles_m, tiles_n = cdiv(M, tile), cdiv(N, tile)
-    tiles = tiles_m * tiles_n * nbatch
+    tiles = tiles_m * tiles_n * taps * nbatch
     slots = 256 * (2 if big else 4)
     maxS = ks // 8 if ks // 8 > 0 else 1
     S, best = 1, -1.0
@@ -135,7 +136,7 @@ def plan_tn(M, N, K, nbatch=1):
     if S > 32 and tiles * 32 >= 192:
         S = 32
     k_per_split = cdiv(ks, S) * BK
-    return TnPlan(tile, tiles_m, tiles_n, cdiv(K, k_per_split), k_per_split)
+    return TnPlan(tile, tiles_m, tiles_n, cdiv(K, k_per_split), k_per_split, taps)
 
 
 def slab_fold_chunks(S):
@@ -147,7 +148,7 @@ def tn_direct(pl, colsum, ldc, c_addr=0, strideC=0):
 
 
 def tn_weighted(pl, nbatch=1):
-    return pl.tile == 128 and nbatch == 1 and pl.S >= 2 and pl.tiles_m * pl.tiles_n * pl.S <= 512
+    return pl.tile == 128 and nbatch == 1 and pl.S >= 2 and pl.tiles_m * pl.tiles_n * pl.taps * pl.S <= 512
 
 
 def tn_store(pl, colsum=False, ldc=0, strideC=0):

@@ -22,7 +22,11 @@ static inline unsigned grid_stride_blocks(long total, int block, int max_blocks)
     return (unsigned)(nb > max_blocks ? max_blocks : (nb < 1 ? 1 : nb));
 }
 
-// Exact n / d for n*d < 2^40 via one 64-bit multiply (n < 2^26 pixels, d < 2^12 here).
+// Exact n / d via one 64-bit multiply by m = ceil(2^40 / d).  With m d = 2^40 + e, 0 <= e < d, and n = q d + r:
+//     n m / 2^40 = q + r / d + n e / (d 2^40),   which is below q + 1 as long as   n e < 2^40 (r <= d - 1),
+// so the quotient is exact for every dividend n with n (d - 1) < 2^40 -- n d <= 2^40 is what fastdiv_exact() asks -- and the
+// product must not wrap: n m < 2^64 (only binds when n / d reaches 2^24: one-pixel-wide images).  The entries that divide
+// pixel indices by an image's W and H refuse shapes outside this range (fastdiv_exact below); the kernels never test it.
 struct FastDiv {
     unsigned long long m;
     int d;
@@ -37,6 +41,17 @@ static inline FastDiv make_fastdiv(int d) {
 }
 __device__ __forceinline__ int fast_div(int n, const FastDiv f) {
     return (int)(((unsigned long long)(unsigned)n * f.m) >> 40);
+}
+// fast_div(n, make_fastdiv(d)) == n / d for every 0 <= n < count (the derivation above): count * d <= 2^40, and the largest
+// product (count - 1) * m stays below 2^64
+static inline bool fastdiv_exact(long count, int d) {
+    if (count <= 0 || d <= 0) return false;
+    if ((unsigned __int128)count * (unsigned)d > ((unsigned __int128)1 << 40)) return false;
+    return (unsigned __int128)(count - 1) * make_fastdiv(d).m < ((unsigned __int128)1 << 64);
+}
+// pixel index -> (image, row, column) of a (B, H, W) tensor: the pixel index by W, then image * H + row by H
+static inline bool fastdiv_image_exact(int B, int H, int W) {
+    return fastdiv_exact((long)B * H * W, W) && fastdiv_exact((long)B * H, H);
 }
 
 // Bijective XCD-aware block remap (cdna_hip_programming.md 5, "XCD swizzle must be bijective"):

@@ -678,8 +678,13 @@ static int conv_common(const float* x, const float* w, const float* bias, float*
     const bool small = (Cin == 4);
     if (!small && (Cin < 32 || (Cin & (Cin - 1)))) return WESUP_ERR_INVALID;
     if ((long)B * H * W * (long)(Cin > Cout ? Cin : Cout) >= (1l << 31)) return WESUP_ERR_INVALID;
+    // the epilogue moves float4 pieces of the output rows (and of bias and mask): whole quads, 16-byte aligned
+    if (Cout <= 0 || (Cout % 4)) return WESUP_ERR_INVALID;
+    if (((uintptr_t)x | (uintptr_t)w | (uintptr_t)y | (uintptr_t)y_relu | (uintptr_t)bias | (uintptr_t)mask) & 15)
+        return WESUP_ERR_INVALID;
+    if ((flags & WESUP_MASK) && !mask) return WESUP_ERR_INVALID;
+    if (!fastdiv_image_exact(B, H, W)) return WESUP_ERR_INVALID;      // pixel -> (image, row, column) by fast_div (common.hpp)
     NtParams p = {};
-    if (y_relu && ((uintptr_t)y_relu & 15)) return WESUP_ERR_INVALID;
     p.A = x; p.Bw = w; p.bias = bias; p.C = y; p.C2 = y_relu; p.mask = mask;
     p.M = B * H * W; p.N = Cout; p.K = wesup_conv3x3_kpad(Cin);
     p.lda = Cin; p.ldb = p.K; p.ldc = Cout; p.ldmask = Cout;
@@ -1357,7 +1362,10 @@ extern "C" int wesup_conv3x3_wgrad(const float* x, const float* dy, float* dw_kc
     const bool small = Ci < 32;
     if (small && Ci != 3) return WESUP_ERR_INVALID;
     if (!small && (Ci & (Ci - 1))) return WESUP_ERR_INVALID;
-    if (Cout % 32) return WESUP_ERR_INVALID;
+    if (Cout <= 0 || (Cout % 32)) return WESUP_ERR_INVALID;
+    // x, dy and the slabs move 16 bytes per lane; dw and db are written float by float
+    if ((((uintptr_t)x | (uintptr_t)dy | (uintptr_t)ws) & 15) || (((uintptr_t)dw_kcrs | (uintptr_t)db) & 3)) return WESUP_ERR_INVALID;
+    if ((long)B * H * W >= (1l << 31) || !fastdiv_image_exact(B, H, W)) return WESUP_ERR_INVALID;   // pixel -> (image, row, column) by fast_div (common.hpp)
     if (ws_bytes < wesup_conv3x3_wgrad_workspace_bytes(B, H, W, Ci, Cout)) return WESUP_ERR_WORKSPACE;
     const TnPlan pl = plan_wgrad(B, H, W, Ci, Cout);
     hipStream_t st = (hipStream_t)stream;
