@@ -667,6 +667,42 @@ int wesup_patch_scatter_u8(const float* pred, uint8_t* out, int H, int W, int p,
  * x -> 255 - x on both maps with `negative` (compute_metrics(negative=True), test_dp2019_pipeline.py:100-111).  Integer counts,
  * exact in any order; accuracy = eq / n and dice = 2 * inter / (sumG + sumS + 1e-7) are the host's, in float64. */
 int wesup_mask_scores(const uint8_t* S, const uint8_t* G, int64_t* out4, long n, int negative, void* stream);
+/* The two entries above over a patch list: list int32 [n_list] in device memory, n_list >= 1 (a null list or
+ * n_list < 1 is WESUP_ERR_INVALID).  Slot i of the pass, 0 <= i < count, stands for list[first + i].  The gather reads
+ * list[min(first + i, n_list - 1)]: a ragged last pass repeats the last listed patch.  The scatter skips a slot with
+ * first + i >= n_list.  A list value outside [0, n_h * n_w) never becomes an address: its slot is left unwritten (gather) or
+ * skipped (scatter).  A listed patch gets the bits the plain entry gives it. */
+int wesup_patch_gather_resize_list(const uint8_t* img, float* out, int H, int W, int p, int h, int w, int align_corners, int first,
+                                   int count, const int32_t* list, int n_list, void* stream);
+int wesup_patch_scatter_u8_list(const float* pred, uint8_t* out, int H, int W, int p, int h, int w, int stride, int mode, int first,
+                                int count, const int32_t* list, int n_list, void* stream);
+
+/* ------------------------------------------------------------------ tissue selection for whole-slide evaluation (csrc/tissue.hip)
+ * Which patches of the lattice above hold tissue (the host statement is wesup_amd/slide.py: pixel_value,
+ * patch_histograms, otsu_threshold, select_patches, and the kernels equal it bit for bit).  A pixel's value v in 0 .. 255:
+ * channel 0 (luma) (77 R + 150 G + 29 B + 128) >> 8, channel 1 (chroma) max(R, G, B) - min(R, G, B).  Tissue: luma v <= t, chroma
+ * v > t, t = -1 every pixel.  All entries: WESUP_ERR_INVALID without a launch for a null pointer, sizes outside the lattice's,
+ * p > 65535 (a cell of hist is a uint32), H * W > 2^32 (Otsu's integers stay below 2^64), a channel outside {0, 1}, a threshold
+ * outside [-1, 254] or min_ppm outside [0, 10^6].  Integer adds only, no workspace, no host sync.
+ *
+ * wesup_patch_value_hist: img uint8 [H][W][3] -> hist uint32 [n_h * n_w][256] (zeroed here), hist[k][v] = the slide pixels of
+ * patch k with value v; the zero padding is never counted.  One read of the slide.  The grid is at most WESUP_TISSUE_MAX_BLOCKS
+ * blocks striding over items of about WESUP_TISSUE_ITEM_PIXELS pixels, max(1, WESUP_TISSUE_ITEM_PIXELS / p) rows of one patch. */
+#define WESUP_TISSUE_MAX_BLOCKS 2048
+#define WESUP_TISSUE_ITEM_PIXELS 8192
+#define WESUP_TISSUE_LIST_CHUNK 256 /* patches per step of the ordered compaction */
+int wesup_patch_value_hist(const uint8_t* img, uint32_t* hist, int H, int W, int p, int channel, void* stream);
+/* hist -> total int64 [256] (8-byte aligned) = the sum over the patches; t = threshold, or with threshold = -1 Otsu's over total:
+ * for t = 0 .. 254 ascending, w0 = sum_{i <= t} h_i, s0 = sum_{i <= t} i h_i, D = w0 (N - w0), skipped where D = 0;
+ * num = |S w0 - s0 N| exactly (128 bits), x = (double)(num >> 64) * 2^64 + (double)(num mod 2^64), q = x * x / (double)D, no
+ * contraction; the first t with the largest q under a strict >, or -1 when no t has D > 0 (a one-level slide).
+ * counts uint32 [n] = the tissue pixels of every patch (a prefix or suffix sum of its histogram).  list int32 [n]: the kept patches
+ * in ascending order, kept = counts[k] >= 1 and counts[k] * 10^6 >= min_ppm * area_k, area_k the patch's pixels inside the slide
+ * (t = -1 keeps every patch); list beyond n_keep is not written.  info int32 [8] = {t, n_keep, n, flat (1 when t = -1), 0, 0, 0, 0}. */
+int wesup_tissue_select(const uint32_t* hist, int H, int W, int p, int channel, int threshold, int min_ppm, int32_t* info,
+                        int64_t* total, uint32_t* counts, int32_t* list, void* stream);
+/* out uint8 [H][W] = 255 where the pixel is tissue under t = info[0] (read on the device), else 0 */
+int wesup_tissue_mask_u8(const uint8_t* img, const int32_t* info, uint8_t* out, int H, int W, int channel, void* stream);
 
 /* ------------------------------------------------------------------ class maps for more than two classes (csrc/classmap.hip)
  * The merge, the resize back, the paste and the scoring of the three sections above as reductions over the C values of a pixel
@@ -701,6 +737,9 @@ int wesup_class_argmax_u8(const float* in, uint8_t* out, long n, int C, void* st
  * the first maximum.  *status is OR-ed into, not zeroed: it collects over the passes of a slide (the caller zeroes it once). */
 int wesup_patch_scatter_classes_u8(const float* pred, uint8_t* out, int32_t* status, int H, int W, int p, int h, int w, int C,
                                    int mode, int first, int count, void* stream);
+/* ... over a patch list, as wesup_patch_scatter_u8_list; a list value outside the lattice is skipped and sets *status */
+int wesup_patch_scatter_classes_u8_list(const float* pred, uint8_t* out, int32_t* status, int H, int W, int p, int h, int w, int C,
+                                        int mode, int first, int count, const int32_t* list, int n_list, void* stream);
 /* S, G uint8 [n] class-index maps (n <= 2^40) -> conf int64 [C][C] (8-byte aligned), conf[g][s] = positions with ground truth g
  * predicted as s: utils.metrics.confusion.  Integer counts in LDS, integer adds of the non-zero cells: exact in any order.  conf
  * and *status are zeroed here. */

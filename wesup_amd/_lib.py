@@ -172,12 +172,19 @@ _SIGS = {
     'wesup_patch_gather_resize': (c_int, 'pp' + 'iiiiiiii' + 'p'),
     'wesup_patch_scatter_u8': (c_int, 'pp' + 'iiiiiiiii' + 'p'),
     'wesup_mask_scores': (c_int, 'ppp' + 'li' + 'p'),
+    # ... over a patch list, and the tissue selection that makes one (csrc/tissue.hip)
+    'wesup_patch_gather_resize_list': (c_int, 'pp' + 'iiiiiiii' + 'pi' + 'p'),
+    'wesup_patch_scatter_u8_list': (c_int, 'pp' + 'iiiiiiiii' + 'pi' + 'p'),
+    'wesup_patch_value_hist': (c_int, 'pp' + 'iiii' + 'p'),
+    'wesup_tissue_select': (c_int, 'p' + 'iiiiii' + 'pppp' + 'p'),
+    'wesup_tissue_mask_u8': (c_int, 'ppp' + 'iii' + 'p'),
     # class maps for more than two classes (csrc/classmap.hip)
     'wesup_window_merge_classes': (c_int, 'ppppp' + 'iiiiiii' + 'p'),
     'wesup_window_merge_classes_views': (c_int, 'ppppp' + 'iiiiiiiii' + 'p'),
     'wesup_planes_resize_acc': (c_int, 'pp' + 'iiiii' + 'fi' + 'p'),
     'wesup_class_argmax_u8': (c_int, 'pp' + 'li' + 'p'),
     'wesup_patch_scatter_classes_u8': (c_int, 'ppp' + 'iiiiiiiii' + 'p'),
+    'wesup_patch_scatter_classes_u8_list': (c_int, 'ppp' + 'iiiiiiiii' + 'pi' + 'p'),
     'wesup_label_confusion': (c_int, 'pppp' + 'li' + 'p'),
     # weak-label preparation (csrc/prepare.hip)
     'wesup_prepare_lds_entries': (c_int, 'i'),
@@ -234,6 +241,9 @@ SELECT_MAX_RANKS = 4     # WESUP_SELECT_MAX_RANKS
 STAIN_BLOCK = 16         # WESUP_STAIN_BLOCK: HE[3][2], pinv[2][3], maxC[2], n_tissue, valid
 SPLIT_SEG, SPLIT_ROWS = 64, 4      # WESUP_SPLIT_SEG, WESUP_SPLIT_ROWS: the distance map's row pass, 4 rows of 64 pixels per block
 SPLIT_TILE, SPLIT_HALO = 32, 8     # WESUP_SPLIT_TILE, WESUP_SPLIT_HALO: the growth kernel's tile edge and halo (rounds per launch)
+TISSUE_MAX_BLOCKS = 2048           # WESUP_TISSUE_MAX_BLOCKS: the histogram kernel's grid, striding over its items
+TISSUE_ITEM_PIXELS = 8192          # WESUP_TISSUE_ITEM_PIXELS: an item is max(1, this // p) rows of one patch
+TISSUE_LIST_CHUNK = 256            # WESUP_TISSUE_LIST_CHUNK: patches per step of the ordered compaction
 ABI_VERSION = 6          # include/wesup_hip.h; a stale libwesup_hip.so with other signatures must not be called
 
 _lib = None

@@ -250,11 +250,13 @@ __global__ __launch_bounds__(CM_BLOCK) void cm_argmax_kernel(const float* __rest
 template <int CMAX, bool VEC4, int MODE>
 __global__ __launch_bounds__(CM_BLOCK) void cm_scatter_kernel(const float* __restrict__ pred, uint8_t* __restrict__ out,
                                                               int32_t* __restrict__ status, int H, int W, int n_w, int last, int p,
-                                                              int h, int w, int C, int first, int count, float sh, float sw) {
+                                                              int h, int w, int C, int first, int count, float sh, float sw,
+                                                              const int32_t* __restrict__ list, int n_list) {
     const long total = (long)count * p * p;
     bool bad = false;
     for (long idx = (long)blockIdx.x * CM_BLOCK + threadIdx.x; idx < total; idx += (long)gridDim.x * CM_BLOCK) {
-        const PatchPixel q = patch_pixel(idx, p, first, n_w, last, H, W);
+        const PatchPixel q = patch_pixel(idx, p, first, n_w, last, H, W, list, n_list);
+        bad = bad || q.bad;                          // (a list value outside the lattice: skipped, told in status)
         if (q.skip) continue;
         int cls = 0;
         if constexpr (MODE == 0) {
@@ -417,8 +419,9 @@ extern "C" int wesup_class_argmax_u8(const float* in, uint8_t* out, long n, int 
     return WESUP_OK;
 }
 
-extern "C" int wesup_patch_scatter_classes_u8(const float* pred, uint8_t* out, int32_t* status, int H, int W, int p, int h, int w,
-                                              int C, int mode, int first, int count, void* stream) {
+// list == NULL: the consecutive patches first .. first + count - 1; otherwise the slots first .. of list[n_list]
+static int cm_scatter(const float* pred, uint8_t* out, int32_t* status, int H, int W, int p, int h, int w, int C, int mode, int first,
+                      int count, const int32_t* list, int n_list, void* stream) {
     int n_w = 0, last = 0;
     if (!pred || !out || !status || h <= 0 || w <= 0 || !cm_range(C) || first < 0 || count < 1 || (mode != 0 && mode != 1) ||
         !sd_lattice(H, W, p, &n_w, &last) || (long)first + count > 0x7fffffffl)
@@ -429,15 +432,28 @@ extern "C" int wesup_patch_scatter_classes_u8(const float* pred, uint8_t* out, i
     const float sh = mode == 0 ? hp_scale(h, p) : ac_scale(h, p), sw = mode == 0 ? hp_scale(w, p) : ac_scale(w, p);
     if (mode == 0) {                                 // (one index per texel: nothing is held per class)
         WESUP_LAUNCH((cm_scatter_kernel<2, false, 0>), grid, block, 0, st, pred, out, status, H, W, n_w, last, p, h, w, C, first,
-                     count, sh, sw);
+                     count, sh, sw, list, n_list);
     } else {
-#define CM_L(CMAX, V) \
-    WESUP_LAUNCH((cm_scatter_kernel<CMAX, V, 1>), grid, block, 0, st, pred, out, status, H, W, n_w, last, p, h, w, C, first, count, sh, sw)
+#define CM_L(CMAX, V)                                                                                                              \
+    WESUP_LAUNCH((cm_scatter_kernel<CMAX, V, 1>), grid, block, 0, st, pred, out, status, H, W, n_w, last, p, h, w, C, first, count, sh, \
+                 sw, list, n_list)
         CM_DISPATCH(C, vec, CM_L);
 #undef CM_L
     }
     WESUP_CHECK_LAUNCH();
     return WESUP_OK;
+}
+
+extern "C" int wesup_patch_scatter_classes_u8(const float* pred, uint8_t* out, int32_t* status, int H, int W, int p, int h, int w,
+                                              int C, int mode, int first, int count, void* stream) {
+    return cm_scatter(pred, out, status, H, W, p, h, w, C, mode, first, count, nullptr, 0, stream);
+}
+
+extern "C" int wesup_patch_scatter_classes_u8_list(const float* pred, uint8_t* out, int32_t* status, int H, int W, int p, int h,
+                                                   int w, int C, int mode, int first, int count, const int32_t* list, int n_list,
+                                                   void* stream) {
+    if (!list || n_list < 1) return WESUP_ERR_INVALID;
+    return cm_scatter(pred, out, status, H, W, p, h, w, C, mode, first, count, list, n_list, stream);
 }
 
 extern "C" int wesup_label_confusion(const uint8_t* S, const uint8_t* G, int64_t* conf, int32_t* status, long n, int C,

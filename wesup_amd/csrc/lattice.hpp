@@ -19,24 +19,34 @@ static inline bool sd_lattice(int H, int W, int p, int* n_w, int* last) {
 
 // Pixel idx of the padded p x p patches first .. first + count - 1 (x fastest, then y, then the patch): n the patch's place in the
 // pass, (y, x) inside the patch, (Y, X) in the slide.  skip: the patch lies past the end of the lattice or the pixel beyond the
-// slide -- never written.
+// slide -- never written.  With a patch list slot first + n names patch list[first + n]: a slot at or beyond
+// n_list is skipped, and so is a list value outside [0, last], which sets bad and never becomes an address.
 struct PatchPixel {
     int n, y, x;
     long Y, X;
-    bool skip;
+    bool skip, bad;
 };
-__device__ __forceinline__ PatchPixel patch_pixel(long idx, int p, int first, int n_w, int last, int H, int W) {
+__device__ __forceinline__ PatchPixel patch_pixel(long idx, int p, int first, int n_w, int last, int H, int W,
+                                                  const int32_t* __restrict__ list = nullptr, int n_list = 0) {
     const long pp = (long)p * p;
     PatchPixel q;
     q.n = (int)(idx / pp);
     const long r = idx - (long)q.n * pp;
     q.y = (int)(r / p);
     q.x = (int)(r - (long)q.y * p);
-    const int k = first + q.n;
+    int k = first + q.n;
+    bool off = false;
+    q.bad = false;
+    if (list) {
+        off = k >= n_list;
+        k = off ? 0 : list[k];
+        q.bad = k < 0 || k > last;
+        if (q.bad) k = 0;
+    }
     const int ky = k / n_w, kx = k - ky * n_w;
     q.Y = (long)ky * p + q.y;
     q.X = (long)kx * p + q.x;
-    q.skip = k > last || q.Y >= H || q.X >= W;
+    q.skip = off || q.bad || k > last || q.Y >= H || q.X >= W;
     return q;
 }
 

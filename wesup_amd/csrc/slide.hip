@@ -5,6 +5,8 @@
 // pass, the scatter resizes a patch's prediction back and pastes it into the slide-size map, the scores kernel counts.  All three
 // are memory movement: no LDS beyond the block reduction of the counts, no workspace, deterministic (integer atomics only).
 // Every offset that involves H * W is a long: a slide may be larger than 2^31 bytes.
+// The gather and the scatter also walk a list of patches instead of consecutive indices (the *_list entries; the list is
+// tissue.hip's): the same kernels with the list as one more argument, null for the plain entries.
 #include "common.hpp"
 #include "bilinear.hpp"
 #include "lattice.hpp"
@@ -16,11 +18,12 @@ namespace {
 
 // out[n][c][y][x] = bilinear(patch_k / 255.f)(y, x), k = min(first + n, last): one thread per output pixel and all three planes,
 // x fastest across lanes (the three plane stores of a wave are 256 contiguous bytes each).  The neighbour indices are clamped
-// at the PATCH border (lerp_of on p texels); a texel beyond the slide border reads as 0 -- pad, then resize.
+// at the PATCH border (lerp_of on p texels); a texel beyond the slide border reads as 0 -- pad, then resize.  With a patch list
+//  k = list[min(first + n, n_list - 1)]; a list value outside [0, last] leaves its slot unwritten.
 template <int AC>
 __global__ __launch_bounds__(SD_BLOCK) void sd_gather_kernel(const uint8_t* __restrict__ img, float* __restrict__ out, int H, int W,
                                                              int n_w, int last, int p, int h, int w, int first, int count,
-                                                             float sh, float sw) {
+                                                             float sh, float sw, const int32_t* __restrict__ list, int n_list) {
     const long plane = (long)h * w;
     const long total = (long)count * plane;
     for (long idx = (long)blockIdx.x * SD_BLOCK + threadIdx.x; idx < total; idx += (long)gridDim.x * SD_BLOCK) {
@@ -28,6 +31,10 @@ __global__ __launch_bounds__(SD_BLOCK) void sd_gather_kernel(const uint8_t* __re
         const long r = idx - (long)n * plane;
         const int y = (int)(r / w), x = (int)(r - (long)y * w);
         int k = first + n;
+        if (list) {
+            k = list[k > n_list - 1 ? n_list - 1 : k];
+            if (k < 0 || k > last) continue;
+        }
         k = k > last ? last : k;
         const int ky = k / n_w, kx = k - ky * n_w;
         const Lerp ly = AC ? lerp_of(y, sh, p) : lerp_half_pixel(y, sh, p);
@@ -56,10 +63,11 @@ __global__ __launch_bounds__(SD_BLOCK) void sd_gather_kernel(const uint8_t* __re
 template <int MODE>
 __global__ __launch_bounds__(SD_BLOCK) void sd_scatter_kernel(const float* __restrict__ pred, uint8_t* __restrict__ out, int H, int W,
                                                               int n_w, int last, int p, int h, int w, int stride, int first,
-                                                              int count, float sh, float sw) {
+                                                              int count, float sh, float sw, const int32_t* __restrict__ list,
+                                                              int n_list) {
     const long total = (long)count * p * p;
     for (long idx = (long)blockIdx.x * SD_BLOCK + threadIdx.x; idx < total; idx += (long)gridDim.x * SD_BLOCK) {
-        const PatchPixel q = patch_pixel(idx, p, first, n_w, last, H, W);
+        const PatchPixel q = patch_pixel(idx, p, first, n_w, last, H, W, list, n_list);
         if (q.skip) continue;
         const float* src = pred + (long)q.n * h * w * stride;
         float v;
@@ -141,8 +149,9 @@ __global__ __launch_bounds__(SD_BLOCK) void sd_scores_kernel(const uint8_t* __re
 
 }  // namespace
 
-extern "C" int wesup_patch_gather_resize(const uint8_t* img, float* out, int H, int W, int p, int h, int w, int align_corners,
-                                         int first, int count, void* stream) {
+// list == NULL: the consecutive patches first .. first + count - 1; otherwise the slots first .. of list[n_list]
+static int sd_gather(const uint8_t* img, float* out, int H, int W, int p, int h, int w, int align_corners, int first, int count,
+                     const int32_t* list, int n_list, void* stream) {
     int n_w = 0, last = 0;
     if (!img || !out || h <= 0 || w <= 0 || first < 0 || count < 1 || (align_corners != 0 && align_corners != 1) ||
         !sd_lattice(H, W, p, &n_w, &last) || (long)first + count > 0x7fffffffl)
@@ -151,17 +160,17 @@ extern "C" int wesup_patch_gather_resize(const uint8_t* img, float* out, int H, 
     const dim3 grid(grid_stride_blocks((long)count * h * w, SD_BLOCK, SD_MAX_BLOCKS)), block(SD_BLOCK);
     if (align_corners) {
         WESUP_LAUNCH(sd_gather_kernel<1>, grid, block, 0, st, img, out, H, W, n_w, last, p, h, w, first, count, ac_scale(p, h),
-                     ac_scale(p, w));
+                     ac_scale(p, w), list, n_list);
     } else {
         WESUP_LAUNCH(sd_gather_kernel<0>, grid, block, 0, st, img, out, H, W, n_w, last, p, h, w, first, count, hp_scale(p, h),
-                     hp_scale(p, w));
+                     hp_scale(p, w), list, n_list);
     }
     WESUP_CHECK_LAUNCH();
     return WESUP_OK;
 }
 
-extern "C" int wesup_patch_scatter_u8(const float* pred, uint8_t* out, int H, int W, int p, int h, int w, int stride, int mode,
-                                      int first, int count, void* stream) {
+static int sd_scatter(const float* pred, uint8_t* out, int H, int W, int p, int h, int w, int stride, int mode, int first, int count,
+                      const int32_t* list, int n_list, void* stream) {
     int n_w = 0, last = 0;
     if (!pred || !out || h <= 0 || w <= 0 || stride < 1 || first < 0 || count < 1 || (mode != 0 && mode != 1) ||
         !sd_lattice(H, W, p, &n_w, &last) || (long)first + count > 0x7fffffffl)
@@ -170,13 +179,35 @@ extern "C" int wesup_patch_scatter_u8(const float* pred, uint8_t* out, int H, in
     const dim3 grid(grid_stride_blocks((long)count * p * p, SD_BLOCK, SD_MAX_BLOCKS)), block(SD_BLOCK);
     if (mode == 0) {
         WESUP_LAUNCH(sd_scatter_kernel<0>, grid, block, 0, st, pred, out, H, W, n_w, last, p, h, w, stride, first, count,
-                     hp_scale(h, p), hp_scale(w, p));
+                     hp_scale(h, p), hp_scale(w, p), list, n_list);
     } else {
         WESUP_LAUNCH(sd_scatter_kernel<1>, grid, block, 0, st, pred, out, H, W, n_w, last, p, h, w, stride, first, count,
-                     ac_scale(h, p), ac_scale(w, p));
+                     ac_scale(h, p), ac_scale(w, p), list, n_list);
     }
     WESUP_CHECK_LAUNCH();
     return WESUP_OK;
+}
+
+extern "C" int wesup_patch_gather_resize(const uint8_t* img, float* out, int H, int W, int p, int h, int w, int align_corners,
+                                         int first, int count, void* stream) {
+    return sd_gather(img, out, H, W, p, h, w, align_corners, first, count, nullptr, 0, stream);
+}
+
+extern "C" int wesup_patch_gather_resize_list(const uint8_t* img, float* out, int H, int W, int p, int h, int w, int align_corners,
+                                              int first, int count, const int32_t* list, int n_list, void* stream) {
+    if (!list || n_list < 1) return WESUP_ERR_INVALID;
+    return sd_gather(img, out, H, W, p, h, w, align_corners, first, count, list, n_list, stream);
+}
+
+extern "C" int wesup_patch_scatter_u8(const float* pred, uint8_t* out, int H, int W, int p, int h, int w, int stride, int mode,
+                                      int first, int count, void* stream) {
+    return sd_scatter(pred, out, H, W, p, h, w, stride, mode, first, count, nullptr, 0, stream);
+}
+
+extern "C" int wesup_patch_scatter_u8_list(const float* pred, uint8_t* out, int H, int W, int p, int h, int w, int stride, int mode,
+                                           int first, int count, const int32_t* list, int n_list, void* stream) {
+    if (!list || n_list < 1) return WESUP_ERR_INVALID;
+    return sd_scatter(pred, out, H, W, p, h, w, stride, mode, first, count, list, n_list, stream);
 }
 
 extern "C" int wesup_mask_scores(const uint8_t* S, const uint8_t* G, int64_t* out4, long n, int negative, void* stream) {

@@ -2041,12 +2041,25 @@ def _patch_lattice(H, W, p, first, count, name):
     return H, W, p, first, count
 
 
-def patch_gather_resize(img_u8_hwc, p, h, w, first, count, align_corners=False, out=None):
+def _patch_list(patch_list, device, name):
+    """The ``(pointer, length)`` tail of a ``*_list`` entry: a non-empty 1-d int32 tensor of patch indices on ``device``
+    (``tissue_select``'s list, cut to its ``n_keep``).  Its values are the kernels' to check: they never become addresses."""
+    _chk(patch_list, torch.int32, 'patch_list')
+    if patch_list.dim() != 1 or patch_list.numel() < 1 or patch_list.device != device:
+        raise _lib.WesupHipError(f'{name}: patch_list {tuple(patch_list.shape)} on {patch_list.device}, expected a non-empty 1-d '
+                                 f'int32 tensor on {device}')
+    return _p(patch_list), patch_list.numel()
+
+
+def patch_gather_resize(img_u8_hwc, p, h, w, first, count, align_corners=False, out=None, patch_list=None):
     """Network inputs for the patches of a slide on the device: img (H,W,3) uint8 -> (count,3,h,w) fp32, the zero-padded
     ``p`` x ``p`` patches ``first .. first + count - 1`` of the ``ceil(H / p)`` x ``ceil(W / p)`` lattice (row-major), each
     ``patch / 255.f`` resized bilinearly to (h, w): ``F.interpolate(mode='bilinear')`` of infer.py, or with ``align_corners`` the
     resize of pixel_infer.py (ops.image_resize_u8 of the patch, bit for bit, where the patch lies inside the slide).  Indices
-    past the last patch repeat it (the padding of a ragged final batch).  ``out``: a buffer reused across passes."""
+    past the last patch repeat it (the padding of a ragged final batch).  ``out``: a buffer reused across passes.
+
+    ``patch_list`` (int32 device tensor): slot ``i`` is patch ``patch_list[min(first + i, len - 1)]`` -- a ragged
+    last pass repeats the last listed patch; a listed patch gets the bits it gets without a list."""
     H, W = _image_u8(img_u8_hwc, 'patch_gather_resize')
     _chk(img_u8_hwc, torch.uint8, 'img')
     H, W, p, first, count = _patch_lattice(H, W, p, first, count, 'patch_gather_resize')
@@ -2054,19 +2067,23 @@ def patch_gather_resize(img_u8_hwc, p, h, w, first, count, align_corners=False, 
     if h < 1 or w < 1:
         raise _lib.WesupHipError(f'patch_gather_resize: target size {h} x {w}')
     out = _out(out, (count, 3, h, w), torch.float32, img_u8_hwc.device, 'patch_gather_resize')
+    tail = () if patch_list is None else _patch_list(patch_list, img_u8_hwc.device, 'patch_gather_resize')
     tok = _tbegin('patch_gather_resize')
-    _lib.call('wesup_patch_gather_resize', _p(img_u8_hwc), _p(out), H, W, p, h, w, int(bool(align_corners)), first, count,
-              _stream())
+    _lib.call('wesup_patch_gather_resize_list' if tail else 'wesup_patch_gather_resize', _p(img_u8_hwc), _p(out), H, W, p, h, w,
+              int(bool(align_corners)), first, count, *tail, _stream())
     _tend(tok, 12.0 * count * h * w)
     return out
 
 
-def patch_scatter_u8(pred, out, p, first, mode=0):
+def patch_scatter_u8(pred, out, p, first, mode=0, patch_list=None):
     """Paste patch predictions into the slide-size map: pred (count,h,w) fp32 -- contiguous, or a view with an element stride
     such as ``probs[..., 1]`` of a (count,h,w,C) prediction, read in place -- for the patches ``first .. first + count - 1``;
     out (H,W) uint8.  Every slide pixel inside those patches becomes ``255 * round(v)`` (half to even), ``v`` the prediction
     resized to ``p`` x ``p``: ``mode`` 0 nearest (infer.py), 1 bilinear with align_corners (pixel_infer.py at one scale).  The
-    rest of ``out`` is left as it is; the lattice's padding beyond the slide is never written."""
+    rest of ``out`` is left as it is; the lattice's padding beyond the slide is never written.
+
+    ``patch_list``: slot ``i`` pastes patch ``patch_list[first + i]``; a slot at or beyond the list's end, or a value outside the
+    lattice, pastes nothing."""
     _chk(out, torch.uint8, 'out')
     if not isinstance(pred, torch.Tensor) or not pred.is_cuda or pred.dtype != torch.float32 or pred.dim() != 3 or out.dim() != 2:
         raise _lib.WesupHipError('patch_scatter_u8: expected (count,h,w) float32 CUDA/HIP predictions and an (H,W) uint8 map')
@@ -2079,9 +2096,87 @@ def patch_scatter_u8(pred, out, p, first, mode=0):
     stride = _plane_stride(pred, 'patch_scatter_u8: pred')
     if pred.device != out.device:
         raise _lib.WesupHipError(f'patch_scatter_u8: pred on {pred.device}, out on {out.device}')
+    tail = () if patch_list is None else _patch_list(patch_list, out.device, 'patch_scatter_u8')
     tok = _tbegin('patch_scatter_u8')
-    _lib.call('wesup_patch_scatter_u8', _p(pred), _p(out), H, W, p, h, w, stride, int(mode), first, count, _stream())
+    _lib.call('wesup_patch_scatter_u8_list' if tail else 'wesup_patch_scatter_u8', _p(pred), _p(out), H, W, p, h, w, stride,
+              int(mode), first, count, *tail, _stream())
     _tend(tok, 4.0 * count * h * w + 1.0 * count * p * p)
+    return out
+
+
+# ---------------------------------------------------------------- tissue selection for whole-slide evaluation (csrc/tissue.hip)
+TISSUE_CHANNELS = ('luma', 'chroma')
+
+
+def _tissue_channel(channel, name):
+    if channel not in TISSUE_CHANNELS:
+        raise _lib.WesupHipError(f'{name}: channel {channel!r}, expected one of {TISSUE_CHANNELS}')
+    return TISSUE_CHANNELS.index(channel)
+
+
+def _tissue_lattice(H, W, p, name):
+    """(H, W, p, n) of the tissue entries: the patch lattice with p <= 65535 (a cell of a histogram is a uint32) and at most
+    2^32 pixels (Otsu's integers stay below 2^64)."""
+    H, W, p, _, _ = _patch_lattice(H, W, p, 0, 1, name)
+    if p > 65535 or H * W > 1 << 32:
+        raise _lib.WesupHipError(f'{name}: patch size {p} for a slide of {H} x {W} (p <= 65535, H * W <= 2^32)')
+    return H, W, p, -(-H // p) * -(-W // p)
+
+
+def patch_value_hist(img_u8_hwc, p, channel='luma', out=None):
+    """Per-patch histograms of a pixel value in one read of the resident slide: img (H,W,3) uint8 -> (n,256) int32 holding
+    uint32 counts (torch has no arithmetic on uint32: read them as ``.cpu().numpy().view(numpy.uint32)``; below 2^31 for
+    p <= 46340), ``hist[k][v]`` = the slide pixels of patch ``k`` of the ``ceil(H / p)`` x ``ceil(W / p)`` lattice whose value is
+    ``v``: ``luma`` (77 R + 150 G + 29 B + 128) >> 8, ``chroma`` max - min (slide.pixel_value).  The zero padding is never
+    counted.  Equal to ``slide.patch_histograms`` exactly."""
+    H, W = _image_u8(img_u8_hwc, 'patch_value_hist')
+    _chk(img_u8_hwc, torch.uint8, 'img')
+    ch = _tissue_channel(channel, 'patch_value_hist')
+    H, W, p, n = _tissue_lattice(H, W, p, 'patch_value_hist')
+    out = _out(out, (n, 256), torch.int32, img_u8_hwc.device, 'patch_value_hist')
+    tok = _tbegin('patch_value_hist')
+    _lib.call('wesup_patch_value_hist', _p(img_u8_hwc), _p(out), H, W, p, ch, _stream())
+    _tend(tok, 3.0 * H * W + 1024.0 * n)
+    return out
+
+
+def tissue_select(hist, H, W, p, channel='luma', threshold=-1, min_ppm=10000):
+    """The rest of the selection from ``patch_value_hist``'s histograms, without a read-back: returns the device tensors
+    ``(info, total, counts, list)``.  ``total`` (256,) int64 the summed histogram; ``t`` = ``threshold`` (0 .. 254), or Otsu's
+    over ``total`` with ``threshold=-1`` (slide.otsu_threshold: -1 for a one-level slide); ``counts`` (n,) int32 (uint32 bits)
+    the tissue pixels per patch; ``list`` (n,) int32 with the kept patches in ascending order in its first ``n_keep`` places
+    (slide.select_patches; the rest is not written); ``info`` (8,) int32 = ``{t, n_keep, n, flat, 0, 0, 0, 0}``."""
+    _chk(hist, torch.int32, 'hist')
+    ch = _tissue_channel(channel, 'tissue_select')
+    H, W, p, n = _tissue_lattice(H, W, p, 'tissue_select')
+    threshold, min_ppm = int(threshold), int(min_ppm)
+    if tuple(hist.shape) != (n, 256):
+        raise _lib.WesupHipError(f'tissue_select: hist {tuple(hist.shape)}, expected {(n, 256)}')
+    if not -1 <= threshold <= 254 or not 0 <= min_ppm <= 1000000:
+        raise _lib.WesupHipError(f'tissue_select: threshold {threshold} (-1 .. 254), min_ppm {min_ppm} (0 .. 10^6)')
+    dev = hist.device
+    info = torch.empty(8, dtype=torch.int32, device=dev)
+    total = torch.empty(256, dtype=torch.int64, device=dev)
+    counts = torch.empty(n, dtype=torch.int32, device=dev)
+    plist = torch.empty(n, dtype=torch.int32, device=dev)
+    tok = _tbegin('tissue_select')
+    _lib.call('wesup_tissue_select', _p(hist), H, W, p, ch, threshold, min_ppm, _p(info), _p(total), _p(counts), _p(plist), _stream())
+    _tend(tok, 2.0 * 1024.0 * n + 12.0 * n)
+    return info, total, counts, plist
+
+
+def tissue_mask(img_u8_hwc, info, channel='luma', out=None):
+    """The tissue mask of a slide under ``tissue_select``'s threshold, read from ``info`` on the device: (H,W) uint8, 255 where
+    the pixel is tissue (``luma`` v <= t, ``chroma`` v > t, t = -1 everywhere), 0 elsewhere."""
+    H, W = _image_u8(img_u8_hwc, 'tissue_mask')
+    _chk(img_u8_hwc, torch.uint8, 'img'); _chk(info, torch.int32, 'info')
+    ch = _tissue_channel(channel, 'tissue_mask')
+    if info.numel() != 8 or info.device != img_u8_hwc.device or H < 1 or W < 1 or max(H, W) > 1 << 30:
+        raise _lib.WesupHipError(f'tissue_mask: info {tuple(info.shape)} on {info.device} for a slide of {H} x {W}')
+    out = _out(out, (H, W), torch.uint8, img_u8_hwc.device, 'tissue_mask')
+    tok = _tbegin('tissue_mask')
+    _lib.call('wesup_tissue_mask_u8', _p(img_u8_hwc), _p(info), _p(out), H, W, ch, _stream())
+    _tend(tok, 4.0 * H * W)
     return out
 
 
@@ -2203,13 +2298,14 @@ def class_argmax_u8(src, out=None):
     return out
 
 
-def patch_scatter_classes_u8(pred, out, p, first, n_classes=None, mode=0, status=None):
+def patch_scatter_classes_u8(pred, out, p, first, n_classes=None, mode=0, status=None, patch_list=None):
     """``patch_scatter_u8`` for class maps: pastes a class index per slide pixel of the patches ``first .. first + count - 1`` into
     out (H,W) uint8 -- the same lattice, the same crop, the rest of ``out`` left as it is.  ``mode`` 0: pred (count,h,w) fp32
     class indices (the superpixel model's painted map) and ``n_classes``, nearest resize; an index outside [0, C) pastes 0 and
     sets ``status``.  ``mode`` 1: pred (count,h,w,C) fp32 probabilities; per class the bilinear align_corners value of
     ``planes_resize_acc(alpha=1)``, then the first maximum.  ``status`` (1,) int32 is OR-ed into, so that one word serves all the
-    passes of a slide; a new zeroed one is made when none is given.  Returns (out, status)."""
+    passes of a slide; a new zeroed one is made when none is given.  Returns (out, status).  ``patch_list``: as in
+    ``patch_scatter_u8``; a list value outside the lattice sets ``status`` too."""
     _chk(out, torch.uint8, 'out'); _chk(pred, name='pred')
     if mode not in (0, 1):
         raise _lib.WesupHipError(f'patch_scatter_classes_u8: mode {mode}')
@@ -2222,9 +2318,10 @@ def patch_scatter_classes_u8(pred, out, p, first, n_classes=None, mode=0, status
     if h < 1 or w < 1:
         raise _lib.WesupHipError(f'patch_scatter_classes_u8: pred {tuple(pred.shape)}')
     status = _status(status, out.device, 'patch_scatter_classes_u8')
+    tail = () if patch_list is None else _patch_list(patch_list, out.device, 'patch_scatter_classes_u8')
     tok = _tbegin('patch_scatter_classes_u8')
-    _lib.call('wesup_patch_scatter_classes_u8', _p(pred), _p(out), _p(status), H, W, p, h, w, C, int(mode), first, count,
-              _stream())
+    _lib.call('wesup_patch_scatter_classes_u8_list' if tail else 'wesup_patch_scatter_classes_u8', _p(pred), _p(out), _p(status),
+              H, W, p, h, w, C, int(mode), first, count, *tail, _stream())
     _tend(tok, 4.0 * count * h * w * (C if mode else 1) + 1.0 * count * p * p)
     return out, status
 
