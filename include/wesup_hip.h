@@ -606,7 +606,8 @@ int wesup_window_merge(const float* pred, const int32_t* tops, const int32_t* le
 /* Test-time augmentation over the views of a square window (infer_tile.apply_view / invert_view): view
  * v = r + 4 f, a left-right mirror first when f, then r counter-clockwise quarter turns.  A view list comes by value: n_views
  * and `views`, four bits per view, the first view in the lowest bits.  WESUP_ERR_INVALID without a launch for n_views outside
- * 1 .. 8, an index above 7 or a repeated index, and for what the entries above refuse.
+ * 1 .. 8, an index above 7 or a repeated index, and for what the entries above refuse.  The entries above (and
+ * wesup_window_merge_classes below) are these with n_views = 1, views = 0: one kernel and one set of checks per pair.
  *
  * wesup_window_gather_views: wesup_window_gather over the slots of windows x views -- slot s = first + n is window s / n_views
  * under view views[s % n_views], a slot past the last repeats the last; out[n] is _to_tensor(apply_view(window, v)) bit for bit. */

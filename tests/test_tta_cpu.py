@@ -316,24 +316,31 @@ def test_wrappers_check_their_arguments_and_have_no_cpu_fallback(lib):
     tops, lefts = T.window_grid(80, 112, 64)
     img = torch.zeros(80, 112, 3, dtype=torch.uint8)
     with pytest.raises(lib.WesupHipError, match='no CPU fallback'):
-        ops.window_gather_views(img, tops, lefts, 64, (0, 4), 0, 4)
+        ops.window_gather(img, tops, lefts, 64, 0, 4, views=(0, 4))
     with pytest.raises(lib.WesupHipError, match='no CPU fallback'):
-        ops.window_merge_views(torch.zeros(4, 2, 64, 64, 1), (0, 4), tops, lefts, 80, 112)
+        ops.window_merge(torch.zeros(4, 2, 64, 64, 1), tops, lefts, 80, 112, views=(0, 4))
     with pytest.raises(lib.WesupHipError, match='no CPU fallback'):
-        ops.window_merge_classes_views(torch.zeros(4, 2, 64, 64, 3), (0, 4), tops, lefts, 80, 112)
+        ops.window_merge_classes(torch.zeros(4, 2, 64, 64, 3), tops, lefts, 80, 112, views=(0, 4))
     with pytest.raises(lib.WesupHipError, match='views'):
-        ops.window_gather_views(img, tops, lefts, 64, (0, 0), 0, 4)
+        ops.window_gather(img, tops, lefts, 64, 0, 4, views=(0, 0))
     with pytest.raises(lib.WesupHipError, match='slots'):
-        ops.window_gather_views(img, tops, lefts, 64, (0, 4), 0, 0)
+        ops.window_gather(img, tops, lefts, 64, 0, 0, views=(0, 4))
+    with pytest.raises(lib.WesupHipError, match='for 2 views'):
+        ops.window_merge(torch.zeros(4, 3, 64, 64, 1), tops, lefts, 80, 112, views=(0, 4))
+    with pytest.raises(lib.WesupHipError, match='windows for a lattice'):
+        ops.window_merge(torch.zeros(3, 2, 64, 64), tops, lefts, 80, 112, views=(0, 4))
+    with pytest.raises(lib.WesupHipError, match='not sorted'):
+        ops.window_merge_classes(torch.zeros(4, 2, 64, 64, 3), [16, 0], lefts, 80, 112, views=(0, 4))
+    with pytest.raises(lib.WesupHipError, match='n_classes'):
+        ops.window_merge_classes(torch.zeros(4, 2, 64, 64), tops, lefts, 80, 112, votes=True, views=(0, 4))
+    with pytest.raises(lib.WesupHipError, match='for 2 views'):
+        ops.window_merge_classes(torch.zeros(4, 8, 64, 64), tops, lefts, 80, 112, n_classes=3, votes=True, views=(0, 4))
+    with pytest.raises(lib.WesupHipError):
+        ops.window_merge_classes(torch.zeros(4, 2, 64, 64, 3), tops, lefts, 80, 112, votes=True, views=(0, 4))
+    # the earlier positional spelling is forwarded to the keyword form: the same checks
+    with pytest.raises(lib.WesupHipError, match='no CPU fallback'):
+        ops.window_gather_views(img, tops, lefts, 64, (0, 4), 0, 4)
     with pytest.raises(lib.WesupHipError, match='for 2 views'):
         ops.window_merge_views(torch.zeros(4, 3, 64, 64, 1), (0, 4), tops, lefts, 80, 112)
-    with pytest.raises(lib.WesupHipError, match='windows for a lattice'):
-        ops.window_merge_views(torch.zeros(3, 2, 64, 64), (0, 4), tops, lefts, 80, 112)
-    with pytest.raises(lib.WesupHipError, match='not sorted'):
-        ops.window_merge_classes_views(torch.zeros(4, 2, 64, 64, 3), (0, 4), [16, 0], lefts, 80, 112)
     with pytest.raises(lib.WesupHipError, match='n_classes'):
         ops.window_merge_classes_views(torch.zeros(4, 2, 64, 64), (0, 4), tops, lefts, 80, 112, votes=True)
-    with pytest.raises(lib.WesupHipError, match='for 2 views'):
-        ops.window_merge_classes_views(torch.zeros(4, 8, 64, 64), (0, 4), tops, lefts, 80, 112, n_classes=3, votes=True)
-    with pytest.raises(lib.WesupHipError):
-        ops.window_merge_classes_views(torch.zeros(4, 2, 64, 64, 3), (0, 4), tops, lefts, 80, 112, votes=True)

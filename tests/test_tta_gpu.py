@@ -1,10 +1,10 @@
 """Test-time augmentation over the eight views of a window on the device (csrc/tiles.hip, csrc/classmap.hip,
 csrc/lattice.hpp, infer_tile.py).
 
-Kernels.  The host functions of ``infer_tile`` are the specification and every comparison is bit for bit: ``window_gather_views``
-against ``_to_tensor(apply_view(window, v))`` slot by slot, ``window_merge_views`` against ``combine_views_to_image``,
-``window_merge_classes_views`` against ``combine_views_to_classes``; under the one upright view each equals its sibling without
-views.  A round trip without a model -- the device-resident walk under all eight views with a pointwise ``forward``, merged
+Kernels.  The host functions of ``infer_tile`` are the specification and every comparison is bit for bit: ``window_gather`` under
+``views=`` against ``_to_tensor(apply_view(window, v))`` slot by slot, ``window_merge`` against ``combine_views_to_image``,
+``window_merge_classes`` against ``combine_views_to_classes``; under the one upright view each equals the plain entry, the call
+without views.  A round trip without a model -- the device-resident walk under all eight views with a pointwise ``forward``, merged
 through the inverse index -- equals the walk without views: a forward / inverse mismatch of the index functions shows there.
 
 End to end.  The models, weights and image of tests/test_tiles_gpu.py (two classes) and tests/test_classmaps_gpu.py (three
@@ -59,7 +59,7 @@ def test_window_gather_views_equals_to_tensor_of_the_views(H, W, p, views):     
     V, S = len(views), N * len(views)
     want = _view_slots(img, p, views)
     img_d = _d(img)
-    got = ops.window_gather_views(img_d, tops, lefts, p, views, 0, S)
+    got = ops.window_gather(img_d, tops, lefts, p, 0, S, views=views)
     assert got.shape == (S, 3, p, p) and got.dtype == torch.float32
     assert torch.equal(got, want)
     if V > 1:                                                          # the views differ: a view ignored would show
@@ -68,12 +68,12 @@ def test_window_gather_views_equals_to_tensor_of_the_views(H, W, p, views):     
     first = max(S - V - 1, 0) if N > 1 else S // 2
     assert V == 1 or first % V != 0
     out = torch.full((S - first + 3, 3, p, p), float('nan'), device=DEV)
-    tail = ops.window_gather_views(img_d, tops, lefts, p, views, first, S - first + 3, out=out)
+    tail = ops.window_gather(img_d, tops, lefts, p, first, S - first + 3, out=out, views=views)
     assert tail is out
     for i in range(S - first + 3):
         assert torch.equal(tail[i], want[min(first + i, S - 1)]), i
     # the upright view alone is window_gather
-    assert torch.equal(ops.window_gather_views(img_d, tops, lefts, p, (0,), 0, N + 1), ops.window_gather(img_d, tops, lefts, p, 0, N + 1))
+    assert torch.equal(ops.window_gather(img_d, tops, lefts, p, 0, N + 1, views=(0,)), ops.window_gather(img_d, tops, lefts, p, 0, N + 1))
 
 
 def test_window_gather_views_where_the_grid_stride_loop_wraps():
@@ -86,7 +86,7 @@ def test_window_gather_views_where_the_grid_stride_loop_wraps():
     tops, lefts, N = _lattice(H, W, p)
     S = N * 8
     assert S * p * (p // 4) > 4096 * 256
-    got = ops.window_gather_views(_d(img), tops, lefts, p, D4, 0, S)
+    got = ops.window_gather(_d(img), tops, lefts, p, 0, S, views=D4)
     assert torch.equal(got, _view_slots(img, p, D4))
 
 
@@ -113,14 +113,14 @@ def test_window_merge_views_equals_the_host_merge(H, W, p, C):
         for round_first in (False, True):
             host = T.combine_views_to_image(np.round(pred) if round_first else pred, views, H, W).reshape(H, W, C)
             out = torch.full((H, W, C), float('nan'), dtype=torch.float64, device=DEV)
-            got = ops.window_merge_views(pred_d, views, tops, lefts, H, W, round_first=round_first, out=out)
+            got = ops.window_merge(pred_d, tops, lefts, H, W, round_first=round_first, out=out, views=views)
             assert got is out and np.array_equal(got.cpu().numpy(), host), (views, round_first)
         if views == (0,):                                              # the upright view alone is window_merge
-            assert torch.equal(ops.window_merge_views(pred_d, views, tops, lefts, H, W), ops.window_merge(pred_d[:, 0], tops, lefts, H, W))
+            assert torch.equal(ops.window_merge(pred_d, tops, lefts, H, W, views=views), ops.window_merge(pred_d[:, 0], tops, lefts, H, W))
         elif views == (5, 2):                                          # and the list is not ignored
             assert not np.array_equal(T.combine_views_to_image(pred, (2, 5), H, W).reshape(H, W, C), host)
         if C == 1:                                                     # the (N,V,p,p) form
-            got = ops.window_merge_views(pred_d[..., 0].contiguous(), views, tops, lefts, H, W)
+            got = ops.window_merge(pred_d[..., 0].contiguous(), tops, lefts, H, W, views=views)
             assert got.shape == (H, W) and np.array_equal(got.cpu().numpy(), T.combine_views_to_image(pred[..., 0], views, H, W))
 
 
@@ -130,7 +130,7 @@ def test_window_merge_views_adds_in_the_order_of_the_definition():
     from wesup_amd import ops
     for pred, views, H, W, at, want, other in order_cases():
         tops, lefts, N = _lattice(H, W, pred.shape[2])
-        got = ops.window_merge_views(_d(pred), views, tops, lefts, H, W).cpu().numpy()
+        got = ops.window_merge(_d(pred), tops, lefts, H, W, views=views).cpu().numpy()
         assert got[at] == want and got[at] != other, (views, got[at])
         assert np.array_equal(got, T.combine_views_to_image(pred, views, H, W))
 
@@ -192,7 +192,7 @@ def test_window_merge_classes_views_equals_the_host_function(H, W, p, C, votes):
         want = T.combine_views_to_classes(pred, views, H, W, C, votes=votes)
         out.fill_(SENTINEL)
         status.fill_(5)
-        got, st = ops.window_merge_classes_views(_d(pred), views, tops, lefts, H, W, n_classes=C, votes=votes, out=out, status=status)
+        got, st = ops.window_merge_classes(_d(pred), tops, lefts, H, W, n_classes=C, votes=votes, out=out, status=status, views=views)
         assert got is out and st is status and int(status) == 0
         assert np.array_equal(got.cpu().numpy(), want), (views, int((got.cpu().numpy() != want).sum()))
         assert len(np.unique(want)) == C, views                                # every class is somewhere
@@ -209,10 +209,35 @@ def test_window_merge_classes_views_equals_the_host_function(H, W, p, C, votes):
             bad = pred.copy()
             bad[0, 0, 0, 0], bad[0, V - 1, 1, 1], bad[N - 1, V - 1, p - 1, p - 1] = -1.0, float(C), np.nan
             want = T.combine_views_to_classes(bad, views, H, W, C, votes=True)
-            got, st = ops.window_merge_classes_views(_d(bad), views, tops, lefts, H, W, n_classes=C, votes=True, out=out, status=status)
+            got, st = ops.window_merge_classes(_d(bad), tops, lefts, H, W, n_classes=C, votes=True, out=out, status=status, views=views)
             assert int(st) != 0 and np.array_equal(got.cpu().numpy(), want), views
             if N == 1 and V == 1:
                 assert want[0, 0] == 0 and want[1, 1] == 0 and want[H - 1, W - 1] == 0      # nobody voted there
+
+
+WRAP = (1100, 1000, 550, (5, 2))         # 2 x 2 windows that overlap along x; 1 100 000 pixels, more than the merges' 4096 x 256 threads
+
+
+@pytest.mark.parametrize('what', ['mean', 'votes', 'probabilities'])
+def test_merges_under_views_where_the_grid_stride_loop_wraps(what):
+    """Every other size here fits the grid once; the end-to-end cases wrap it, but without views."""
+    from wesup_amd import infer_tile as T
+    from wesup_amd import ops
+    H, W, p, views = WRAP
+    tops, lefts, N = _lattice(H, W, p)
+    assert N == 4 and list(lefts) == [0, 450] and H * W > 4096 * 256
+    rs = np.random.RandomState(len(what))
+    if what == 'mean':
+        pred = _planted(rs, (N, 2, p, p, 1))
+        got = ops.window_merge(_d(pred), tops, lefts, H, W, views=views)
+        want = T.combine_views_to_image(pred, views, H, W).reshape(H, W, 1)
+    else:
+        votes = what == 'votes'
+        pred = _view_votes(rs, H, W, p, 3, views) if votes else _view_probabilities(rs, N, 2, p, 3)
+        got, status = ops.window_merge_classes(_d(pred), tops, lefts, H, W, n_classes=3, votes=votes, views=views)
+        assert int(status) == 0
+        want = T.combine_views_to_classes(pred, views, H, W, 3, votes=votes)
+    assert np.array_equal(got.cpu().numpy(), want)
 
 
 # ---------------------------------------------------------------------------------------- 4. round trip without a model
@@ -235,7 +260,7 @@ def test_round_trip_through_the_walk_equals_the_walk_without_views(H, W, p, batc
         assert kept_v.shape == (N, len(views), p, p, 1) and (h, w) == (H, W)
         assert list(tops_v) == list(tops) and list(lefts_v) == list(lefts)
         if views == D4:
-            turned = ops.window_merge_views(kept_v, views, tops, lefts, H, W)
+            turned = ops.window_merge(kept_v, tops, lefts, H, W, views=views)
             assert torch.equal(turned, plain)
             assert p == 1 or not torch.equal(kept_v[:, 1], kept_v[:, 0])       # (the views were really made)
         # ... and every kept slot is its view of the window's plain prediction (any list, any batch: the slot arithmetic)
@@ -383,11 +408,11 @@ def test_three_class_pixel_forms_under_views(pixel3, image, tta, monkeypatch):
     single = T.pixel_predict_array_classes(pixel3, image, P_, device=DEV, views=views)
     assert single.shape == (H_, W_) and single.dtype == np.uint8
     CM._assert_not_vacuous(name, single)
-    seen = _recorded(monkeypatch, 'window_merge_classes_views')
+    seen = _recorded(monkeypatch, 'window_merge_classes')
     one = T.pixel_predict_array_classes_batched(pixel3, image, P_, batch=1, device=DEV, views=views)
     assert np.array_equal(one, single) and len(seen) == 1 and seen[0].shape == (18, len(views), P_, P_, 3)
     tops, lefts, N = _lattice(H_, W_, P_)
-    merged = ops.window_merge_views(seen[0], views, tops, lefts, H_, W_).cpu().numpy()      # the means behind the batch-1 map
+    merged = ops.window_merge(seen[0], tops, lefts, H_, W_, views=views).cpu().numpy()      # the means behind the batch-1 map
     assert np.array_equal(single, merged.argmax(axis=-1))
     amb = CM._top_two_gap(merged) < AMBIGUOUS
     _few_ambiguous(name, amb)

@@ -3,11 +3,11 @@ do with torch, and beside the forward pass they stand around.  No speed was fixe
 the entries without views and ``torch.rot90`` / ``torch.flip`` copies, at 1000 x 1400, p = 464 (12 windows) under all eight views:
 
   (a) gather: ops.window_gather of the 12 windows, then per view one torch flip / rot90 copy into the (12, 8, 3, p, p) input, against
-      ops.window_gather_views of the 96 slots;
+      ops.window_gather(views=...) of the 96 slots;
   (b) merge, C = 1 and C = 3: per view one inverse torch rot90 / flip copy into an upright (12, p, p, 8 C) buffer, ops.window_merge
-      over it and the mean over the views, against ops.window_merge_views (the composition adds in another order: equal to rounding,
+      over it and the mean over the views, against ops.window_merge(views=...) (the composition adds in another order: equal to rounding,
       not bit for bit);
-  (c) class merge, C = 3 probabilities: (b)'s composition followed by torch.argmax, against ops.window_merge_classes_views;
+  (c) class merge, C = 3 probabilities: (b)'s composition followed by torch.argmax, against ops.window_merge_classes(views=...);
   (d) one view at a time: the gather and the merge of all 12 windows under the single view 0, 4 (mirror), 2 (half turn), 1 and 3
       (odd quarter turns: a wave's source reads are one image row, resp. one window row, apart);
   (e) one forward pass of the superpixel model at batch 4, p = 464 (GPU SLIC, the network, the painted map), next to one gather
@@ -89,7 +89,7 @@ def gather_case(views=D4, old=True):
 
     def new(i):
         s = sets[i]
-        ops.window_gather_views(s['img'], tops, lefts, P, views, 0, N * V, out=s['x'])
+        ops.window_gather(s['img'], tops, lefts, P, 0, N * V, out=s['x'], views=views)
 
     def check():
         composed(0); new(0)
@@ -97,7 +97,7 @@ def gather_case(views=D4, old=True):
     win = 3.0 * N * P * P                                           # the bytes of the windows, read once
     name = f'views {views}' if V < 8 else 'all eight views'
     cfgs = [dict(name=f'(a) window_gather + {V} torch view copies', run=composed, bytes=win + 4 * win * (1 + 2 * V)),
-            dict(name=f'(a) window_gather_views, {name}', run=new, bytes=win * V + 4 * win * V)]
+            dict(name=f'(a) window_gather(views), {name}', run=new, bytes=win * V + 4 * win * V)]
     return (cfgs if old else cfgs[1:]), ring, (check if old else None)
 
 
@@ -126,9 +126,9 @@ def merge_case(C, classes=False, views=D4, old=True):
     def new(i):
         s = sets[i]
         if classes:
-            ops.window_merge_classes_views(s['pred'], views, tops, lefts, H, W, out=s['u8'], status=s['st'])
+            ops.window_merge_classes(s['pred'], tops, lefts, H, W, out=s['u8'], status=s['st'], views=views)
         else:
-            ops.window_merge_views(s['pred'], views, tops, lefts, H, W, out=s['f64_new'])
+            ops.window_merge(s['pred'], tops, lefts, H, W, out=s['f64_new'], views=views)
 
     def check():
         composed(0); new(0)
@@ -139,14 +139,14 @@ def merge_case(C, classes=False, views=D4, old=True):
             assert differ <= H * W // 10000
         else:
             err = float((s['f64'] - s['f64_new']).abs().max())
-            say(f'    (b) C={C}: max |composition - window_merge_views| = {err:.2e} (another order of the sum)')
+            say(f'    (b) C={C}: max |composition - window_merge(views)| = {err:.2e} (another order of the sum)')
             assert err < 1e-12
     tag = '(c)' if classes else '(b)'
     name = f'views {views}' if V < 8 else 'all eight views'
     tail_old = 8.0 * H * W if classes else 0.0
     cfgs = [dict(name=f'{tag} C={C}  {V} inverse copies + window_merge + mean' + (' + argmax' if classes else ''), run=composed,
                  bytes=3.0 * pred_b + 2.0 * V * f64 + (2.0 if classes else 1.0) * f64 + tail_old),
-            dict(name=f'{tag} C={C}  window_merge{"_classes" if classes else ""}_views, {name}', run=new,
+            dict(name=f'{tag} C={C}  window_merge{"_classes" if classes else ""}(views), {name}', run=new,
                  bytes=1.0 * pred_b + (1.0 * H * W if classes else 1.0 * f64))]
     return (cfgs if old else cfgs[1:]), ring, (check if old else None)
 
@@ -223,7 +223,7 @@ def forward():
 
 
 def gather_pass(k):
-    ops.window_gather_views(img_d, tops, lefts, P, D4, passes[k % len(passes)][0], B, out=x)
+    ops.window_gather(img_d, tops, lefts, P, passes[k % len(passes)][0], B, out=x, views=D4)
 
 
 gather_pass(1)                                       # (slots 4 .. 7: the views 4 .. 7 of window 0)
@@ -243,9 +243,9 @@ for rep in range(a.reps):
 fwd_us, gat_us = float(np.median(fwd)), float(np.median(gat))
 merge_share = d4_us['merge C=1'] * B / (N * 8)
 say(f'    forward pass, batch {B}:                         median {fwd_us:10.1f} us (min {min(fwd):.1f}, max {max(fwd):.1f})')
-say(f'    window_gather_views, one pass of {B} slots:      median {gat_us:10.1f} us (min {min(gat):.1f}, max {max(gat):.1f}; all 24 passes '
+say(f'    window_gather(views), one pass of {B} slots:     median {gat_us:10.1f} us (min {min(gat):.1f}, max {max(gat):.1f}; all 24 passes '
     f'of the 96 slots in turn, every view among them)')
-say(f'    window_merge_views C=1, the share of {B} slots:  {merge_share:10.1f} us ({d4_us["merge C=1"]:.1f} us once per image / 24 passes)')
+say(f'    window_merge(views) C=1, the share of {B} slots: {merge_share:10.1f} us ({d4_us["merge C=1"]:.1f} us once per image / 24 passes)')
 say(f'    gather + merge share over the forward pass: {(gat_us + merge_share) / fwd_us:.4f}')
 if a.out:
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)

@@ -161,7 +161,7 @@ _SIGS = {
     # window inference on large images (csrc/tiles.hip)
     'wesup_window_gather': (c_int, 'pppp' + 'iiiiiii' + 'p'),
     'wesup_window_merge': (c_int, 'pppp' + 'iiiiiii' + 'p'),
-    # ... over windows x views: n_views and the view word, four bits per view
+    # ... over windows x views: n_views and the view word, four bits per view; the two above are these at 1, 0
     'wesup_window_gather_views': (c_int, 'pppp' + 'iiiiiiiii' + 'p'),
     'wesup_window_merge_views': (c_int, 'pppp' + 'iiiiiiiii' + 'p'),
     # whole-image multi-scale pixel inference (csrc/pixel.hip)

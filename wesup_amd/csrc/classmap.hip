@@ -69,74 +69,22 @@ __device__ __forceinline__ Corners corners_of(const float* in, const Lerp ly, co
             in + ((long)ly.i1 * w + lx.i1) * C};
 }
 
-// ---- 1. merge: out[y][x] = first maximum over c of the mean over the covering windows.  One thread per PIXEL: the covering
-// windows are found once (covering, lattice.hpp: tl_merge_kernel's search), a window's C values are one contiguous run, and the
-// (H, W, C) fp64 tensor is never formed.  VOTES = 0: pred [N][p][p][C] probabilities; per class tl_merge_kernel's arithmetic --
-// ascending row-major adds onto 0.0 in fp64, one IEEE division by the count -- then the argmax of the quotients (two sums may round
-// to one quotient: the division is not skipped).  VOTES = 1: pred [N][p][p] class indices as floats; integer counts per class (a
-// vote is compared with every c, it never indexes), the first maximum of the counts.
-template <int CMAX, bool VEC4, bool VOTES>
+// ---- 1. merge: out[y][x] = first maximum over c of the mean over the covering windows and their views (the plain
+// entry is the one-view case V = 1, views = 0, and UPRIGHT is that case at compile time, as in tiles.hip).  One thread per PIXEL:
+// the covering windows are found once (covering, lattice.hpp: tl_merge_kernel's search), every covering window (ascending,
+// row-major) contributes its V views in list order, each read through view_inverse (lattice.hpp) at an offset tested to lie in
+// [0, p); the C values of a window pixel are one contiguous run, and the (H, W, C) fp64 tensor is never formed.  VOTES = 0: pred
+// [N][V][p][p][C] probabilities in VIEW space; per class tl_merge_kernel's arithmetic -- adds onto 0.0 in fp64, one IEEE division
+// by the number of values, covering windows x V -- then the argmax of the quotients (two sums may round to one quotient: the
+// division is not skipped).  VOTES = 1: pred [N][V][p][p] class indices as floats; integer counts per class (a vote is compared
+// with every c, it never indexes), the first maximum of the counts.  infer_tile.combine_views_to_classes
+// (combine_patches_to_classes for one upright view) bit for bit.
+template <int CMAX, bool VEC4, bool VOTES, bool UPRIGHT>
 __global__ __launch_bounds__(CM_BLOCK) void cm_merge_kernel(const float* __restrict__ pred, const int32_t* __restrict__ tops,
                                                             const int32_t* __restrict__ lefts, uint8_t* __restrict__ out,
                                                             int32_t* __restrict__ status, int H, int W, int C, int n_h, int n_w,
-                                                            int p) {
-    const long total = (long)H * W;
-    for (long idx = (long)blockIdx.x * CM_BLOCK + threadIdx.x; idx < total; idx += (long)gridDim.x * CM_BLOCK) {
-        const int y = (int)(idx / W), x = (int)(idx - (long)y * W);
-        const Covering rows = covering(tops, n_h, y, p), cols = covering(lefts, n_w, x, p);
-        double acc[CMAX];
-        int votes[CMAX];
-#pragma unroll
-        for (int c = 0; c < CMAX; ++c) {
-            acc[c] = 0.0;
-            votes[c] = 0;
-        }
-        int cnt = 0;
-        bool bad = false;
-        for (int i = rows.i0; i < rows.i1; ++i) {
-            const int dy = y - tops[i];
-            if (dy < 0 || dy >= p) continue;         // (an unsorted lattice: never an address outside the window)
-            for (int j = cols.i0; j < cols.i1; ++j) {
-                const int dx = x - lefts[j];
-                if (dx < 0 || dx >= p) continue;
-                const long at = ((long)(i * n_w + j) * p + dy) * p + dx;
-                if constexpr (VOTES) {
-                    const float v = rintf(pred[at]);
-                    if (v >= 0.f && v < (float)C) {
-#pragma unroll
-                        for (int c = 0; c < CMAX; ++c)
-                            if (c < C) votes[c] += (v == (float)c) ? 1 : 0;
-                    } else bad = true;               // (a NaN lands here too)
-                } else {
-                    load_classes<CMAX, VEC4>(pred + at * C, C, [&](int c, float v) { acc[c] += (double)v; });
-                }
-                ++cnt;
-            }
-        }
-        int cls;
-        if constexpr (VOTES) {
-            cls = first_max<CMAX>(votes, C);
-            if (bad) atomicOr(status, 1);
-        } else {
-            const double n = (double)cnt;
-#pragma unroll
-            for (int c = 0; c < CMAX; ++c)
-                if (c < C) acc[c] = acc[c] / n;
-            cls = first_max<CMAX>(acc, C);
-        }
-        out[idx] = (uint8_t)cls;
-    }
-}
-
-// ---- 1v. cm_merge_kernel over windows x views: pred [N][V][p][p][C] or [N][V][p][p] in VIEW space.  The same
-// search, tests, registers and first maximum; every covering window (ascending) contributes its V views in list order, each read
-// through view_inverse (lattice.hpp) at an offset tested to lie in [0, p).  The divisor is the number of values, covering
-// windows x V: infer_tile.combine_views_to_classes bit for bit.
-template <int CMAX, bool VEC4, bool VOTES>
-__global__ __launch_bounds__(CM_BLOCK) void cm_merge_views_kernel(const float* __restrict__ pred, const int32_t* __restrict__ tops,
-                                                                  const int32_t* __restrict__ lefts, uint8_t* __restrict__ out,
-                                                                  int32_t* __restrict__ status, int H, int W, int C, int n_h,
-                                                                  int n_w, int p, int V, uint32_t views) {
+                                                            int p, int n_views, uint32_t views) {
+    const int V = UPRIGHT ? 1 : n_views;
     const long total = (long)H * W;
     for (long idx = (long)blockIdx.x * CM_BLOCK + threadIdx.x; idx < total; idx += (long)gridDim.x * CM_BLOCK) {
         const int y = (int)(idx / W), x = (int)(idx - (long)y * W);
@@ -158,7 +106,7 @@ __global__ __launch_bounds__(CM_BLOCK) void cm_merge_views_kernel(const float* _
                 if (dx < 0 || dx >= p) continue;
                 const long slot = (long)(i * n_w + j) * V;
                 for (int t = 0; t < V; ++t) {
-                    const ViewPixel q = view_inverse(view_at(views, t), p, dy, dx);
+                    const ViewPixel q = view_inverse(UPRIGHT ? 0 : view_at(views, t), p, dy, dx);
                     if (!view_inside(q, p)) continue;
                     const long at = ((slot + t) * p + q.y) * p + q.x;
                     if constexpr (VOTES) {
@@ -352,44 +300,41 @@ inline bool aligned16(const void* a) { return (((uintptr_t)a) & 15) == 0; }
         else { if (vec) { LAUNCH(16, true); } else { LAUNCH(16, false); } }               \
     } while (0)
 
-extern "C" int wesup_window_merge_classes(const float* pred, const int32_t* tops, const int32_t* lefts, uint8_t* out,
-                                          int32_t* status, int H, int W, int C, int n_h, int n_w, int p, int votes, void* stream) {
-    if (!pred || !tops || !lefts || !out || !status || p < 1 || p > H || p > W || !cm_range(C) || n_h < 1 || n_w < 1 ||
-        (long)n_h * n_w > 0x7fffffffl || (votes != 0 && votes != 1))
-        return WESUP_ERR_INVALID;
-    hipStream_t st = (hipStream_t)stream;
-    if (wesup_fill_words_(status, 0u, 1, st) != WESUP_OK) return WESUP_ERR_LAUNCH;
-    const dim3 grid(grid_stride_blocks((long)H * W, CM_BLOCK, CM_MAX_BLOCKS)), block(CM_BLOCK);
-    const bool vec = !votes && (C % 4 == 0) && aligned16(pred);
-#define CM_L(CMAX, V)                                                                                                      \
-    if (votes) WESUP_LAUNCH((cm_merge_kernel<CMAX, false, true>), grid, block, 0, st, pred, tops, lefts, out, status, H, W, C, n_h, \
-                            n_w, p);                                                                                       \
-    else WESUP_LAUNCH((cm_merge_kernel<CMAX, V, false>), grid, block, 0, st, pred, tops, lefts, out, status, H, W, C, n_h, n_w, p)
-    CM_DISPATCH(C, vec, CM_L);
-#undef CM_L
-    WESUP_CHECK_LAUNCH();
-    return WESUP_OK;
-}
-
-extern "C" int wesup_window_merge_classes_views(const float* pred, const int32_t* tops, const int32_t* lefts, uint8_t* out,
-                                                int32_t* status, int H, int W, int C, int n_h, int n_w, int p, int n_views,
-                                                uint32_t views, int votes, void* stream) {
+// (called with n_views = 1, views = 0 by the plain entry)
+static int cm_merge(const float* pred, const int32_t* tops, const int32_t* lefts, uint8_t* out, int32_t* status, int H, int W, int C,
+                    int n_h, int n_w, int p, int n_views, uint32_t views, int votes, void* stream) {
     if (!pred || !tops || !lefts || !out || !status || p < 1 || p > H || p > W || !cm_range(C) || n_h < 1 || n_w < 1 ||
         !views_ok(n_views, views) || (long)n_h * n_w * n_views > 0x7fffffffl || (votes != 0 && votes != 1))
         return WESUP_ERR_INVALID;
     hipStream_t st = (hipStream_t)stream;
     if (wesup_fill_words_(status, 0u, 1, st) != WESUP_OK) return WESUP_ERR_LAUNCH;
     const dim3 grid(grid_stride_blocks((long)H * W, CM_BLOCK, CM_MAX_BLOCKS)), block(CM_BLOCK);
-    const bool vec = !votes && (C % 4 == 0) && aligned16(pred);
-#define CM_L(CMAX, V)                                                                                                            \
-    if (votes) WESUP_LAUNCH((cm_merge_views_kernel<CMAX, false, true>), grid, block, 0, st, pred, tops, lefts, out, status, H, W, C, \
-                            n_h, n_w, p, n_views, views);                                                                        \
-    else WESUP_LAUNCH((cm_merge_views_kernel<CMAX, V, false>), grid, block, 0, st, pred, tops, lefts, out, status, H, W, C, n_h, n_w, \
-                      p, n_views, views)
+    const bool vec = !votes && (C % 4 == 0) && aligned16(pred), upright = n_views == 1 && views == 0;
+#define CM_M(CMAX, V, VOTES, UP)                                                                                                   \
+    WESUP_LAUNCH((cm_merge_kernel<CMAX, V, VOTES, UP>), grid, block, 0, st, pred, tops, lefts, out, status, H, W, C, n_h, n_w, p, \
+                 n_views, views)
+#define CM_L(CMAX, V)                                                                            \
+    if (votes) {                                                                                 \
+        if (upright) CM_M(CMAX, false, true, true);                                              \
+        else CM_M(CMAX, false, true, false);                                                     \
+    } else if (upright) CM_M(CMAX, V, false, true);                                              \
+    else CM_M(CMAX, V, false, false)
     CM_DISPATCH(C, vec, CM_L);
 #undef CM_L
+#undef CM_M
     WESUP_CHECK_LAUNCH();
     return WESUP_OK;
+}
+
+extern "C" int wesup_window_merge_classes(const float* pred, const int32_t* tops, const int32_t* lefts, uint8_t* out,
+                                          int32_t* status, int H, int W, int C, int n_h, int n_w, int p, int votes, void* stream) {
+    return cm_merge(pred, tops, lefts, out, status, H, W, C, n_h, n_w, p, 1, 0u, votes, stream);
+}
+
+extern "C" int wesup_window_merge_classes_views(const float* pred, const int32_t* tops, const int32_t* lefts, uint8_t* out,
+                                                int32_t* status, int H, int W, int C, int n_h, int n_w, int p, int n_views,
+                                                uint32_t views, int votes, void* stream) {
+    return cm_merge(pred, tops, lefts, out, status, H, W, C, n_h, n_w, p, n_views, views, votes, stream);
 }
 
 extern "C" int wesup_planes_resize_acc(const float* in, float* out, int h, int w, int H, int W, int C, float alpha, int accumulate,

@@ -22,10 +22,10 @@ Test-time augmentation (``--tta {flips,rot,d4}``, ``views=`` on all eight forms;
 each view of a list -- quarter turns and their mirror images, ``apply_view`` -- every prediction is turned back and the mean runs
 over windows x views (``combine_views_to_image`` / ``combine_views_to_classes``, the specification).  The superpixel model is
 segmented afresh under every view, so the views' tessellations differ and their mean resolves boundaries below superpixel size;
-with two classes it merges un-rounded probabilities under views.  The device-resident forms cut and turn in one kernel
-(``ops.window_gather_views``) and merge through the inverse index (``ops.window_merge_views`` /
-``ops.window_merge_classes_views``).  V views cost V times the forward work; what they gain in accuracy has not been measured
-here (no trained checkpoint)."""
+with two classes it merges un-rounded probabilities under views.  The device-resident forms hand the list on as ``views=``: the
+same ``ops.window_gather`` cuts and turns in one kernel, the same ``ops.window_merge`` / ``ops.window_merge_classes`` merge through
+the inverse index (no views is their one-upright-view case).  V views cost V times the forward work; what they gain in accuracy
+has not been measured here (no trained checkpoint)."""
 import argparse
 import math
 from pathlib import Path
@@ -312,14 +312,14 @@ def _resident_windows(img, patch_size, batch, stain, device, forward, tail, keep
     in it waits for the device.  Returns (the (N, p, p, *tail) device buffer of all windows, tops, lefts, H, W).
 
     With ``views`` (V of them) a view is one more index on the slot axis: N * V slots, slot ``s`` window ``s // V`` under view
-    ``views[s % V]``, ``batch`` SLOTS per pass cut and turned by ``ops.window_gather_views``, and the buffer is
+    ``views[s % V]``, ``batch`` SLOTS per pass cut and turned by ``ops.window_gather(views=...)``, and the buffer is
     (N, V, p, p, *tail), every prediction in the space of its view.  It grows V-fold: the pixel-wise model at C = 16, p = 464,
     16 windows and all eight views keeps 16 * 8 * 464 * 464 * 16 * 4 bytes, about 1.8 GB."""
     p = int(patch_size)
     H, W = img.shape[:2]
     tops, lefts = window_grid(H, W, p)
     N = len(tops) * len(lefts)
-    lead = (N,) if views is None else (N, len(check_views(views)))
+    lead = (N,) if views is None else (N, len(check_views(views)))       # (the buffer has a V axis only under views)
     passes, batch = window_batches(math.prod(lead), batch)
     img_d = _upload(img, device, stain)                              # (a stain fit happens once, on the upright image)
     kept = torch.empty(*lead, p, p, *tail, dtype=torch.float32, device=img_d.device)
@@ -327,10 +327,7 @@ def _resident_windows(img, patch_size, batch, stain, device, forward, tail, keep
     x = torch.empty(batch, 3, p, p, dtype=torch.float32, device=img_d.device)
     with torch.no_grad():
         for first, valid in passes:
-            if views is None:
-                ops.window_gather(img_d, tops, lefts, p, first, batch, out=x)
-            else:
-                ops.window_gather_views(img_d, tops, lefts, p, views, first, batch, out=x)
+            ops.window_gather(img_d, tops, lefts, p, first, batch, out=x, views=views)
             keep(slots, forward(x), first, valid)
     return kept, tops, lefts, H, W
 
@@ -344,8 +341,8 @@ def predict_array_batched(trainer, img, patch_size, batch=4, device='cuda', stai
     turn a pixel whose probability sits at 0.5 (tests/test_tiles_gpu.py).
 
     ``views``: ``predict_array``'s test-time augmentation on the device -- ``batch`` (window, view) slots per pass, the un-rounded
-    painted probabilities of all N x V slots kept (V times the memory and the forward work), ONE ``ops.window_merge_views`` that
-    reads every view through its inverse index, one copy.  Equal to ``predict_array(views=...)`` bit for bit at ``batch=1``; the
+    painted probabilities of all N x V slots kept (V times the memory and the forward work), ONE ``ops.window_merge(views=...)``
+    that reads every view through its inverse index, one copy.  Equal to ``predict_array(views=...)`` bit for bit at ``batch=1``; the
     three other ``_batched`` forms take ``views`` the same way.
 
     A trainer with a CPU ``slic_fn`` still segments window by window on the host inside ``preprocess`` (one round trip per
@@ -354,10 +351,7 @@ def predict_array_batched(trainer, img, patch_size, batch=4, device='cuda', stai
         input_, _ = trainer.preprocess(x)
         return trainer.model(input_)
     kept, tops, lefts, H, W = _resident_windows(img, patch_size, batch, stain, device, forward, (1,), views=views)
-    if views is None:
-        merged = ops.window_merge(kept, tops, lefts, H, W, round_first=True)
-    else:
-        merged = ops.window_merge_views(kept, views, tops, lefts, H, W, round_first=False)
+    merged = ops.window_merge(kept, tops, lefts, H, W, round_first=views is None, views=views)
     return merged.view(H, W).cpu().numpy()
 
 
@@ -369,10 +363,7 @@ def pixel_predict_array_batched(model, img, patch_size, batch=2, device='cuda', 
         kept[first:first + valid, :, :, 0].copy_(pred[:valid, :, :, 1])         # a strided device copy, no arithmetic
     kept, tops, lefts, H, W = _resident_windows(img, patch_size, batch, stain, device, model.forward_batch, (1,), keep_class_1,
                                                 views=views)
-    if views is None:
-        merged = ops.window_merge(kept, tops, lefts, H, W, round_first=False)
-    else:
-        merged = ops.window_merge_views(kept, views, tops, lefts, H, W, round_first=False)
+    merged = ops.window_merge(kept, tops, lefts, H, W, round_first=False, views=views)
     return merged.view(H, W).cpu().numpy()
 
 
@@ -385,10 +376,7 @@ def predict_array_classes_batched(trainer, img, patch_size, batch=4, device='cud
         return trainer.model(input_)
     C = _n_classes(trainer.model)
     kept, tops, lefts, H, W = _resident_windows(img, patch_size, batch, stain, device, forward, (), views=views)
-    if views is None:
-        merged, status = ops.window_merge_classes(kept, tops, lefts, H, W, n_classes=C, votes=True)
-    else:
-        merged, status = ops.window_merge_classes_views(kept, views, tops, lefts, H, W, n_classes=C, votes=True)
+    merged, status = ops.window_merge_classes(kept, tops, lefts, H, W, n_classes=C, votes=True, views=views)
     merged = merged.cpu().numpy()
     _check_status(status, C, 'predict_array_classes_batched')            # (behind the copy: no wait of its own)
     return merged
@@ -401,10 +389,7 @@ def pixel_predict_array_classes_batched(model, img, patch_size, batch=2, device=
     def forward(x):
         return model.forward_batch(x).contiguous()                        # (batch, p, p, C)
     kept, tops, lefts, H, W = _resident_windows(img, patch_size, batch, stain, device, forward, (_n_classes(model),), views=views)
-    if views is None:
-        merged, _ = ops.window_merge_classes(kept, tops, lefts, H, W)     # (probabilities: nothing comes in as an index)
-    else:
-        merged, _ = ops.window_merge_classes_views(kept, views, tops, lefts, H, W)
+    merged, _ = ops.window_merge_classes(kept, tops, lefts, H, W, views=views)      # (probabilities: nothing comes in as an index)
     return merged.cpu().numpy()
 
 

@@ -1878,51 +1878,6 @@ def _lattice(tops, lefts, H, W, p, device):
     return _lattice_axis(tops, H, p, 'tops', device), _lattice_axis(lefts, W, p, 'lefts', device)
 
 
-def window_gather(img_u8_hwc, tops, lefts, p, first, count, out=None):
-    """Network input windows of an image on the device: img (H,W,3) uint8, the lattice ``tops`` x ``lefts`` of
-    infer_tile.window_grid (host integer sequences; checked here, their device copies are cached) -> (count,3,p,p) fp32 in
-    [0, 1], the row-major windows ``first .. first + count - 1``, bit-equal to infer_tile._to_tensor.  Indices past the last
-    window repeat it (the padding of a ragged final batch)."""
-    H, W = _image_u8(img_u8_hwc, 'window_gather')
-    first, count, p = int(first), int(count), int(p)
-    if first < 0 or count < 1:
-        raise _lib.WesupHipError(f'window_gather: windows [{first}, {first} + {count})')
-    tops_d, lefts_d = _lattice(tops, lefts, H, W, p, img_u8_hwc.device)
-    _chk(img_u8_hwc, torch.uint8, 'img')
-    out = _out(out, (count, 3, p, p), torch.float32, img_u8_hwc.device, 'window_gather')
-    if out.data_ptr() % 16:
-        raise _lib.WesupHipError('window_gather: out is not 16-byte aligned')
-    tok = _tbegin('window_gather')
-    _lib.call('wesup_window_gather', _p(img_u8_hwc), _p(tops_d), _p(lefts_d), _p(out), H, W, tops_d.numel(), lefts_d.numel(), p,
-              first, count, _stream())
-    _tend(tok, 15.0 * count * p * p)                  # 3 bytes in, 3 floats out per window pixel
-    return out
-
-
-def window_merge(pred, tops, lefts, H, W, round_first=False, out=None):
-    """Mean over the covering windows: pred (N,p,p,C) or (N,p,p) fp32 for ALL N = len(tops) * len(lefts) windows of one image
-    (row-major) -> (H,W,C) / (H,W) fp64, equal to infer_tile.combine_patches_to_image bit for bit; ``round_first`` rounds
-    every value half to even before it is added (torch.round / np.round of the per-window path)."""
-    if not isinstance(pred, torch.Tensor) or pred.dim() not in (3, 4):
-        raise _lib.WesupHipError('window_merge: expected (N,p,p) or (N,p,p,C) predictions')
-    flat = pred.dim() == 3
-    N, p, p2 = pred.shape[:3]
-    C = 1 if flat else pred.shape[3]
-    H, W = int(H), int(W)
-    if p != p2 or C < 1:
-        raise _lib.WesupHipError(f'window_merge: pred {tuple(pred.shape)}')
-    tops_d, lefts_d = _lattice(tops, lefts, H, W, p, pred.device)
-    if N != tops_d.numel() * lefts_d.numel():
-        raise _lib.WesupHipError(f'window_merge: {N} windows for a lattice of {tops_d.numel()} x {lefts_d.numel()}')
-    _chk(pred, name='pred')
-    out = _out(out, (H, W) if flat else (H, W, C), torch.float64, pred.device, 'window_merge')
-    tok = _tbegin('window_merge')
-    _lib.call('wesup_window_merge', _p(pred), _p(tops_d), _p(lefts_d), _p(out), H, W, C, tops_d.numel(), lefts_d.numel(), p,
-              int(bool(round_first)), _stream())
-    _tend(tok, 4.0 * N * p * p * C + 8.0 * H * W * C)
-    return out
-
-
 def _view_word(views, name):
     """A view list (infer_tile.VIEW_SETS: 1 .. 8 distinct indices in [0, 8), any order) -> (V, the word the entries take: four
     bits per view, the first view in the lowest bits)."""
@@ -1935,50 +1890,94 @@ def _view_word(views, name):
     return len(views), sum(v << (4 * t) for t, v in enumerate(views))
 
 
-def window_gather_views(img_u8_hwc, tops, lefts, p, views, first, count, out=None):
-    """``window_gather`` over the slots of windows x views: slot ``s`` is window ``s // V`` under view ``views[s % V]``
-    (infer_tile.apply_view) -> (count,3,p,p) fp32, the slots ``first .. first + count - 1``, each bit-equal to
-    ``_to_tensor(apply_view(window, v))``.  Slots past the last one repeat it."""
-    H, W = _image_u8(img_u8_hwc, 'window_gather_views')
+def _views_tail(views, name):
+    """``views=`` of the window entries -> (V, the ``n_views, views`` arguments of the ``_views`` entry).  ``None``
+    is (1, ()): the plain entry, the same kernel under the one upright view, whose buffers have no V axis."""
+    if views is None:
+        return 1, ()
+    V, word = _view_word(views, name)
+    return V, (V, word)
+
+
+def window_gather(img_u8_hwc, tops, lefts, p, first, count, out=None, views=None):
+    """Network input windows of an image on the device: img (H,W,3) uint8, the lattice ``tops`` x ``lefts`` of
+    infer_tile.window_grid (host integer sequences; checked here, their device copies are cached) -> (count,3,p,p) fp32 in
+    [0, 1], the row-major windows ``first .. first + count - 1``, bit-equal to infer_tile._to_tensor.  Indices past the last
+    window repeat it (the padding of a ragged final batch).
+
+    ``views`` (a view list, V of them): the slots of windows x views instead -- slot ``s`` is window ``s // V`` under view
+    ``views[s % V]`` (infer_tile.apply_view), each bit-equal to ``_to_tensor(apply_view(window, v))``; slots past the last one
+    repeat it."""
+    H, W = _image_u8(img_u8_hwc, 'window_gather')
     first, count, p = int(first), int(count), int(p)
     if first < 0 or count < 1:
-        raise _lib.WesupHipError(f'window_gather_views: slots [{first}, {first} + {count})')
-    V, word = _view_word(views, 'window_gather_views')
+        raise _lib.WesupHipError(f'window_gather: {"windows" if views is None else "slots"} [{first}, {first} + {count})')
+    V, tail = _views_tail(views, 'window_gather')
     tops_d, lefts_d = _lattice(tops, lefts, H, W, p, img_u8_hwc.device)
     _chk(img_u8_hwc, torch.uint8, 'img')
-    out = _out(out, (count, 3, p, p), torch.float32, img_u8_hwc.device, 'window_gather_views')
+    out = _out(out, (count, 3, p, p), torch.float32, img_u8_hwc.device, 'window_gather')
     if out.data_ptr() % 16:
-        raise _lib.WesupHipError('window_gather_views: out is not 16-byte aligned')
-    tok = _tbegin('window_gather_views')
-    _lib.call('wesup_window_gather_views', _p(img_u8_hwc), _p(tops_d), _p(lefts_d), _p(out), H, W, tops_d.numel(), lefts_d.numel(),
-              p, V, word, first, count, _stream())
-    _tend(tok, 15.0 * count * p * p)                  # 3 bytes in, 3 floats out per slot pixel
+        raise _lib.WesupHipError('window_gather: out is not 16-byte aligned')
+    tok = _tbegin('window_gather')
+    _lib.call('wesup_window_gather_views' if tail else 'wesup_window_gather', _p(img_u8_hwc), _p(tops_d), _p(lefts_d), _p(out), H, W,
+              tops_d.numel(), lefts_d.numel(), p, *tail, first, count, _stream())
+    _tend(tok, 15.0 * count * p * p)                  # 3 bytes in, 3 floats out per window pixel
     return out
+
+
+def _window_preds(pred, views, tops, lefts, H, W, tail_dims, name, classes=None):
+    """What the window merges share, in the order the checks have always had: pred (N,p,p,...) -- (N,V,p,p,...) under ``views`` --
+    with ``tail_dims`` allowed numbers of dimensions behind p x p, for ALL N = len(tops) * len(lefts) windows of the lattice ->
+    (N, V, p, C, the entry's view arguments, the lattice on the device).  C is pred's last dimension (1 without one), or with
+    ``classes = (n_classes, indexed)`` what ``_classes_of`` makes of it.  ``pred``'s own dtype, device and layout are the caller's
+    ``_chk``: the lattice is checked first."""
+    lead = 1 if views is None else 2
+    if not isinstance(pred, torch.Tensor) or pred.dim() - lead - 2 not in tail_dims:
+        shapes = ' or '.join('(N,p,p' + ',C' * d + ')' for d in tail_dims)
+        raise _lib.WesupHipError(f'{name}: expected {shapes} predictions, with V behind N under views')
+    C = 1 if pred.dim() == lead + 2 else pred.shape[-1]
+    if classes is not None:
+        C = _classes_of(pred, *classes, name)
+    V, tail = _views_tail(views, name)
+    N, (p, p2) = pred.shape[0], pred.shape[lead:lead + 2]
+    if p != p2 or C < 1 or (tail and pred.shape[1] != V):
+        raise _lib.WesupHipError(f'{name}: pred {tuple(pred.shape)}' + (f' for {V} views' if tail else ''))
+    tops_d, lefts_d = _lattice(tops, lefts, int(H), int(W), p, pred.device)
+    if N != tops_d.numel() * lefts_d.numel():
+        raise _lib.WesupHipError(f'{name}: {N} windows for a lattice of {tops_d.numel()} x {lefts_d.numel()}')
+    return N, V, p, C, tail, tops_d, lefts_d
+
+
+def window_merge(pred, tops, lefts, H, W, round_first=False, out=None, views=None):
+    """Mean over the covering windows: pred (N,p,p,C) or (N,p,p) fp32 for ALL N = len(tops) * len(lefts) windows of one image
+    (row-major) -> (H,W,C) / (H,W) fp64, equal to infer_tile.combine_patches_to_image bit for bit; ``round_first`` rounds
+    every value half to even before it is added (torch.round / np.round of the per-window path).
+
+    ``views`` (a view list, V of them): the mean over the covering windows and their views -- pred (N,V,p,p,C) or (N,V,p,p), every
+    prediction in the space of its view -- equal to infer_tile.combine_views_to_image bit for bit."""
+    N, V, p, C, tail, tops_d, lefts_d = _window_preds(pred, views, tops, lefts, H, W, (0, 1), 'window_merge')
+    flat = pred.dim() == (4 if tail else 3)
+    H, W = int(H), int(W)
+    _chk(pred, name='pred')
+    out = _out(out, (H, W) if flat else (H, W, C), torch.float64, pred.device, 'window_merge')
+    tok = _tbegin('window_merge')
+    _lib.call('wesup_window_merge_views' if tail else 'wesup_window_merge', _p(pred), _p(tops_d), _p(lefts_d), _p(out), H, W, C,
+              tops_d.numel(), lefts_d.numel(), p, *tail, int(bool(round_first)), _stream())
+    _tend(tok, 4.0 * N * V * p * p * C + 8.0 * H * W * C)
+    return out
+
+
+# ``views=`` as a positional argument, the spelling before the keyword: forwarded, nothing of their own.
+def window_gather_views(img_u8_hwc, tops, lefts, p, views, first, count, out=None):
+    return window_gather(img_u8_hwc, tops, lefts, p, first, count, out=out, views=views)
 
 
 def window_merge_views(pred, views, tops, lefts, H, W, round_first=False, out=None):
-    """Mean over the covering windows and their views: pred (N,V,p,p,C) or (N,V,p,p) fp32, every prediction in the space of its
-    view, for ALL N = len(tops) * len(lefts) windows (row-major) -> (H,W,C) / (H,W) fp64, equal to
-    infer_tile.combine_views_to_image bit for bit; ``round_first`` as in ``window_merge``."""
-    if not isinstance(pred, torch.Tensor) or pred.dim() not in (4, 5):
-        raise _lib.WesupHipError('window_merge_views: expected (N,V,p,p) or (N,V,p,p,C) predictions')
-    flat = pred.dim() == 4
-    N, Vp, p, p2 = pred.shape[:4]
-    C = 1 if flat else pred.shape[4]
-    H, W = int(H), int(W)
-    V, word = _view_word(views, 'window_merge_views')
-    if p != p2 or C < 1 or Vp != V:
-        raise _lib.WesupHipError(f'window_merge_views: pred {tuple(pred.shape)} for {V} views')
-    tops_d, lefts_d = _lattice(tops, lefts, H, W, p, pred.device)
-    if N != tops_d.numel() * lefts_d.numel():
-        raise _lib.WesupHipError(f'window_merge_views: {N} windows for a lattice of {tops_d.numel()} x {lefts_d.numel()}')
-    _chk(pred, name='pred')
-    out = _out(out, (H, W) if flat else (H, W, C), torch.float64, pred.device, 'window_merge_views')
-    tok = _tbegin('window_merge_views')
-    _lib.call('wesup_window_merge_views', _p(pred), _p(tops_d), _p(lefts_d), _p(out), H, W, C, tops_d.numel(), lefts_d.numel(), p,
-              V, word, int(bool(round_first)), _stream())
-    _tend(tok, 4.0 * N * V * p * p * C + 8.0 * H * W * C)
-    return out
+    return window_merge(pred, tops, lefts, H, W, round_first=round_first, out=out, views=views)
+
+
+def window_merge_classes_views(pred, views, tops, lefts, H, W, n_classes=None, votes=False, out=None, status=None):
+    return window_merge_classes(pred, tops, lefts, H, W, n_classes=n_classes, votes=votes, out=out, status=status, views=views)
 
 
 # ---------------------------------------------------------------- whole-image multi-scale pixel inference (csrc/pixel.hip)
@@ -2212,57 +2211,26 @@ def _status(status, device, name):
     return status
 
 
-def window_merge_classes(pred, tops, lefts, H, W, n_classes=None, votes=False, out=None, status=None):
+def window_merge_classes(pred, tops, lefts, H, W, n_classes=None, votes=False, out=None, status=None, views=None):
     """The class map of a window-merged prediction for ALL N = len(tops) * len(lefts) windows of one image (row-major) ->
     (out (H,W) uint8 class indices, status (1,) int32), equal to infer_tile.combine_patches_to_classes bit for bit.
     ``votes=False``: pred (N,p,p,C) fp32 probabilities; per class the fp64 mean over the covering windows of ``window_merge``,
     then the first maximum.  ``votes=True``: pred (N,p,p) fp32 class indices (what the superpixel model paints for C > 2) and
     ``n_classes``; every covering window votes and the first maximum of the counts wins.  A vote outside [0, C) is not counted
-    and sets ``status`` (zeroed by the entry)."""
+    and sets ``status`` (zeroed by the entry).
+
+    ``views`` (a view list, V of them): over windows x views -- pred (N,V,p,p,C) or, with votes, (N,V,p,p), every prediction in the
+    space of its view; every (window, view) votes -- equal to infer_tile.combine_views_to_classes bit for bit."""
     votes = bool(votes)
-    if not isinstance(pred, torch.Tensor) or pred.dim() != (3 if votes else 4):
-        raise _lib.WesupHipError('window_merge_classes: expected (N,p,p,C) probabilities, or (N,p,p) class indices with votes=True')
-    N, p, p2 = pred.shape[:3]
-    C = _classes_of(pred, n_classes, votes, 'window_merge_classes')
+    N, V, p, C, tail, tops_d, lefts_d = _window_preds(pred, views, tops, lefts, H, W, (0,) if votes else (1,), 'window_merge_classes',
+                                                      classes=(n_classes, votes))
     H, W = int(H), int(W)
-    if p != p2:
-        raise _lib.WesupHipError(f'window_merge_classes: pred {tuple(pred.shape)}')
-    tops_d, lefts_d = _lattice(tops, lefts, H, W, p, pred.device)
-    if N != tops_d.numel() * lefts_d.numel():
-        raise _lib.WesupHipError(f'window_merge_classes: {N} windows for a lattice of {tops_d.numel()} x {lefts_d.numel()}')
     _chk(pred, name='pred')
     out = _out(out, (H, W), torch.uint8, pred.device, 'window_merge_classes')
     status = _status(status, pred.device, 'window_merge_classes')
     tok = _tbegin('window_merge_classes')
-    _lib.call('wesup_window_merge_classes', _p(pred), _p(tops_d), _p(lefts_d), _p(out), _p(status), H, W, C, tops_d.numel(),
-              lefts_d.numel(), p, int(votes), _stream())
-    _tend(tok, 4.0 * N * p * p * (1 if votes else C) + 1.0 * H * W)
-    return out, status
-
-
-def window_merge_classes_views(pred, views, tops, lefts, H, W, n_classes=None, votes=False, out=None, status=None):
-    """``window_merge_classes`` over windows x views -> (out (H,W) uint8, status (1,) int32), equal to
-    infer_tile.combine_views_to_classes bit for bit.  ``votes=False``: pred (N,V,p,p,C) fp32 probabilities; ``votes=True``: pred
-    (N,V,p,p) fp32 class indices and ``n_classes``, every (window, view) votes.  Every prediction is in the space of its view."""
-    votes = bool(votes)
-    if not isinstance(pred, torch.Tensor) or pred.dim() != (4 if votes else 5):
-        raise _lib.WesupHipError('window_merge_classes_views: expected (N,V,p,p,C) probabilities, or (N,V,p,p) class indices with '
-                                 'votes=True')
-    N, Vp, p, p2 = pred.shape[:4]
-    C = _classes_of(pred, n_classes, votes, 'window_merge_classes_views')
-    H, W = int(H), int(W)
-    V, word = _view_word(views, 'window_merge_classes_views')
-    if p != p2 or Vp != V:
-        raise _lib.WesupHipError(f'window_merge_classes_views: pred {tuple(pred.shape)} for {V} views')
-    tops_d, lefts_d = _lattice(tops, lefts, H, W, p, pred.device)
-    if N != tops_d.numel() * lefts_d.numel():
-        raise _lib.WesupHipError(f'window_merge_classes_views: {N} windows for a lattice of {tops_d.numel()} x {lefts_d.numel()}')
-    _chk(pred, name='pred')
-    out = _out(out, (H, W), torch.uint8, pred.device, 'window_merge_classes_views')
-    status = _status(status, pred.device, 'window_merge_classes_views')
-    tok = _tbegin('window_merge_classes_views')
-    _lib.call('wesup_window_merge_classes_views', _p(pred), _p(tops_d), _p(lefts_d), _p(out), _p(status), H, W, C, tops_d.numel(),
-              lefts_d.numel(), p, V, word, int(votes), _stream())
+    _lib.call('wesup_window_merge_classes_views' if tail else 'wesup_window_merge_classes', _p(pred), _p(tops_d), _p(lefts_d), _p(out),
+              _p(status), H, W, C, tops_d.numel(), lefts_d.numel(), p, *tail, int(votes), _stream())
     _tend(tok, 4.0 * N * V * p * p * (1 if votes else C) + 1.0 * H * W)
     return out, status
 
