@@ -572,6 +572,39 @@ int wesup_label_grow(const uint8_t* mask, const int32_t* seeds, int32_t* labels,
  * no byte with mask or labels */
 int wesup_label_cut(const uint8_t* mask, const int32_t* labels, uint8_t* out, int B, int H, int W, void* stream);
 
+/* ------------------------------------------------------------------ surface-distance metrics (csrc/surface.hip)
+ * Masks and border maps uint8 [B][H][W] (non-zero = set), distance maps int32 [B][H][W]; the shapes of the section above.  All
+ * integer but the two sums of square roots, equal to the numpy restatement in wesup_amd/surface.py bit for bit.  Every entry
+ * returns WESUP_ERR_INVALID for a null pointer, a non-positive or oversized shape, a short workspace and overlapping operands, on
+ * the host and before any launch.
+ *
+ * wesup_edt_full: the exact squared Euclidean distance map, without a cap: d2 = 0 where the mask is 0, elsewhere the squared
+ * distance to the nearest zero pixel of the same image (pixels outside the image are not zero pixels), WESUP_EDT_NONE everywhere
+ * in an image without a zero pixel.  invert = 1 transforms (mask == 0) instead.  Shapes with (H-1)^2 + (W-1)^2 >=
+ * WESUP_EDT_NONE are refused (the workspace query returns 0).  Three launches whatever the data; the column pass works on chunks
+ * of WESUP_EDT_CHUNK rows and blocks of WESUP_EDT_COLS columns, the row pass on WESUP_EDT_ROWS rows of WESUP_EDT_SEG pixels per
+ * block and scans outward until dx^2 reaches the best value so far: O(W) per pixel at worst. */
+#define WESUP_EDT_NONE 2147483647
+#define WESUP_EDT_CHUNK 64
+#define WESUP_EDT_COLS 256
+#define WESUP_EDT_SEG 64
+#define WESUP_EDT_ROWS 4
+size_t wesup_edt_full_workspace_bytes(int B, int H, int W);
+int wesup_edt_full(const uint8_t* mask, int32_t* d2, int B, int H, int W, int invert, void* ws, size_t ws_bytes, void* stream);
+/* out = 1 where the mask is set and one of the pixel's four neighbours is 0 or lies outside the image, 0 elsewhere */
+int wesup_mask_border(const uint8_t* mask, uint8_t* out, int B, int H, int W, void* stream);
+/* The raw quantities of the surface metrics of B image pairs: border_p / border_g the two border maps, d2_to_g / d2_to_p the
+ * distance maps to the borders (wesup_edt_full of the border maps with invert = 1).  stats [B][WESUP_SURFACE_STATS] 8-byte slots
+ * that stay on the device: int64 n_p, n_g, max_pg, max_gp, within_p, within_g (d2 <= t2), lo, hi, then float64 sum_pg, sum_gp (the
+ * roots of d2_to_g over border_p and of d2_to_p over border_g, reduced in a fixed order: the same input gives the same bits).
+ * lo and hi are the order statistics k = floor((n - 1) * q_frac) and min(k + 1, n - 1) of the n = n_p + n_g squared distances of
+ * both directions together, the ranks derived on the device; q_frac_bits carries the bits of the float64 q_frac in [0, 1].  An
+ * empty border: its count, maximum and sum are 0; both empty: lo = hi = 0.  Eleven launches (eight of them the select's), no read-back. */
+#define WESUP_SURFACE_STATS 10
+size_t wesup_surface_stats_workspace_bytes(int B, int H, int W);
+int wesup_surface_stats(const uint8_t* border_p, const uint8_t* border_g, const int32_t* d2_to_g, const int32_t* d2_to_p,
+                        void* stats, int B, int H, int W, long t2, long q_frac_bits, void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------ painted object comparisons (csrc/paint.hip)
  * wesup_object_match: tables [B][nS + 1][nG + 1] as wesup_contingency writes them (nS, nG: the maxima of the batch), nS_dev /
  * nG_dev [B]: each image's own object counts (wesup_cc_label's n_labels); cells outside an image's own counts are not read.
@@ -811,6 +844,11 @@ int wesup_tsne_iterate(const float* p, float* y, float* upd, float* gains, float
 #define WESUP_SELECT_MAX_RANKS 4
 size_t wesup_select_f32_workspace_bytes(long n);
 int wesup_select_f32(const float* keys, long n, const long* ranks, int n_ranks, float* out, void* ws, size_t ws_bytes,
+                     void* stream);
+/* The same for int32 keys 0 .. 2^31 - 1 (a negative key is outside the contract): np.sort(keys)[ranks], through the same passes --
+ * on a pattern with the sign bit clear the select's key map is a pure bit map that keeps the integer order, NaN patterns included. */
+size_t wesup_select_i32_workspace_bytes(long n);
+int wesup_select_i32(const int32_t* keys, long n, const long* ranks, int n_ranks, int32_t* out, void* ws, size_t ws_bytes,
                      void* stream);
 /* The fit of image b, WESUP_STAIN_BLOCK floats (64 bytes) that stay on the device:
  *   [0..5] HE[c][k] (c = r, g, b; k = 0 "H", 1 "E"), [6..11] pinv[k][c], [12..13] maxC[k], [14] n_tissue, [15] valid (1 or 0;

@@ -141,6 +141,12 @@ _SIGS = {
     'wesup_label_grow_workspace_bytes': (c_size_t, 'iii'),
     'wesup_label_grow': (c_int, 'pppp' + 'iiiiii' + 'pzp'),
     'wesup_label_cut': (c_int, 'ppp' + 'iii' + 'p'),
+    # surface-distance metrics: the exact distance map, borders, the raw quantities (csrc/surface.hip)
+    'wesup_edt_full_workspace_bytes': (c_size_t, 'iii'),
+    'wesup_edt_full': (c_int, 'pp' + 'iiii' + 'pzp'),
+    'wesup_mask_border': (c_int, 'pp' + 'iii' + 'p'),
+    'wesup_surface_stats_workspace_bytes': (c_size_t, 'iii'),
+    'wesup_surface_stats': (c_int, 'ppppp' + 'iii' + 'll' + 'pzp'),
     # painted object comparisons (csrc/paint.hip)
     'wesup_object_match_workspace_bytes': (c_size_t, 'ii'),
     'wesup_object_match': (c_int, 'pppp' + 'iii' + 'pzp'),
@@ -154,6 +160,8 @@ _SIGS = {
     # stain normalisation and stain jitter, exact order statistics (csrc/stain.hip)
     'wesup_select_f32_workspace_bytes': (c_size_t, 'l'),
     'wesup_select_f32': (c_int, 'plpip' + 'pzp'),
+    'wesup_select_i32_workspace_bytes': (c_size_t, 'l'),
+    'wesup_select_i32': (c_int, 'plpip' + 'pzp'),
     'wesup_stain_fit_workspace_bytes': (c_size_t, 'iiii'),
     'wesup_stain_fit_stage_offset': (c_size_t, 'iiiii'),
     'wesup_stain_fit': (c_int, 'pp' + 'iiii' + 'fffi' + 'pzp'),
@@ -241,6 +249,10 @@ SELECT_MAX_RANKS = 4     # WESUP_SELECT_MAX_RANKS
 STAIN_BLOCK = 16         # WESUP_STAIN_BLOCK: HE[3][2], pinv[2][3], maxC[2], n_tissue, valid
 SPLIT_SEG, SPLIT_ROWS = 64, 4      # WESUP_SPLIT_SEG, WESUP_SPLIT_ROWS: the distance map's row pass, 4 rows of 64 pixels per block
 SPLIT_TILE, SPLIT_HALO = 32, 8     # WESUP_SPLIT_TILE, WESUP_SPLIT_HALO: the growth kernel's tile edge and halo (rounds per launch)
+EDT_NONE = 2 ** 31 - 1              # WESUP_EDT_NONE: the distance map of an image without a zero pixel
+EDT_CHUNK, EDT_COLS = 64, 256      # WESUP_EDT_CHUNK, WESUP_EDT_COLS: the full distance map's column pass, chunks of rows x columns per block
+EDT_SEG, EDT_ROWS = 64, 4          # WESUP_EDT_SEG, WESUP_EDT_ROWS: its row pass, 4 rows of 64 pixels per block
+SURFACE_STATS = 10                 # WESUP_SURFACE_STATS: 8-byte slots of a pair's block
 TISSUE_MAX_BLOCKS = 2048           # WESUP_TISSUE_MAX_BLOCKS: the histogram kernel's grid, striding over its items
 TISSUE_ITEM_PIXELS = 8192          # WESUP_TISSUE_ITEM_PIXELS: an item is max(1, this // p) rows of one patch
 TISSUE_LIST_CHUNK = 256            # WESUP_TISSUE_LIST_CHUNK: patches per step of the ordered compaction

@@ -54,6 +54,12 @@ static inline bool fastdiv_image_exact(int B, int H, int W) {
     return fastdiv_exact((long)B * H * W, W) && fastdiv_exact((long)B * H, H);
 }
 
+// stain.hip: the exact radix select (wesup_select_f32) for `batch` arrays of n keys each, as the modules of the library call it.
+// ws holds wesup_select_workspace_bytes_(n, batch) bytes, 16-byte aligned; ranks [batch][rank_stride] on the device.
+size_t wesup_select_workspace_bytes_(long n, int batch);
+void wesup_select_launch_(const float* keys, long key_stride, long n, const long* ranks, long rank_stride, int n_ranks, float* out,
+                          long out_stride, int batch, void* ws, hipStream_t st);
+
 // Bijective XCD-aware block remap (cdna_hip_programming.md 5, "XCD swizzle must be bijective"):
 // blocks b and b+8 share an XCD; give each XCD a contiguous range of logical tiles so that
 // neighbouring tiles (which share activation rows / halos) hit the same L2.

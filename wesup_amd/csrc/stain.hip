@@ -606,6 +606,13 @@ __global__ __launch_bounds__(256) void st_apply_kernel(const uint8_t* img, uint8
 
 }  // namespace
 
+// the select for the other modules of the library (common.hpp; csrc/surface.hip)
+size_t wesup_select_workspace_bytes_(long n, int batch) { return sel_ws_bytes(n, batch); }
+void wesup_select_launch_(const float* keys, long key_stride, long n, const long* ranks, long rank_stride, int n_ranks, float* out,
+                          long out_stride, int batch, void* ws, hipStream_t st) {
+    sel_launch(keys, key_stride, n, ranks, rank_stride, n_ranks, out, out_stride, batch, ws, st);
+}
+
 // ---------------------------------------------------------------- entries
 extern "C" size_t wesup_select_f32_workspace_bytes(long n) {
     if (n < 1) return 0;
@@ -695,4 +702,15 @@ extern "C" int wesup_stain_apply(const uint8_t* img, uint8_t* out, const float* 
                  jitter, keep_residual, HW, io, wide);
     WESUP_CHECK_LAUNCH();
     return WESUP_OK;
+}
+
+// Non-negative int32 keys through the same passes.  A key 0 .. 2^31 - 1 read as a float has its sign bit clear, and sel_key maps
+// such a pattern u to u | 0x80000000: a pure bit map that keeps the integer order of every one of them, the patterns above
+// 0x7F800000 (NaNs to a float reader) included; sel_unkey clears the bit again.  Between the load and the store the value only
+// passes through bit casts and integer instructions, so no NaN is quieted on the way.
+extern "C" size_t wesup_select_i32_workspace_bytes(long n) { return wesup_select_f32_workspace_bytes(n); }
+
+extern "C" int wesup_select_i32(const int32_t* keys, long n, const long* ranks, int n_ranks, int32_t* out, void* ws, size_t ws_bytes,
+                                void* stream) {
+    return wesup_select_f32((const float*)keys, n, ranks, n_ranks, (float*)out, ws, ws_bytes, stream);
 }

@@ -1500,6 +1500,97 @@ def split_objects(mask, radius, return_labels=False):
     return (out, labels) if return_labels else out
 
 
+# ---------------------------------------------------------------- surface-distance metrics (csrc/surface.hip)
+EDT_NONE = _lib.EDT_NONE
+SURFACE_STAT_KEYS = ('n_p', 'n_g', 'max_pg', 'max_gp', 'within_p', 'within_g', 'lo', 'hi', 'sum_pg', 'sum_gp')
+
+
+def _edt_shape(B, H, W, name):
+    if (H - 1) ** 2 + (W - 1) ** 2 >= EDT_NONE:
+        raise _lib.WesupHipError(f'{name}: squared distances of a {H} x {W} image reach {EDT_NONE}')
+    if not _lib.load().wesup_edt_full_workspace_bytes(B, H, W):
+        raise _lib.WesupHipError(f'{name}: shape ({B}, {H}, {W}) is outside the entry\'s range')
+
+
+def edt_sq_full(mask, invert=False):
+    """Exact squared distance map without a cap: mask (H,W) / (B,H,W) uint8 -> int32 of the same shape, 0 where the mask is 0 and
+    elsewhere the squared distance to the nearest zero pixel of the same image, EDT_NONE in an image without one
+    (surface.edt_sq_full_host).  ``invert`` transforms ``mask == 0`` instead."""
+    m, squeeze = _mask3(mask)
+    B, H, W = m.shape
+    _edt_shape(B, H, W, 'edt_sq_full')
+    d2 = torch.empty(B, H, W, dtype=torch.int32, device=m.device)
+    nb = _lib.load().wesup_edt_full_workspace_bytes(B, H, W)
+    ws = workspace(nb, m.device, 'regions')
+    _lib.call('wesup_edt_full', _p(m), _p(d2), B, H, W, int(bool(invert)), _p(ws), nb, _stream())
+    return d2[0] if squeeze else d2
+
+
+def mask_border(mask):
+    """The 4-neighbour border of a mask: (H,W) / (B,H,W) uint8 -> {0,1} uint8 of the same shape, 1 on the foreground pixels with
+    a neighbour on the background or outside the image (surface.border_host)."""
+    m, squeeze = _mask3(mask)
+    B, H, W = m.shape
+    if min(B, H, W) < 1:
+        raise _lib.WesupHipError(f'mask_border: empty shape {tuple(m.shape)}')
+    out = torch.empty_like(m)
+    _lib.call('wesup_mask_border', _p(m), _p(out), B, H, W, _stream())
+    return out[0] if squeeze else out
+
+
+def select_i32(keys, ranks, out=None):
+    """keys (n,) int32, all >= 0 (not checked: that would be a read-back), ranks (r,) int64 ON THE DEVICE, r <= 4 -> (r,) int32:
+    np.sort(keys)[ranks], exact, without a read-back.  A rank outside [0, n) is taken to the nearest end."""
+    _chk(keys, torch.int32, 'keys'); _chk(ranks, torch.int64, 'ranks')
+    n, r = keys.numel(), ranks.numel()
+    if keys.dim() != 1 or ranks.dim() != 1 or n < 1 or not 1 <= r <= _lib.SELECT_MAX_RANKS or ranks.device != keys.device:
+        raise _lib.WesupHipError(f'select_i32: keys {tuple(keys.shape)}, ranks {tuple(ranks.shape)} (1 .. {_lib.SELECT_MAX_RANKS} ranks)')
+    out = torch.empty(r, dtype=torch.int32, device=keys.device) if out is None else _chk(out, torch.int32, 'out')
+    if out.numel() != r or out.device != keys.device:
+        raise _lib.WesupHipError(f'select_i32: out {tuple(out.shape)} for {r} ranks')
+    nb = _lib.load().wesup_select_i32_workspace_bytes(n)
+    ws = workspace(nb, keys.device, 'regions')
+    _lib.call('wesup_select_i32', _p(keys), n, _p(ranks), r, _p(out), _p(ws), nb, _stream())
+    return out
+
+
+def surface_stats_blocks(pred, gt, tolerance, q=95.0):
+    """The launch chain of ``surface_stats`` without its read-back: (B,H,W) masks -> the (B, 10) int64 tensor of the pairs'
+    blocks on the device (slots 8 and 9 hold the bits of the two float64 sums).  Borders of both masks in one launch, both
+    distance maps in one transform of 2 B images, the reductions and the selection."""
+    p, _ = _mask3(pred, 'pred')
+    g, _ = _mask3(gt, 'gt')
+    if p.shape != g.shape or p.device != g.device:
+        raise _lib.WesupHipError(f'surface_stats: pred {tuple(p.shape)} and gt {tuple(g.shape)} differ')
+    tolerance, q = float(tolerance), float(q)
+    if not 0.0 <= tolerance < float('inf') or not 0.0 <= q <= 100.0:
+        raise _lib.WesupHipError(f'surface_stats: tolerance {tolerance} (finite, >= 0), q {q} (0 .. 100)')
+    B, H, W = p.shape
+    if 2 * B > 65535:
+        raise _lib.WesupHipError(f'surface_stats: {B} pairs (at most 32767)')
+    _edt_shape(2 * B, H, W, 'surface_stats')
+    t2 = int(min(tolerance * tolerance, float(EDT_NONE)))            # floor of the float64 square, as the host takes it (no d2 is above EDT_NONE)
+    q_bits = struct.unpack('<q', struct.pack('<d', q / 100.0))[0]
+    borders = mask_border(torch.cat((p, g)))                         # S_P of every pair, then S_G
+    d2 = edt_sq_full(borders, invert=True)                           # the distances to S_P, then to S_G
+    stats = torch.empty(B, _lib.SURFACE_STATS, dtype=torch.int64, device=p.device)
+    nb = _lib.load().wesup_surface_stats_workspace_bytes(B, H, W)
+    ws = workspace(nb, p.device, 'surface')                          # (the distance maps' scratch is 'regions': another buffer)
+    _lib.call('wesup_surface_stats', _p(borders[:B]), _p(borders[B:]), _p(d2[B:]), _p(d2[:B]), _p(stats), B, H, W, t2, q_bits,
+              _p(ws), nb, _stream())
+    return stats
+
+
+def surface_stats(pred, gt, tolerance, q=95.0):
+    """The raw quantities of the surface metrics (surface.surface_stats_host) as Python numbers: pred, gt (H,W) uint8 -> a dict
+    of SURFACE_STAT_KEYS, (B,H,W) -> a list of B dicts.  One read-back of 80 bytes per pair, after the whole chain."""
+    blocks = surface_stats_blocks(pred, gt, tolerance, q).cpu()
+    sums = blocks[:, 8:].contiguous().view(torch.float64)
+    rows = [dict(zip(SURFACE_STAT_KEYS, [int(v) for v in blocks[b, :8]] + [float(v) for v in sums[b]]))
+            for b in range(blocks.shape[0])]
+    return rows[0] if pred.dim() == 2 else rows
+
+
 def contingency(S, G, nS, nG):
     """Label maps S, G (H,W) / (B,H,W) int32 with labels in [0, nS] / [0, nG] -> (B, nS+1, nG+1) int32 pixel counts (the batch
     axis only for batched input).  Raises when a label lies outside the table or the table would exceed
