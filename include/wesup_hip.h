@@ -187,7 +187,10 @@ int wesup_conv3x3_dgrad_winograd_unpool(const float* dy, const float* u_dgrad, c
  * Mt [P][tiles][C] -> y = A^T M A + bias, masked by mask_src > 0, added to the old y if accumulate, with the optional
  * second output y_relu = max(y, 0).  plane_elems: elements between two of the P position planes of V / Mt (0: tiles * C);
  * larger when a sub-batch works inside the planes of a whole batch, which is how the engine can pipeline the memory-bound
- * transforms of one half of the batch under the GEMM of the other. */
+ * transforms of one half of the batch under the GEMM of the other.  plane_elems must be a multiple of 4 and, unless 0, at
+ * least tiles * C (WESUP_ERR_INVALID otherwise); what lies between two planes is neither read nor written.  The entries that
+ * take it are wesup_winograd_input_transform[_bits], _output_transform[_unpool] and the three _gemm_output_transform* (there
+ * for V); _outgrad_transform, _dual_transform[_unpool] and the composite entries always work on dense planes. */
 int wesup_winograd_input_transform(const float* x, float* V, long plane_elems, int B, int H, int W, int C, int relu_in,
                                    int m, void* stream);
 int wesup_gemm_nt_batched(const float* A, int lda, long strideA, const float* B, int ldb, long strideB,
@@ -284,7 +287,10 @@ int wesup_conv3x3_dgrad_winograd_gather(const float* dy, const float* u_dgrad, c
  * column sums of its dM operand) to dw (Cout,Cin,3,3) = G^T (sum over S) G.  The bias gradient db = sum over pixels of dy:
  * m = 2, the column sums of dM at position (1,1) (index 5; filter_grad's db); m = 4 (its point set 0, +-3/4, +-3/2, inf
  * has no position that is a plain sum), the optional db of the outgrad transform, summed from the values it loads anyway
- * (ws: wesup_winograd_outgrad_workspace_bytes; db must be NULL for m = 2 there, and for m = 4 in filter_grad). */
+ * (ws: wesup_winograd_outgrad_workspace_bytes; db must be NULL for m = 2 there, and for m = 4 in filter_grad).
+ * filter_grad: slab_stride = elements between two splits (>= Cout*Cin + Cout), batch_stride = between two positions
+ * (>= S * slab_stride); any such strides, pair counts and alignment are accepted -- m = 4 reads 16 bytes at a time only where
+ * Cout*Cin, both strides and the pointer allow it, and gives the same bits either way. */
 size_t wesup_winograd_outgrad_workspace_bytes(int B, int H, int W, int C, int m);
 int wesup_winograd_outgrad_transform(const float* dy, float* dM, float* db, int B, int H, int W, int C, int m,
                                      void* ws, size_t ws_bytes, void* stream);
