@@ -611,6 +611,35 @@ size_t wesup_surface_stats_workspace_bytes(int B, int H, int W);
 int wesup_surface_stats(const uint8_t* border_p, const uint8_t* border_g, const int32_t* d2_to_g, const int32_t* d2_to_p,
                         void* stats, int B, int H, int W, long t2, long q_frac_bits, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------ object outlines (csrc/contour.hip)
+ * Label maps int32 [B][H][W]; B <= 65535 and 4 B H W < 2^31 (slots and crack indices are int32).  All integer, equal to the
+ * sequential tracer wesup_amd/contour.py:trace_host word for word.  A crack is a unit edge between a pixel of label l > 0 and a
+ * 4-neighbour of another label or the outside, directed with the pixel on its left (sides N W S E = 0 1 2 3, slot 4 (r W + c) +
+ * side); its successor is the first of right turn, straight on, left turn that is a crack of l, so the cracks fall into rings.
+ * Every entry returns WESUP_ERR_INVALID for a null pointer, a bad shape, a short workspace, negative counts and overlapping
+ * operands, on the host and before any launch.
+ *
+ * The workspace: wesup_contour_workspace_bytes serves every map of the shape (4 B H W cracks), 0 for a bad shape;
+ * wesup_contour_trace_workspace_bytes is what a map of n_cracks cracks needs (what the entries ask for: wesup_contour_count
+ * takes n_cracks = 0), 0 for a bad shape and for n_cracks outside 0 .. 4 B H W.
+ *
+ * wesup_contour_count: counts [B][2] = the cracks and the corners of every image (a crack starts a corner when its predecessor
+ * has another direction).  Local work: no ring is followed.
+ *
+ * wesup_contour_trace: n_cracks / n_corners the totals of counts over the batch, ring_cap the records rings holds (rings never
+ * exceed corners / 4).  rings [ring_cap][WESUP_CONTOUR_RING] int32, 8-byte aligned: image, label, index of the first vertex,
+ * vertices, cracks, xmin, ymin, xmax, ymax, leader slot (the ring's smallest, within its image), area2 as one int64 (positive:
+ * an outer ring, counter-clockwise on screen; negative: a hole).  Rings in the order of (image, leader slot); verts [n_corners][2]
+ * int32 (x, y) ring after ring, each from its leader on; n_rings [B].  When the map does not hold exactly n_cracks cracks and
+ * n_corners corners, or holds more than ring_cap rings, status[0] |= 1 and no word of rings or verts is written (n_rings is
+ * zeroed); status is never cleared here.  18 + ceil(log2 n_cracks) launches whatever the data. */
+#define WESUP_CONTOUR_RING 12
+size_t wesup_contour_workspace_bytes(int B, int H, int W);
+size_t wesup_contour_trace_workspace_bytes(int B, int H, int W, int n_cracks);
+int wesup_contour_count(const int32_t* labels, int32_t* counts, int B, int H, int W, void* ws, size_t ws_bytes, void* stream);
+int wesup_contour_trace(const int32_t* labels, int32_t* rings, int32_t* verts, int32_t* n_rings, int32_t* status, int B, int H,
+                        int W, int n_cracks, int n_corners, int ring_cap, void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------ painted object comparisons (csrc/paint.hip)
  * wesup_object_match: tables [B][nS + 1][nG + 1] as wesup_contingency writes them (nS, nG: the maxima of the batch), nS_dev /
  * nG_dev [B]: each image's own object counts (wesup_cc_label's n_labels); cells outside an image's own counts are not read.

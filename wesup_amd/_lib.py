@@ -147,6 +147,11 @@ _SIGS = {
     'wesup_mask_border': (c_int, 'pp' + 'iii' + 'p'),
     'wesup_surface_stats_workspace_bytes': (c_size_t, 'iii'),
     'wesup_surface_stats': (c_int, 'ppppp' + 'iii' + 'll' + 'pzp'),
+    # object outlines: ordered boundary rings of a label map (csrc/contour.hip)
+    'wesup_contour_workspace_bytes': (c_size_t, 'iii'),
+    'wesup_contour_trace_workspace_bytes': (c_size_t, 'iiii'),
+    'wesup_contour_count': (c_int, 'pp' + 'iii' + 'pzp'),
+    'wesup_contour_trace': (c_int, 'ppppp' + 'iiiiii' + 'pzp'),
     # painted object comparisons (csrc/paint.hip)
     'wesup_object_match_workspace_bytes': (c_size_t, 'ii'),
     'wesup_object_match': (c_int, 'pppp' + 'iii' + 'pzp'),
@@ -253,6 +258,7 @@ EDT_NONE = 2 ** 31 - 1              # WESUP_EDT_NONE: the distance map of an ima
 EDT_CHUNK, EDT_COLS = 64, 256      # WESUP_EDT_CHUNK, WESUP_EDT_COLS: the full distance map's column pass, chunks of rows x columns per block
 EDT_SEG, EDT_ROWS = 64, 4          # WESUP_EDT_SEG, WESUP_EDT_ROWS: its row pass, 4 rows of 64 pixels per block
 SURFACE_STATS = 10                 # WESUP_SURFACE_STATS: 8-byte slots of a pair's block
+CONTOUR_RING = 12                  # WESUP_CONTOUR_RING: int32 words of a ring record
 TISSUE_MAX_BLOCKS = 2048           # WESUP_TISSUE_MAX_BLOCKS: the histogram kernel's grid, striding over its items
 TISSUE_ITEM_PIXELS = 8192          # WESUP_TISSUE_ITEM_PIXELS: an item is max(1, this // p) rows of one patch
 TISSUE_LIST_CHUNK = 256            # WESUP_TISSUE_LIST_CHUNK: patches per step of the ordered compaction

@@ -1591,6 +1591,56 @@ def surface_stats(pred, gt, tolerance, q=95.0):
     return rows[0] if pred.dim() == 2 else rows
 
 
+# ---------------------------------------------------------------- object outlines (csrc/contour.hip)
+CONTOUR_RING = _lib.CONTOUR_RING
+
+
+def _labels_bhw(labels, name):
+    """(H,W) or (B,H,W) int32 -> (B,H,W) inside the entries' range (4 B H W < 2^31)."""
+    _chk(labels, torch.int32, name)
+    if labels.dim() not in (2, 3):
+        raise _lib.WesupHipError(f'{name}: expected (H,W) or (B,H,W), got {tuple(labels.shape)}')
+    l3 = labels.unsqueeze(0) if labels.dim() == 2 else labels
+    if not _lib.load().wesup_contour_trace_workspace_bytes(*l3.shape, 0):
+        raise _lib.WesupHipError(f'{name}: shape {tuple(l3.shape)} is outside the entry\'s range (B <= 65535, 4 B H W < 2^31)')
+    return l3
+
+
+def contour_count(labels):
+    """labels (H,W) / (B,H,W) int32 -> (B, 2) int32 on the device: the cracks and the corners of every image
+    (contour.count_host).  No read-back."""
+    l3 = _labels_bhw(labels, 'contour_count')
+    B, H, W = l3.shape
+    counts = torch.empty(B, 2, dtype=torch.int32, device=l3.device)
+    nb = _lib.load().wesup_contour_trace_workspace_bytes(B, H, W, 0)
+    ws = workspace(nb, l3.device, 'contour')
+    _lib.call('wesup_contour_count', _p(l3), _p(counts), B, H, W, _p(ws), nb, _stream())
+    return counts
+
+
+def contour_trace(labels):
+    """The boundary rings of a label map, labels (H,W) / (B,H,W) int32 -> (rings (R, 12) int32, verts (V, 2) int32, n_rings (B,)
+    int32) on the device, equal to contour.trace_host.  One read-back of the counts sizes the buffers before the trace; the
+    status word and the ring counts come back together after it (rings is cut to R from them)."""
+    l3 = _labels_bhw(labels, 'contour_trace')
+    B, H, W = l3.shape
+    dev = l3.device
+    tot = contour_count(l3).sum(0, dtype=torch.int64).tolist()               # the read-back
+    n_cracks, n_corners = int(tot[0]), int(tot[1])
+    ring_cap = n_corners // 4
+    rings = torch.empty(max(ring_cap, 1), CONTOUR_RING, dtype=torch.int32, device=dev)
+    verts = torch.empty(max(n_corners, 1), 2, dtype=torch.int32, device=dev)
+    tail = torch.zeros(B + 1, dtype=torch.int32, device=dev)                 # n_rings, then the status word
+    nb = _lib.load().wesup_contour_trace_workspace_bytes(B, H, W, n_cracks)
+    ws = workspace(nb, dev, 'contour')
+    _lib.call('wesup_contour_trace', _p(l3), _p(rings), _p(verts), _p(tail), ctypes.c_void_p(tail.data_ptr() + 4 * B), B, H, W,
+              n_cracks, n_corners, ring_cap, _p(ws), nb, _stream())
+    t = tail.tolist()
+    if t[B] != 0:
+        raise _lib.WesupHipError(f'contour_trace: status {t[B]}: the map changed between the count and the trace')
+    return rings[:sum(t[:B])], verts[:n_corners], tail[:B]
+
+
 def contingency(S, G, nS, nG):
     """Label maps S, G (H,W) / (B,H,W) int32 with labels in [0, nS] / [0, nG] -> (B, nS+1, nG+1) int32 pixel counts (the batch
     axis only for batched input).  Raises when a label lies outside the table or the table would exceed

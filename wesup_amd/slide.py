@@ -503,7 +503,7 @@ def score_directory(output_dir, gt_dir, log=print, device=None, n_classes=2):
 
 
 def main(data_root, checkpoint, model_type='wesup', pixel=False, patch_size=PATCH_SIZE, skip_infer=False, device=None, batch=None,
-         post_threshold=None, log=print, stain_normalize=None, skip_background=None, tissue_masks=None):
+         post_threshold=None, log=print, stain_normalize=None, skip_background=None, tissue_masks=None, geojson=None):
     """test_dp2019_pipeline.py:114-219 without its patch files: predict every slide of ``data_root/images/*.jpg`` (unless
     ``skip_infer``), write the combined PNGs, score them against ``data_root/masks``.  Returns ``score_directory``'s result.
 
@@ -514,7 +514,9 @@ def main(data_root, checkpoint, model_type='wesup', pixel=False, patch_size=PATC
     ``skip_background`` (``True`` or a dict of ``tissue_patches``' parameters): only the tissue patches of a slide
     are predicted, the others are 0 in its map; one log line per slide tells the threshold and how many patches were kept.
     ``tissue_masks``: a directory that gets every slide's tissue mask (255 tissue, 0 glass) as ``<stem>.png``; needs
-    ``skip_background``."""
+    ``skip_background``.
+    ``geojson``: a directory that gets the outlines of every combined map as ``<stem>.geojson``: the objects of
+    the binary map as it is written (after ``post_threshold``), for more than two classes the objects of every class."""
     from PIL import Image
     data_root = Path(data_root).expanduser()
     output_dir = output_dir_for(checkpoint, pixel)
@@ -566,6 +568,10 @@ def main(data_root, checkpoint, model_type='wesup', pixel=False, patch_size=PATC
             if post_threshold is not None:
                 combined = postprocess(combined, post_threshold, device)
             Image.fromarray(combined).save(output_dir / f'{path.stem}.png', format='PNG')
+            if geojson is not None:
+                from . import contour
+                polys = (contour.classmap_polygons(combined, C, device) if C > 2 else contour.mask_polygons(combined, device))
+                contour.write_geojson(Path(geojson).expanduser() / f'{path.stem}.geojson', polys)
         log(f'Combined results saved to {output_dir}.')
     return score_directory(output_dir, data_root / 'masks', log, device if not skip_infer else None, n_classes=C)
 
@@ -589,6 +595,7 @@ def parse_args(argv=None):
     ap.add_argument('--tissue-threshold', default='otsu', metavar='otsu|INT',
                     help="the tissue threshold: Otsu's over the slide (default) or a value in 0 .. 254")
     ap.add_argument('--tissue-masks', default=None, metavar='DIR', help='write the tissue mask PNGs here (with --skip-background)')
+    ap.add_argument('--geojson', default=None, metavar='DIR', help='write the outlines of every combined map here as <stem>.geojson')
     from .stain import add_argument
     add_argument(ap)
     return ap.parse_args(argv)
@@ -602,6 +609,8 @@ def cli(argv=None):
                                     'threshold': a.tissue_threshold if a.tissue_threshold == 'otsu' else int(a.tissue_threshold)}
     if a.tissue_masks is not None:
         extra['tissue_masks'] = a.tissue_masks
+    if a.geojson is not None:
+        extra['geojson'] = a.geojson
     return main(a.data_root, a.checkpoint, model_type=a.model, pixel=a.pixel, patch_size=a.patch_size, skip_infer=a.skip_infer,
                 device=a.device, batch=a.batch, post_threshold=a.post_threshold, **extra,
                 **({} if a.stain_normalize is None else {'stain_normalize': a.stain_normalize}))
