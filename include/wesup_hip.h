@@ -640,6 +640,39 @@ int wesup_contour_count(const int32_t* labels, int32_t* counts, int B, int H, in
 int wesup_contour_trace(const int32_t* labels, int32_t* rings, int32_t* verts, int32_t* n_rings, int32_t* status, int B, int H,
                         int W, int n_cracks, int n_corners, int ring_cap, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------ object measurements (csrc/measure.hip)
+ * Label maps int32 [B][H][W] with labels 0 .. L (0: background); B <= 65535, H, W <= 32768, L + 1 <= 2^20, B (L + 1) <= 2^26.
+ * All integer, equal to wesup_amd/measure.py:measure_host word for word.  Every entry returns WESUP_ERR_INVALID for a null
+ * pointer, a bad shape, a short workspace, negative counts and overlapping operands, on the host and before any launch.
+ *
+ * wesup_measure_limit(which): 0 the labels (L + 1) up to which a block keeps its moment table in LDS, 1
+ * WESUP_MEASURE_HULL_CHUNK, 2 WESUP_MEASURE_WORDS, 3 the largest H / W, 4 the largest L + 1, 5 the largest n_prof; -1 otherwise.
+ *
+ * wesup_measure_workspace_bytes: what a call with a profile capacity of n_prof needs (wesup_measure_profile_count takes
+ * n_prof = 0); 0 for a bad shape.
+ *
+ * wesup_measure_profile_count: count[0] = the sum over the labels present of (rmax - rmin + 2), the lines of pixel corners every
+ * label spans: the profile capacity wesup_object_measure needs; twice that bounds the hull vertices.  status [B] is zeroed,
+ * then bit 0 of an image is set by a label outside [0, L] (skipped, never used as an index).
+ *
+ * wesup_object_measure: d2 NULL or int32 [B][H][W], values >= 0 (a distance map); table [B][L + 1][WESUP_MEASURE_WORDS] int64:
+ * 0 pixels, 1-5 the sums of r, c, r^2, r c, c^2, 6-9 rmin cmin rmax cmax ((H, W, -1, -1) for an absent label, whose other
+ * words are 0; the row of label 0 is 0), 10-12 border pixels of the classes A B C, 13-15 bit quads Q1 Q3 QD, 16 hull area2,
+ * 17 hull vertices, 18 the squared maximum Feret diameter, 19-20 the lattice indices y (W + 1) + x of its pair, 21 the maximum of
+ * d2, 22 the first pixel r W + c that attains it (both 0 without d2), 23 the index of the first hull vertex.  hull_verts
+ * [vert_cap][2] int32 (x, y): the strict vertices of the convex hull of the label's pixel corners, image by image and label
+ * by label, each from its smallest (y, x) down the left side first.  status [B] as above; when the map needs more than n_prof
+ * profile lines or has more than vert_cap hull vertices, bit 1 is set on every image and no word of table or hull_verts is
+ * written.  19 launches whatever the data (9 for n_prof = 0). */
+#define WESUP_MEASURE_WORDS 24
+#define WESUP_MEASURE_HULL_CHUNK 256
+int wesup_measure_limit(int which);
+size_t wesup_measure_workspace_bytes(int B, int H, int W, int L, int n_prof);
+int wesup_measure_profile_count(const int32_t* labels, int64_t* count, int32_t* status, int B, int H, int W, int L, void* ws,
+                                size_t ws_bytes, void* stream);
+int wesup_object_measure(const int32_t* labels, const int32_t* d2, int64_t* table, int32_t* hull_verts, int32_t* status, int B,
+                         int H, int W, int L, int n_prof, int vert_cap, void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------ painted object comparisons (csrc/paint.hip)
  * wesup_object_match: tables [B][nS + 1][nG + 1] as wesup_contingency writes them (nS, nG: the maxima of the batch), nS_dev /
  * nG_dev [B]: each image's own object counts (wesup_cc_label's n_labels); cells outside an image's own counts are not read.

@@ -152,6 +152,11 @@ _SIGS = {
     'wesup_contour_trace_workspace_bytes': (c_size_t, 'iiii'),
     'wesup_contour_count': (c_int, 'pp' + 'iii' + 'pzp'),
     'wesup_contour_trace': (c_int, 'ppppp' + 'iiiiii' + 'pzp'),
+    # object measurements: moments, shape counts, exact hulls (csrc/measure.hip)
+    'wesup_measure_limit': (c_int, 'i'),
+    'wesup_measure_workspace_bytes': (c_size_t, 'iiiii'),
+    'wesup_measure_profile_count': (c_int, 'ppp' + 'iiii' + 'pzp'),
+    'wesup_object_measure': (c_int, 'ppppp' + 'iiiiii' + 'pzp'),
     # painted object comparisons (csrc/paint.hip)
     'wesup_object_match_workspace_bytes': (c_size_t, 'ii'),
     'wesup_object_match': (c_int, 'pppp' + 'iii' + 'pzp'),
@@ -259,6 +264,9 @@ EDT_CHUNK, EDT_COLS = 64, 256      # WESUP_EDT_CHUNK, WESUP_EDT_COLS: the full d
 EDT_SEG, EDT_ROWS = 64, 4          # WESUP_EDT_SEG, WESUP_EDT_ROWS: its row pass, 4 rows of 64 pixels per block
 SURFACE_STATS = 10                 # WESUP_SURFACE_STATS: 8-byte slots of a pair's block
 CONTOUR_RING = 12                  # WESUP_CONTOUR_RING: int32 words of a ring record
+MEASURE_WORDS = 24                 # WESUP_MEASURE_WORDS: int64 words of a label's row
+MEASURE_HULL_CHUNK = 256           # WESUP_MEASURE_HULL_CHUNK: candidates per block of the hull test
+MEASURE_LDS_LABELS = 512           # wesup_measure_limit(0): labels (L + 1) up to which a block keeps its moment table in LDS
 TISSUE_MAX_BLOCKS = 2048           # WESUP_TISSUE_MAX_BLOCKS: the histogram kernel's grid, striding over its items
 TISSUE_ITEM_PIXELS = 8192          # WESUP_TISSUE_ITEM_PIXELS: an item is max(1, this // p) rows of one patch
 TISSUE_LIST_CHUNK = 256            # WESUP_TISSUE_LIST_CHUNK: patches per step of the ordered compaction

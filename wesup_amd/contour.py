@@ -233,9 +233,10 @@ def classmap_polygons(cmap, n_classes, device=None, min_area=0):
     return out
 
 
-def to_geojson(polys, scale=1.0, offset=(0, 0), class_names=None):
+def to_geojson(polys, scale=1.0, offset=(0, 0), class_names=None, measurements=None):
     """A GeoJSON FeatureCollection (a dict): one Polygon feature per object, the outer ring first and then the holes, rings closed
-    and in the direction they were traced; coordinates x * scale + offset[0], y * scale + offset[1]."""
+    and in the direction they were traced; coordinates x * scale + offset[0], y * scale + offset[1].  ``measurements`` maps
+    (image, label) to a feature dict (measure.features), written to ``properties.measurements`` of that object."""
     ox, oy = offset
 
     def ring(p):
@@ -249,16 +250,18 @@ def to_geojson(polys, scale=1.0, offset=(0, 0), class_names=None):
         if 'class' in p:
             k = int(p['class'])
             props['classification'] = {'name': str(class_names[k]) if class_names is not None else f'class {k}'}
+        if measurements is not None and (int(p['image']), int(p['label'])) in measurements:
+            props['measurements'] = measurements[(int(p['image']), int(p['label']))]
         feats.append({'type': 'Feature', 'geometry': {'type': 'Polygon', 'coordinates': [ring(p['outer'])] + [ring(h) for h in p['holes']]},
                       'properties': props})
     return {'type': 'FeatureCollection', 'features': feats}
 
 
-def write_geojson(path, polys, scale=1.0, offset=(0, 0), class_names=None):
+def write_geojson(path, polys, scale=1.0, offset=(0, 0), class_names=None, measurements=None):
     path = Path(path)
     path.parent.mkdir(parents=True, exist_ok=True)
     with open(path, 'w') as f:
-        json.dump(to_geojson(polys, scale, offset, class_names), f)
+        json.dump(to_geojson(polys, scale, offset, class_names, measurements), f)
     return path
 
 

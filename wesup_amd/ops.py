@@ -1641,6 +1641,72 @@ def contour_trace(labels):
     return rings[:sum(t[:B])], verts[:n_corners], tail[:B]
 
 
+# ---------------------------------------------------------------- object measurements (csrc/measure.hip)
+MEASURE_WORDS = _lib.MEASURE_WORDS
+
+
+def measure_limits():
+    """(labels L + 1 up to which a block keeps its moment table in LDS, candidates per block of the hull test)."""
+    lib = _lib.load()
+    return lib.wesup_measure_limit(0), lib.wesup_measure_limit(1)
+
+
+def _measure_args(labels, L, name):
+    _chk(labels, torch.int32, name)
+    if labels.dim() not in (2, 3) or labels.numel() < 1:
+        raise _lib.WesupHipError(f'{name}: expected (H,W) or (B,H,W), got {tuple(labels.shape)}')
+    l3 = labels.unsqueeze(0) if labels.dim() == 2 else labels
+    L = int(L)
+    if not _lib.load().wesup_measure_workspace_bytes(*l3.shape, L, 0):
+        raise _lib.WesupHipError(f'{name}: shape {tuple(l3.shape)} with L = {L} is outside the entry\'s range (B <= 65535, sides '
+                                 'up to 32768, L + 1 <= 2^20, B (L + 1) <= 2^26)')
+    return l3, L
+
+
+def measure_profile_count(labels, L):
+    """labels (H,W) / (B,H,W) int32 -> ((1,) int64 on the device: the lines of pixel corners all labels in 1 .. L span together,
+    the profile capacity of ``object_measure``; status (B,) int32).  No read-back."""
+    l3, L = _measure_args(labels, L, 'measure_profile_count')
+    B, H, W = l3.shape
+    count = torch.empty(1, dtype=torch.int64, device=l3.device)
+    status = torch.empty(B, dtype=torch.int32, device=l3.device)
+    nb = _lib.load().wesup_measure_workspace_bytes(B, H, W, L, 0)
+    ws = workspace(nb, l3.device, 'measure')
+    _lib.call('wesup_measure_profile_count', _p(l3), _p(count), _p(status), B, H, W, L, _p(ws), nb, _stream())
+    return count, status
+
+
+def object_measure(labels, L, d2=None):
+    """Per-label measurements of a label map, labels (H,W) / (B,H,W) int32 with labels 0 .. L, d2 None or an int32 map of the same
+    shape (``edt_sq_full(labels > 0)``) -> (table (B, L+1, 24) int64, hull_verts (V, 2) int32, status (B,) int32) on the device,
+    equal to measure.measure_host.  The call's one read-back, 8 bytes, comes in front: the profile count sizes the workspace, the
+    capacity of hull_verts (twice the count) and the grid.  The status words and the number of vertices (the sum of the table's
+    word 17, to which hull_verts is cut) come back together after the call."""
+    l3, L = _measure_args(labels, L, 'object_measure')
+    B, H, W = l3.shape
+    dev = l3.device
+    if d2 is not None:
+        _chk(d2, torch.int32, 'd2')
+        if d2.numel() != l3.numel() or d2.device != dev:
+            raise _lib.WesupHipError(f'object_measure: d2 {tuple(d2.shape)} for labels {tuple(labels.shape)}')
+    n_prof = int(measure_profile_count(l3, L)[0].item())                      # the read-back
+    if n_prof > _lib.load().wesup_measure_limit(5):
+        raise _lib.WesupHipError(f'object_measure: {n_prof} profile lines')
+    vert_cap = 2 * n_prof
+    table = torch.empty(B, L + 1, MEASURE_WORDS, dtype=torch.int64, device=dev)
+    verts = torch.empty(max(vert_cap, 1), 2, dtype=torch.int32, device=dev)
+    status = torch.empty(B, dtype=torch.int32, device=dev)
+    nb = _lib.load().wesup_measure_workspace_bytes(B, H, W, L, n_prof)
+    ws = workspace(nb, dev, 'measure')
+    _lib.call('wesup_object_measure', _p(l3), _p(d2), _p(table), _p(verts), _p(status), B, H, W, L, n_prof, vert_cap, _p(ws), nb,
+              _stream())
+    short = (status & 2).any()                                                 # (the table is unwritten then: not summed)
+    tail = torch.stack((short.to(torch.int64), torch.where(short, 0, table[:, :, 17].sum()))).tolist()
+    if tail[0]:
+        raise _lib.WesupHipError('object_measure: status 2: the map changed between the count and the measurement')
+    return table, verts[:tail[1]], status
+
+
 def contingency(S, G, nS, nG):
     """Label maps S, G (H,W) / (B,H,W) int32 with labels in [0, nS] / [0, nG] -> (B, nS+1, nG+1) int32 pixel counts (the batch
     axis only for batched input).  Raises when a label lies outside the table or the table would exceed

@@ -503,7 +503,8 @@ def score_directory(output_dir, gt_dir, log=print, device=None, n_classes=2):
 
 
 def main(data_root, checkpoint, model_type='wesup', pixel=False, patch_size=PATCH_SIZE, skip_infer=False, device=None, batch=None,
-         post_threshold=None, log=print, stain_normalize=None, skip_background=None, tissue_masks=None, geojson=None):
+         post_threshold=None, log=print, stain_normalize=None, skip_background=None, tissue_masks=None, geojson=None,
+         measure=None):
     """test_dp2019_pipeline.py:114-219 without its patch files: predict every slide of ``data_root/images/*.jpg`` (unless
     ``skip_infer``), write the combined PNGs, score them against ``data_root/masks``.  Returns ``score_directory``'s result.
 
@@ -516,7 +517,9 @@ def main(data_root, checkpoint, model_type='wesup', pixel=False, patch_size=PATC
     ``tissue_masks``: a directory that gets every slide's tissue mask (255 tissue, 0 glass) as ``<stem>.png``; needs
     ``skip_background``.
     ``geojson``: a directory that gets the outlines of every combined map as ``<stem>.geojson``: the objects of
-    the binary map as it is written (after ``post_threshold``), for more than two classes the objects of every class."""
+    the binary map as it is written (after ``post_threshold``), for more than two classes the objects of every class.
+    ``measure``: a directory that gets the measurements of the same objects as ``<stem>.csv``, one row per object (DESIGN.md
+    3.22)."""
     from PIL import Image
     data_root = Path(data_root).expanduser()
     output_dir = output_dir_for(checkpoint, pixel)
@@ -572,6 +575,13 @@ def main(data_root, checkpoint, model_type='wesup', pixel=False, patch_size=PATC
                 from . import contour
                 polys = (contour.classmap_polygons(combined, C, device) if C > 2 else contour.mask_polygons(combined, device))
                 contour.write_geojson(Path(geojson).expanduser() / f'{path.stem}.geojson', polys)
+            if measure is not None:
+                from . import measure as measure_mod
+                rows = []
+                for k in (range(1, C) if C > 2 else (0,)):
+                    inst = measure_mod._instances(combined == k if C > 2 else combined, device)
+                    rows += measure_mod.object_rows(inst, f'{path.stem}.png', device, k)[0]
+                measure_mod.write_csv(Path(measure).expanduser() / f'{path.stem}.csv', rows)
         log(f'Combined results saved to {output_dir}.')
     return score_directory(output_dir, data_root / 'masks', log, device if not skip_infer else None, n_classes=C)
 
@@ -596,6 +606,7 @@ def parse_args(argv=None):
                     help="the tissue threshold: Otsu's over the slide (default) or a value in 0 .. 254")
     ap.add_argument('--tissue-masks', default=None, metavar='DIR', help='write the tissue mask PNGs here (with --skip-background)')
     ap.add_argument('--geojson', default=None, metavar='DIR', help='write the outlines of every combined map here as <stem>.geojson')
+    ap.add_argument('--measure', default=None, metavar='DIR', help='write the measurements of the objects of every combined map here as <stem>.csv')
     from .stain import add_argument
     add_argument(ap)
     return ap.parse_args(argv)
@@ -611,6 +622,8 @@ def cli(argv=None):
         extra['tissue_masks'] = a.tissue_masks
     if a.geojson is not None:
         extra['geojson'] = a.geojson
+    if a.measure is not None:
+        extra['measure'] = a.measure
     return main(a.data_root, a.checkpoint, model_type=a.model, pixel=a.pixel, patch_size=a.patch_size, skip_infer=a.skip_infer,
                 device=a.device, batch=a.batch, post_threshold=a.post_threshold, **extra,
                 **({} if a.stain_normalize is None else {'stain_normalize': a.stain_normalize}))

@@ -1,6 +1,6 @@
 """Splitting touching objects of a predicted mask: distance seeds, label growth, cuts.
 
-  python -m wesup_amd.split PRED_DIR OUT_DIR --radius R [--gpu] [--labels] [--geojson DIR]
+  python -m wesup_amd.split PRED_DIR OUT_DIR --radius R [--gpu] [--labels] [--geojson DIR] [--measure CSV]
 
 Every object-level metric takes an object to be an 8-connected component of the mask, so two glands whose predictions touch
 count as one.  ``split_objects`` separates them: the pixels whose whole open disc of radius ``radius`` is foreground are the
@@ -145,14 +145,18 @@ def split_objects(mask, radius, device=None, return_labels=False):
     return (out, L) if return_labels else out
 
 
-def split_directory(pred_dir, out_dir, radius, device=None, labels=False, log=print, geojson=None):
+def split_directory(pred_dir, out_dir, radius, device=None, labels=False, log=print, geojson=None, measure=None):
     """Split every 0/255 mask (``*.png``, ``*.bmp``) of ``pred_dir`` into ``out_dir`` (masks x 255; with ``labels`` also the
     instance map -- the 8-connected components of the result in raster order -- as ``<stem>_labels.png``, 16 bit; with
-    ``geojson`` the outlines of the split instances as ``<stem>.geojson`` in that directory)."""
+    ``geojson`` the outlines of the split instances as ``<stem>.geojson`` in that directory; with
+    ``measure`` the measurements of the split instances of all masks as that csv file)."""
     from PIL import Image
     pred_dir, out_dir = Path(pred_dir).expanduser(), Path(out_dir).expanduser()
     out_dir.mkdir(parents=True, exist_ok=True)
     paths = sorted(p for e in ('*.bmp', '*.png') for p in pred_dir.glob(e))
+    rows = []
+    if measure is not None:
+        from . import measure as measure_mod
     for path in paths:
         a = np.asarray(Image.open(path))
         a = a[..., 0] if a.ndim == 3 else a
@@ -167,7 +171,11 @@ def split_directory(pred_dir, out_dir, radius, device=None, labels=False, log=pr
             from . import contour
             contour.write_geojson(Path(geojson).expanduser() / (path.stem + '.geojson'),
                                   contour.polygons(*contour.trace(inst.astype(np.int32), device)[:2]))
+        if measure is not None:
+            rows += measure_mod.object_rows(inst.astype(np.int32), path.name, device)[0]
         log(f'{path.name}: {n_before} -> {int(inst.max())} objects')
+    if measure is not None:
+        measure_mod.write_csv(measure, rows)
     return paths
 
 
@@ -180,13 +188,14 @@ def build_parser():
     ap.add_argument('-d', '--device', default='cuda')
     ap.add_argument('--labels', action='store_true', help='also write the instance maps as 16-bit <stem>_labels.png')
     ap.add_argument('--geojson', default=None, metavar='DIR', help='write the outlines of the split instances here as <stem>.geojson')
+    ap.add_argument('--measure', default=None, metavar='CSV', help='write the measurements of the split instances, one row per object')
     return ap
 
 
 def main(argv=None):
     a = build_parser().parse_args(argv)
     _check_radius(a.radius)
-    split_directory(a.pred_dir, a.out_dir, a.radius, a.device if a.gpu else None, a.labels, geojson=a.geojson)
+    split_directory(a.pred_dir, a.out_dir, a.radius, a.device if a.gpu else None, a.labels, geojson=a.geojson, measure=a.measure)
 
 
 if __name__ == '__main__':
