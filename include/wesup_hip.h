@@ -673,6 +673,41 @@ int wesup_measure_profile_count(const int32_t* labels, int64_t* count, int32_t* 
 int wesup_object_measure(const int32_t* labels, const int32_t* d2, int64_t* table, int32_t* hull_verts, int32_t* status, int B,
                          int H, int W, int L, int n_prof, int vert_cap, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------ polygon fill (csrc/raster.hip)
+ * General polygons in, label maps and class maps out; all integer, equal to wesup_amd/raster.py:fill_host bit for bit.
+ * Coordinates are fixed point with WESUP_RASTER_FRAC_BITS fractional bits: one pixel is 256 units, pixel (r, c) covers
+ * [c, c+1] x [r, r+1] and has its centre at (Xc, Yc) = (256 c + 128, 256 r + 128).  A feature is a list of rings (outer rings,
+ * holes and the parts of a multi-polygon alike), a ring a cyclic list of n >= 1 vertices.  An edge with its ends ordered so that
+ * y0 < y1 counts for a pixel iff y0 <= Yc < y1 and (x1 - x0)(Yc - y0) <= (Xc - x0)(y1 - y0) (int64 products; horizontal edges
+ * never count); a feature covers a pixel iff an odd number of its edges counts (even-odd; tops and left sides inclusive, bottoms
+ * and right sides exclusive); labels [B][H][W] int32 = 1 + the largest index among the features of the image that cover the
+ * pixel, 0 where none does; with values, out8 [B][H][W] uint8 = values[label - 1], 0 where the label is 0.
+ *
+ * Operands in CSR form, device memory: verts [V][2] int32 (x, y), 8-byte aligned; ring_first [R + 1]; feature_first_ring
+ * [F + 1]; feature_image [F]; values [F] uint8 and out8 together or both NULL.  B H W < 2^31, H, W <= 2^21.  verts may be NULL
+ * for V = 0, feature_image and values for F = 0.  WESUP_ERR_INVALID for a null pointer otherwise, a bad shape, negative counts,
+ * a short workspace (wesup_polygon_fill_workspace_bytes(B, H, W, F); 0 for a bad shape) and overlapping operands, on the host
+ * and before any launch.  status[0] is zeroed here; a feature with a vertex outside +-2^28, an image index outside [0, B), ring
+ * offsets that leave [0, R] or decrease, or a ring of it whose vertex offsets leave [0, V] or decrease sets status[0] |= 1 and
+ * paints nothing (nothing behind a refused offset is read).  F = 0 or V = 0 gives a zeroed map.
+ *
+ * Six launches whatever the data, seven with values (F = 0: two, three with values); no read-back: the fill kernel's grid is
+ * fixed and strides over the tiles (WESUP_RASTER_TILE_ROWS x WESUP_RASTER_TILE_COLS pixels, aligned to the image) of the
+ * features' clipped bounding boxes, counted and scanned on the device; feature and tile counts are bounded by no grid limit.
+ * Labels are raised by an integer atomicMax: the result does not depend on the order in which blocks run.
+ *
+ * wesup_raster_limit(which): 0 WESUP_RASTER_TILE_ROWS, 1 WESUP_RASTER_TILE_COLS, 2 WESUP_RASTER_BLOCK (threads that walk a
+ * feature's edges together), 3 the largest |coordinate| (2^28), 4 WESUP_RASTER_FRAC_BITS, 5 the fill kernel's grid; -1 otherwise. */
+#define WESUP_RASTER_FRAC_BITS 8
+#define WESUP_RASTER_TILE_ROWS 64
+#define WESUP_RASTER_TILE_COLS 64
+#define WESUP_RASTER_BLOCK 256
+int wesup_raster_limit(int which);
+size_t wesup_polygon_fill_workspace_bytes(int B, int H, int W, int F);
+int wesup_polygon_fill(const int32_t* verts, const int32_t* ring_first, const int32_t* feature_first_ring,
+                       const int32_t* feature_image, const uint8_t* values, int32_t* labels, uint8_t* out8, int32_t* status, int B,
+                       int H, int W, int F, int R, int V, void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------ painted object comparisons (csrc/paint.hip)
  * wesup_object_match: tables [B][nS + 1][nG + 1] as wesup_contingency writes them (nS, nG: the maxima of the batch), nS_dev /
  * nG_dev [B]: each image's own object counts (wesup_cc_label's n_labels); cells outside an image's own counts are not read.

@@ -157,6 +157,10 @@ _SIGS = {
     'wesup_measure_workspace_bytes': (c_size_t, 'iiiii'),
     'wesup_measure_profile_count': (c_int, 'ppp' + 'iiii' + 'pzp'),
     'wesup_object_measure': (c_int, 'ppppp' + 'iiiiii' + 'pzp'),
+    # polygon fill: fixed-point polygons in CSR form -> label maps and class maps (csrc/raster.hip)
+    'wesup_raster_limit': (c_int, 'i'),
+    'wesup_polygon_fill_workspace_bytes': (c_size_t, 'iiii'),
+    'wesup_polygon_fill': (c_int, 'pppppppp' + 'iiiiii' + 'pzp'),
     # painted object comparisons (csrc/paint.hip)
     'wesup_object_match_workspace_bytes': (c_size_t, 'ii'),
     'wesup_object_match': (c_int, 'pppp' + 'iii' + 'pzp'),
@@ -267,6 +271,10 @@ CONTOUR_RING = 12                  # WESUP_CONTOUR_RING: int32 words of a ring r
 MEASURE_WORDS = 24                 # WESUP_MEASURE_WORDS: int64 words of a label's row
 MEASURE_HULL_CHUNK = 256           # WESUP_MEASURE_HULL_CHUNK: candidates per block of the hull test
 MEASURE_LDS_LABELS = 512           # wesup_measure_limit(0): labels (L + 1) up to which a block keeps its moment table in LDS
+RASTER_FRAC_BITS = 8               # WESUP_RASTER_FRAC_BITS: one pixel is 256 units
+RASTER_TILE_ROWS, RASTER_TILE_COLS = 64, 64     # WESUP_RASTER_TILE_ROWS, WESUP_RASTER_TILE_COLS: the fill kernel's tile
+RASTER_BLOCK = 256                 # WESUP_RASTER_BLOCK: threads that walk a feature's edges together
+RASTER_COORD_MAX = 2 ** 28         # wesup_raster_limit(3): the largest |coordinate| in fixed point
 TISSUE_MAX_BLOCKS = 2048           # WESUP_TISSUE_MAX_BLOCKS: the histogram kernel's grid, striding over its items
 TISSUE_ITEM_PIXELS = 8192          # WESUP_TISSUE_ITEM_PIXELS: an item is max(1, this // p) rows of one patch
 TISSUE_LIST_CHUNK = 256            # WESUP_TISSUE_LIST_CHUNK: patches per step of the ordered compaction

@@ -1641,6 +1641,48 @@ def contour_trace(labels):
     return rings[:sum(t[:B])], verts[:n_corners], tail[:B]
 
 
+# ---------------------------------------------------------------- polygon fill (csrc/raster.hip)
+def polygon_fill(verts, ring_first, feature_first_ring, feature_image, shape, values=None):
+    """Polygons in CSR form, fixed point with 8 fractional bits (raster.pack) -> (labels int32, out8 uint8 or None, status (1,)
+    int32) on the device, equal to raster.fill_host: verts (V, 2), ring_first (R + 1,), feature_first_ring (F + 1,),
+    feature_image (F,) int32 device tensors, ``shape`` (H, W) or (B, H, W), ``values`` (F,) uint8 for the class map.  No
+    read-back: bit 0 of status says that a feature was refused (it paints nothing)."""
+    name = 'polygon_fill'
+    for t, what in ((verts, 'verts'), (ring_first, 'ring_first'), (feature_first_ring, 'feature_first_ring'),
+                    (feature_image, 'feature_image')):
+        _chk(t, torch.int32, f'{name}: {what}')
+    dev = verts.device
+    s = tuple(int(v) for v in shape)
+    if len(s) not in (2, 3):
+        raise _lib.WesupHipError(f'{name}: shape (H, W) or (B, H, W), got {shape}')
+    B, H, W = (1,) + s if len(s) == 2 else s
+    F, R, V = feature_image.numel(), ring_first.numel() - 1, verts.shape[0] if verts.dim() == 2 else -1
+    if V < 0 or verts.shape[1] != 2 or ring_first.dim() != 1 or R < 0 or feature_first_ring.dim() != 1 or \
+            feature_first_ring.numel() != F + 1 or feature_image.dim() != 1:
+        raise _lib.WesupHipError(f'{name}: expected verts (V, 2), ring_first (R + 1,), feature_first_ring (F + 1,), feature_image '
+                                 f'(F,), got {tuple(verts.shape)}, {tuple(ring_first.shape)}, {tuple(feature_first_ring.shape)}, '
+                                 f'{tuple(feature_image.shape)}')
+    if any(t.device != dev for t in (ring_first, feature_first_ring, feature_image)):
+        raise _lib.WesupHipError(f'{name}: the operands lie on different devices')
+    nb = _lib.load().wesup_polygon_fill_workspace_bytes(B, H, W, F)
+    if not nb:
+        raise _lib.WesupHipError(f'{name}: shape {(B, H, W)} is outside the entry\'s range (B H W < 2^31, H, W <= 2^21)')
+    out8 = None
+    if values is not None:
+        _chk(values, torch.uint8, f'{name}: values')
+        if values.shape != (F,) or values.device != dev:
+            raise _lib.WesupHipError(f'{name}: values {tuple(values.shape)} on {values.device}, expected ({F},) on {dev}')
+        out8 = torch.empty(B, H, W, dtype=torch.uint8, device=dev)
+    labels = torch.empty(B, H, W, dtype=torch.int32, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    ws = workspace(nb, dev, 'raster')
+    _lib.call('wesup_polygon_fill', _p(verts), _p(ring_first), _p(feature_first_ring), _p(feature_image), _p(values), _p(labels),
+              _p(out8), _p(status), B, H, W, F, R, V, _p(ws), nb, _stream())
+    if len(s) == 2:
+        labels, out8 = labels[0], (None if out8 is None else out8[0])
+    return labels, out8, status
+
+
 # ---------------------------------------------------------------- object measurements (csrc/measure.hip, DESIGN.md 3.22)
 MEASURE_WORDS = _lib.MEASURE_WORDS
 
