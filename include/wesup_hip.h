@@ -640,6 +640,23 @@ int wesup_contour_count(const int32_t* labels, int32_t* counts, int B, int H, in
 int wesup_contour_trace(const int32_t* labels, int32_t* rings, int32_t* verts, int32_t* n_rings, int32_t* status, int B, int H,
                         int W, int n_cracks, int n_corners, int ring_cap, void* ws, size_t ws_bytes, void* stream);
 
+/* Ring simplification: the exact integer Douglas-Peucker of wesup_amd/contour.py:simplify_host, word for word.
+ * rings [R][WESUP_CONTOUR_RING] and verts [V][2] as wesup_contour_trace leaves them: every ring of at least one vertex, the vertex
+ * ranges consecutive from 0 to V in ring order; tol_q4 the tolerance in sixteenths of a pixel, 0 .. WESUP_SIMPLIFY_TOL_MAX.
+ * rings_out [R] records (image, label, cracks and leader slot as given; first vertex, vertices, bounding box and area2 of the kept
+ * vertices), verts_out of capacity V, flags [R] (bit 0: emitted as traced because fewer than 3 vertices were left or area2 lost
+ * its sign; bit 1: emitted as traced because the record's bounding box spans 32768 or more), counts [WESUP_SIMPLIFY_COUNTS]:
+ * kept vertices, rings with flag 1, rings with flag 2, status.  Records whose ranges are not as above set status = 1, and no
+ * vertex, record or flag is written.  WESUP_ERR_INVALID on the host and before any launch for a null pointer, negative sizes,
+ * R > V, V > 2^28, tol_q4 out of range, a short workspace, overlapping operands and rings / rings_out that are not 8-byte
+ * aligned.  Seven launches whatever the data (two when R = 0); the level loop runs inside one kernel, at most n levels for a
+ * ring of n vertices.  No floating point; integer atomics only, so two runs give the same words. */
+#define WESUP_SIMPLIFY_TOL_MAX 4096
+#define WESUP_SIMPLIFY_COUNTS 4
+size_t wesup_contour_simplify_workspace_bytes(int R, int V);
+int wesup_contour_simplify(const int32_t* rings, int R, const int32_t* verts, int V, int tol_q4, int32_t* rings_out,
+                           int32_t* verts_out, int32_t* flags, int32_t* counts, void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------ object measurements (csrc/measure.hip)
  * Label maps int32 [B][H][W] with labels 0 .. L (0: background); B <= 65535, H, W <= 32768, L + 1 <= 2^20, B (L + 1) <= 2^26.
  * All integer, equal to wesup_amd/measure.py:measure_host word for word.  Every entry returns WESUP_ERR_INVALID for a null

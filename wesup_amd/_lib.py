@@ -152,6 +152,9 @@ _SIGS = {
     'wesup_contour_trace_workspace_bytes': (c_size_t, 'iiii'),
     'wesup_contour_count': (c_int, 'pp' + 'iii' + 'pzp'),
     'wesup_contour_trace': (c_int, 'ppppp' + 'iiiiii' + 'pzp'),
+    # ... and their exact simplification
+    'wesup_contour_simplify_workspace_bytes': (c_size_t, 'ii'),
+    'wesup_contour_simplify': (c_int, 'pipii' + 'pppp' + 'pzp'),
     # object measurements: moments, shape counts, exact hulls (csrc/measure.hip)
     'wesup_measure_limit': (c_int, 'i'),
     'wesup_measure_workspace_bytes': (c_size_t, 'iiiii'),
@@ -268,6 +271,8 @@ EDT_CHUNK, EDT_COLS = 64, 256      # WESUP_EDT_CHUNK, WESUP_EDT_COLS: the full d
 EDT_SEG, EDT_ROWS = 64, 4          # WESUP_EDT_SEG, WESUP_EDT_ROWS: its row pass, 4 rows of 64 pixels per block
 SURFACE_STATS = 10                 # WESUP_SURFACE_STATS: 8-byte slots of a pair's block
 CONTOUR_RING = 12                  # WESUP_CONTOUR_RING: int32 words of a ring record
+SIMPLIFY_TOL_MAX = 4096            # WESUP_SIMPLIFY_TOL_MAX: sixteenths of a pixel
+SIMPLIFY_COUNTS = 4                # WESUP_SIMPLIFY_COUNTS: kept vertices, rings flagged 1, rings flagged 2, status
 MEASURE_WORDS = 24                 # WESUP_MEASURE_WORDS: int64 words of a label's row
 MEASURE_HULL_CHUNK = 256           # WESUP_MEASURE_HULL_CHUNK: candidates per block of the hull test
 MEASURE_LDS_LABELS = 512           # wesup_measure_limit(0): labels (L + 1) up to which a block keeps its moment table in LDS

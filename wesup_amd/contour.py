@@ -1,6 +1,6 @@
 """Object outlines: exact boundary rings of a label map, polygons with holes, GeoJSON.
 
-  python -m wesup_amd.contour PRED_DIR OUT_DIR [--gpu] [--labels] [--classes C] [--min-area A] [--scale S]
+  python -m wesup_amd.contour PRED_DIR OUT_DIR [--gpu] [--labels] [--classes C] [--min-area A] [--scale S] [--simplify PX]
 
 Pixel (r, c) covers [c, c+1] x [r, r+1]; vertices are integer pixel corners (x, y), y downwards.  A *crack* is a unit edge between
 a pixel of label l > 0 and a 4-neighbour whose label differs or that lies outside the image, directed with its pixel on the left
@@ -20,7 +20,10 @@ whose direction differs from their predecessor's, from the leader on, and area2 
 positive for outer rings (counter-clockwise on screen) and negative for holes.
 
 ``trace_host`` is this definition, a sequential tracer in plain Python; the device path (csrc/contour.hip, ``ops.contour_trace``)
-is held to it word for word."""
+is held to it word for word.
+
+Simplification is opt-in: ``simplify_host`` is an exact integer Douglas-Peucker over the traced rings, the device
+path (``ops.contour_simplify``) is held to it word for word, and ``simplify=PX`` / ``--simplify PX`` put it under the exports."""
 import argparse
 import json
 from pathlib import Path
@@ -191,6 +194,244 @@ def polygons(rings, verts):
     return out
 
 
+# ---------------------------------------------------------------- simplification
+SIMPLIFY_TOL_MAX = 4096                      # sixteenths of a pixel: 256 px
+SIMPLIFY_SPAN = 32768                        # a ring whose bounding box spans this or more is emitted as traced (flag 2)
+FLAG_ORIENTATION, FLAG_OVERSIZE = 1, 2
+_M64 = (1 << 64) - 1
+
+
+def _wrap64(v):
+    v &= _M64
+    return v - (1 << 64) if v >> 63 else v
+
+
+def _area2_points(x, y):
+    n = len(x)
+    return _wrap64(-sum(x[i] * y[(i + 1) % n] - x[(i + 1) % n] * y[i] for i in range(n)))
+
+
+def _kept_of_ring(x, y, tol2):
+    """The kept indices of one ring of n > 4 vertices (Python integer lists), ascending: the anchors and every split point."""
+    n = len(x)
+    x0, y0 = x[0], y[0]
+    a1, far = 0, 0
+    for k in range(n):
+        d = (x[k] - x0) ** 2 + (y[k] - y0) ** 2
+        if d > far:
+            a1, far = k, d
+    keep = {0, a1}
+    stack = [(0, a1), (a1, n)]                # positions along the ring, n standing for vertex 0 again
+    while stack:
+        lo, hi = stack.pop()
+        if hi - lo < 2:
+            continue
+        ax, ay = x[lo], y[lo]
+        bx, by = x[hi % n], y[hi % n]
+        ux, uy = bx - ax, by - ay
+        L = ux * ux + uy * uy
+        best, bkey, m = -1, 0, -1
+        for k in range(lo + 1, hi):
+            px, py = x[k] - ax, y[k] - ay
+            if L == 0:
+                D = px * px + py * py
+            else:
+                t = px * ux + py * uy
+                if t <= 0:
+                    D = (px * px + py * py) * L
+                elif t >= L:
+                    D = ((x[k] - bx) ** 2 + (y[k] - by) ** 2) * L
+                else:
+                    c = px * uy - py * ux
+                    D = c * c
+            key = abs(2 * k - lo - hi)
+            if D > best or (D == best and key < bkey):        # k ascends: among equal (D, key) the smallest k stays
+                best, bkey, m = D, key, k
+        if best > (tol2 * (L if L else 1)) >> 8:
+            keep.add(m)
+            stack.append((lo, m))
+            stack.append((m, hi))
+    return sorted(keep)
+
+
+def simplify_host(rings, verts, tol_q4):
+    """Exact Douglas-Peucker of traced rings: ring records (R, 12) and vertices (V, 2) as ``trace_host`` returns
+    them, ``tol_q4`` the tolerance in sixteenths of a pixel (an integer, 0 .. 4096) -> (rings2 (R, 12) int32, verts2 (V2, 2)
+    int32, flags (R,) int32).  Rings and vertices stay in order, the kept vertices are a subsequence of every ring's; image, label,
+    cracks and leader slot stay as traced, first vertex, vertex count, bounding box and area2 are those of the kept vertices.
+
+    A ring of n <= 4 vertices is emitted as it is; one whose record's bounding box spans 32768 or more as it is with flag 2.
+    Otherwise the anchors are vertex 0 and the vertex farthest from it (the smallest index among equals), and a piece between kept
+    positions lo < hi splits at the position m of the largest D (squared distance to the segment, times L = |b - a|^2; among
+    equals the smallest |2k - lo - hi|, then the smallest k) iff 256 D(m) > tol_q4^2 L.  A ring left with fewer than 3 vertices or
+    with an area2 that is zero or of the other sign is emitted as traced with flag 1.  Plain Python integers, an explicit stack."""
+    if int(tol_q4) != tol_q4 or not 0 <= int(tol_q4) <= SIMPLIFY_TOL_MAX:
+        raise ValueError(f'tol_q4 {tol_q4}: an integer in 0 .. {SIMPLIFY_TOL_MAX}')
+    tol2 = int(tol_q4) ** 2
+    rings = np.asarray(rings, np.int32).reshape(-1, RING)
+    verts = np.asarray(verts, np.int32).reshape(-1, 2)
+    V = len(verts)
+    out = rings.copy()
+    flags = np.zeros(len(rings), np.int32)
+    a2 = area2_of(rings).tolist()
+    chunks, nv, expect = [np.zeros((0, 2), np.int32)], 0, 0
+    for i, rec in enumerate(rings.tolist()):
+        fv, n = rec[2], rec[3]
+        if fv != expect or n < 1 or fv + n > V:
+            raise ValueError(f'ring {i}: vertices {fv} .. {fv + n} do not follow ring {i - 1} inside 0 .. {V}')
+        expect = fv + n
+        x, y = verts[fv:fv + n, 0].tolist(), verts[fv:fv + n, 1].tolist()
+        kept = list(range(n))
+        if n > 4:
+            if rec[7] - rec[5] >= SIMPLIFY_SPAN or rec[8] - rec[6] >= SIMPLIFY_SPAN:
+                flags[i] |= FLAG_OVERSIZE
+            else:
+                k2 = _kept_of_ring(x, y, tol2)
+                s = _area2_points([x[k] for k in k2], [y[k] for k in k2]) if len(k2) >= 3 else 0
+                if len(k2) < 3 or s == 0 or (s > 0) != (a2[i] > 0) or a2[i] == 0:
+                    flags[i] |= FLAG_ORIENTATION
+                else:
+                    kept = k2
+        kx, ky = [x[k] for k in kept], [y[k] for k in kept]
+        lo, hi = np.array([_area2_points(kx, ky)], '<i8').view('<i4')
+        out[i, 2], out[i, 3] = nv, len(kept)
+        out[i, 5:9] = (min(kx), min(ky), max(kx), max(ky))
+        out[i, 10], out[i, 11] = lo, hi
+        chunks.append(verts[fv:fv + n][kept])
+        nv += len(kept)
+    if expect != V:
+        raise ValueError(f'the rings hold {expect} vertices, verts {V}')
+    return out, np.concatenate(chunks).astype(np.int32).reshape(-1, 2), flags
+
+
+def _tol_q4(tolerance_px):
+    t = float(tolerance_px)
+    if not 0 <= t <= SIMPLIFY_TOL_MAX / 16:
+        raise ValueError(f'simplify tolerance {tolerance_px}: 0 .. {SIMPLIFY_TOL_MAX // 16} pixels')
+    return int(round(16 * t))
+
+
+def simplify(rings, verts, tolerance_px, device=None):
+    """``simplify_host`` at tol_q4 = round(16 tolerance_px), or with ``device`` the same from the GPU (ops.contour_simplify);
+    numpy arrays either way: (rings2, verts2, flags)."""
+    tol = _tol_q4(tolerance_px)
+    if device is None:
+        return simplify_host(rings, verts, tol)
+    import torch
+    from . import ops
+    dev = torch.device(device)
+    with torch.cuda.device(dev):
+        r = torch.as_tensor(np.ascontiguousarray(np.asarray(rings, np.int32).reshape(-1, RING))).to(dev)
+        v = torch.as_tensor(np.ascontiguousarray(np.asarray(verts, np.int32).reshape(-1, 2))).to(dev)
+        return tuple(t.cpu().numpy() for t in ops.contour_simplify(r, v, tol)[:3])
+
+
+def _per_label(before, after):
+    per = {}
+    for arr in (before, after):
+        ls, cs = np.unique(arr[arr > 0], return_counts=True)
+        for l, c in zip(ls.tolist(), cs.tolist()):
+            per[l] = per.get(l, 0) + c
+    return per
+
+
+def _change_device(lab3, rings2, verts2):
+    """``simplify_change`` on device tensors: lab3 (B, H, W) int32 with nothing below 0."""
+    import torch
+    from . import ops, raster
+    if rings2.shape[0]:
+        fv, rf, ffr, fimg, flab = raster.rings_to_csr(rings2, verts2)
+        filled = ops.polygon_fill(fv, rf, ffr, fimg, tuple(lab3.shape))[0]
+        after = torch.cat([torch.zeros(1, dtype=torch.int32, device=lab3.device), flab])[filled.long()]
+    else:
+        after = torch.zeros_like(lab3)
+    diff = after != lab3
+    return int(diff.sum().item()), _per_label(lab3[diff].cpu().numpy().astype(np.int64), after[diff].cpu().numpy().astype(np.int64))
+
+
+def simplify_change(labels, rings2, verts2, device=None):
+    """What a simplification changed: the simplified polygons filled back (one feature per (image, label), later features over
+    earlier ones) against ``labels`` (H,W) / (B,H,W) -> (the number of pixels whose label differs, {label: pixels that the label
+    lost or gained}).  ``raster.fill_host`` on the host, ``raster.rings_to_csr`` and ``ops.polygon_fill`` with ``device``."""
+    from . import raster
+    L = _labels3(labels)
+    L = np.where(L > 0, L, 0)
+    rings2 = np.asarray(rings2, np.int32).reshape(-1, RING)
+    verts2 = np.asarray(verts2, np.int32).reshape(-1, 2)
+    if device is not None:
+        import torch
+        dev = torch.device(device)
+        with torch.cuda.device(dev):
+            return _change_device(torch.as_tensor(L.astype(np.int32)).to(dev), torch.as_tensor(rings2).to(dev),
+                                  torch.as_tensor(verts2).to(dev))
+    key = (rings2[:, 0].astype(np.int64) << 32) | (rings2[:, 1].astype(np.int64) & 0xffffffff)
+    order = np.argsort(key, kind='stable')
+    n = rings2[order, 3].astype(np.int64)
+    ring_first = np.concatenate([[0], np.cumsum(n)]).astype(np.int32)
+    src, _ = raster._ranges(rings2[order, 2].astype(np.int64), n)
+    k, counts = np.unique(key[order], return_counts=True)
+    ffr = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+    filled = raster.fill_host(verts2[src] * raster.ONE, ring_first, ffr, (k >> 32).astype(np.int32), L.shape)[0]
+    after = np.concatenate([[0], (k & 0xffffffff).astype(np.int64)])[filled]
+    diff = after != L
+    return int(diff.sum()), _per_label(L[diff], after[diff])
+
+
+def _traced_and_simplified(lab, device, tolerance_px, stats):
+    """(rings, verts, rings2, verts2) of an instance map as numpy arrays; with ``device`` the map, the rings and the fill-back stay
+    on the GPU (ops.contour_trace, ops.contour_simplify, ops.polygon_fill).  ``stats`` collects the counts of ``simplify_log``."""
+    tol = _tol_q4(tolerance_px)
+    if device is None:
+        lab = np.asarray(lab)
+        r, v = trace_host(lab)[:2]
+        r2, v2, fl = simplify_host(r, v, tol)
+        changed = simplify_change(lab, r2, v2)[0] if stats is not None else 0
+    else:
+        import torch
+        from . import ops
+        dev = torch.device(device)
+        with torch.cuda.device(dev):
+            t = lab if isinstance(lab, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(np.asarray(lab).astype(np.int32))).to(dev)
+            rt, vt, _ = ops.contour_trace(t)
+            r2t, v2t, flt, _ = ops.contour_simplify(rt, vt, tol)
+            t3 = t.clamp(min=0).reshape((-1,) + tuple(t.shape[-2:]))
+            changed = _change_device(t3, r2t, v2t)[0] if stats is not None else 0
+            r, v, r2, v2, fl = (x.cpu().numpy() for x in (rt, vt, r2t, v2t, flt))
+    if stats is not None:
+        for k, n in (('vertices', len(v)), ('kept', len(v2)), ('flag1', int((fl & FLAG_ORIENTATION != 0).sum())),
+                     ('flag2', int((fl & FLAG_OVERSIZE != 0).sum())), ('changed', changed)):
+            stats[k] = stats.get(k, 0) + n
+    return r, v, r2, v2
+
+
+def label_polygons(lab, device=None, min_area=0, simplify=None, stats=None):
+    """The polygons of an instance map (H, W) in which every label is one 8-connected object.  ``simplify``: a tolerance in pixels
+    (DESIGN.md 3.24); area_px / perimeter_px / bbox stay those of the traced object, ``simplified_area2`` (the area2 of the
+    simplified rings, holes counting negative) and ``simplify_px`` are added.  ``stats``: a dict that collects vertices, kept,
+    flag1, flag2 and changed (``simplify_change``) for ``simplify_log``."""
+    if simplify is None:
+        return [p for p in polygons(*trace(np.asarray(lab).astype(np.int32), device)[:2]) if p['area_px'] >= min_area]
+    r, v, r2, v2 = _traced_and_simplified(lab, device, simplify, stats)
+    traced = {(p['image'], p['label']): p for p in polygons(r, v)}
+    a2 = {}
+    for rec, a in zip(r2.tolist(), area2_of(r2).tolist()):
+        a2[(rec[0], rec[1])] = a2.get((rec[0], rec[1]), 0) + a
+    out = []
+    for p in polygons(r2, v2):
+        t = traced[(p['image'], p['label'])]
+        if t['area_px'] < min_area:
+            continue
+        p.update(area_px=t['area_px'], perimeter_px=t['perimeter_px'], bbox=t['bbox'],
+                 simplified_area2=int(a2[(p['image'], p['label'])]), simplify_px=float(simplify))
+        out.append(p)
+    return out
+
+
+def simplify_log(stats, simplify):
+    return (f"simplify {simplify} px: {stats.get('vertices', 0)} -> {stats.get('kept', 0)} vertices, {stats.get('flag1', 0)} rings "
+            f"kept for their orientation, {stats.get('flag2', 0)} oversize, {stats.get('changed', 0)} pixels change on fill-back")
+
+
 def _components(mask, device):
     m = np.asarray(mask) != 0
     if m.ndim != 2:
@@ -204,10 +445,12 @@ def _components(mask, device):
         return ops.cc_label(t, 8)[0], t.device
 
 
-def mask_polygons(mask, device=None, min_area=0):
+def mask_polygons(mask, device=None, min_area=0, simplify=None, stats=None):
     """The objects of a binary mask (H, W), 8-connected (``cc_label(..., 8)``), as polygons with holes; objects of fewer than
-    ``min_area`` pixels are dropped.  With ``device`` labelling and tracing run on the GPU."""
+    ``min_area`` pixels are dropped.  With ``device`` labelling and tracing run on the GPU.  ``simplify``: see ``label_polygons``."""
     lab, dev = _components(mask, device)
+    if simplify is not None:
+        return label_polygons(lab, device, min_area, simplify, stats)            # (with a device the labels stay there)
     if dev is None:
         r, v, _ = trace_host(lab)
     else:
@@ -218,7 +461,7 @@ def mask_polygons(mask, device=None, min_area=0):
     return [p for p in polygons(r, v) if p['area_px'] >= min_area]
 
 
-def classmap_polygons(cmap, n_classes, device=None, min_area=0):
+def classmap_polygons(cmap, n_classes, device=None, min_area=0, simplify=None, stats=None):
     """The objects of every class 1 .. n_classes - 1 of a class-index map (H, W), each polygon carrying its ``class``; labels
     number the objects of their class."""
     cmap = np.asarray(cmap)
@@ -227,7 +470,8 @@ def classmap_polygons(cmap, n_classes, device=None, min_area=0):
         raise ValueError(f'n_classes {n_classes}: at least 2')
     out = []
     for k in range(1, n_classes):
-        for p in mask_polygons(cmap == k, device, min_area):
+        for p in (mask_polygons(cmap == k, device, min_area) if simplify is None else
+                  mask_polygons(cmap == k, device, min_area, simplify, stats)):
             p['class'] = k
             out.append(p)
     return out
@@ -250,6 +494,9 @@ def to_geojson(polys, scale=1.0, offset=(0, 0), class_names=None, measurements=N
         if 'class' in p:
             k = int(p['class'])
             props['classification'] = {'name': str(class_names[k]) if class_names is not None else f'class {k}'}
+        if 'simplify_px' in p:
+            props['simplified_area2'] = int(p['simplified_area2'])
+            props['simplify_px'] = float(p['simplify_px'])
         if measurements is not None and (int(p['image']), int(p['label'])) in measurements:
             props['measurements'] = measurements[(int(p['image']), int(p['label']))]
         feats.append({'type': 'Feature', 'geometry': {'type': 'Polygon', 'coordinates': [ring(p['outer'])] + [ring(h) for h in p['holes']]},
@@ -278,9 +525,10 @@ def geojson_to_mask_host(doc, shape, scale=1.0, offset=(0, 0)):
     return _fill(T, H, W)
 
 
-def export_directory(pred_dir, out_dir, device=None, labels=False, classes=0, min_area=0, scale=1.0, log=print):
+def export_directory(pred_dir, out_dir, device=None, labels=False, classes=0, min_area=0, scale=1.0, log=print, simplify=None):
     """``<stem>.geojson`` in ``out_dir`` for every ``*.png`` / ``*.bmp`` of ``pred_dir``: binary masks (any non-zero) by default,
-    16-bit instance maps with ``labels``, class-index maps with ``classes`` = C."""
+    16-bit instance maps with ``labels``, class-index maps with ``classes`` = C.  ``simplify``: a tolerance in pixels (DESIGN.md
+    3.24); the vertex counts, the flagged rings and the pixels that change on fill-back are logged per file."""
     from PIL import Image
     pred_dir, out_dir = Path(pred_dir).expanduser(), Path(out_dir).expanduser()
     out_dir.mkdir(parents=True, exist_ok=True)
@@ -288,14 +536,22 @@ def export_directory(pred_dir, out_dir, device=None, labels=False, classes=0, mi
     for path in paths:
         a = np.asarray(Image.open(path))
         a = a[..., 0] if a.ndim == 3 else a
-        if labels:
-            polys = [p for p in polygons(*trace(a.astype(np.int32), device)[:2]) if p['area_px'] >= min_area]
+        stats = {}
+        if simplify is None:
+            if labels:
+                polys = [p for p in polygons(*trace(a.astype(np.int32), device)[:2]) if p['area_px'] >= min_area]
+            elif classes:
+                polys = classmap_polygons(a, classes, device, min_area)
+            else:
+                polys = mask_polygons(a, device, min_area)
+        elif labels:
+            polys = label_polygons(a, device, min_area, simplify, stats)
         elif classes:
-            polys = classmap_polygons(a, classes, device, min_area)
+            polys = classmap_polygons(a, classes, device, min_area, simplify, stats)
         else:
-            polys = mask_polygons(a, device, min_area)
+            polys = mask_polygons(a, device, min_area, simplify, stats)
         write_geojson(out_dir / (path.stem + '.geojson'), polys, scale)
-        log(f'{path.name}: {len(polys)} polygons')
+        log(f'{path.name}: {len(polys)} polygons' + ('' if simplify is None else '; ' + simplify_log(stats, simplify)))
     return paths
 
 
@@ -309,6 +565,7 @@ def build_parser():
     ap.add_argument('--classes', type=int, default=0, help='the inputs are class-index maps of this many classes')
     ap.add_argument('--min-area', type=int, default=0, help='drop objects of fewer pixels')
     ap.add_argument('--scale', type=float, default=1.0, help='slide pixels per mask pixel')
+    ap.add_argument('--simplify', type=float, default=None, metavar='PX', help='simplify every ring within this many pixels (exact Douglas-Peucker, DESIGN.md 3.24)')
     return ap
 
 
@@ -316,7 +573,7 @@ def main(argv=None):
     a = build_parser().parse_args(argv)
     if a.labels and a.classes:
         raise SystemExit('--labels and --classes exclude each other')
-    export_directory(a.pred_dir, a.out_dir, a.device if a.gpu else None, a.labels, a.classes, a.min_area, a.scale)
+    export_directory(a.pred_dir, a.out_dir, a.device if a.gpu else None, a.labels, a.classes, a.min_area, a.scale, simplify=a.simplify)
 
 
 if __name__ == '__main__':

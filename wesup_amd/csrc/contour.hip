@@ -28,6 +28,15 @@
 //   ct_place_kernel    ring order: the crack of every place, the corner flag of every place; the leaders start their records
 //   sc_block_sums, sc_small, sc_apply    vertex indices: the scan of the corner flags in ring order
 //   ct_emit_kernel     one thread per place: vertices, bounding boxes, areas; a wave inside one ring folds first
+//
+// wesup_contour_simplify, seven launches whatever the data: the exact Douglas-Peucker of contour.py:simplify_host
+//   fill (counts), sp_validate_kernel (the records' vertex ranges; every later kernel is a no-op unless they are consecutive)
+//   sp_simplify_kernel one block per ring, the blocks striding over the rings: anchors, then level after level every vertex of a
+//                      live piece measures itself against the piece's chord, the piece's maximum by a 64-bit atomicMax, the tie
+//                      rule by a 64-bit atomicMin, split or retire; the live vertices are kept as a compact list, so a level
+//                      costs what is still live.  State in LDS up to SP_LDS_N vertices, in the workspace above.
+//   sc_block_sums, sc_small, sc_apply    the scan of the keep flags: the output index of every kept vertex
+//   sp_emit_kernel     kept vertices to their places, every record's first vertex, the total
 #include "common.hpp"
 
 #define CT_SCAN 1024
@@ -480,6 +489,367 @@ extern "C" int wesup_contour_trace(const int32_t* labels, int32_t* rings, int32_
         WESUP_LAUNCH(ct_emit_kernel, dim3(gc), dim3(CT_BLOCK), 0, st, (const int32_t*)hdr, fin, (const int32_t*)slot,
                      (const u64*)rk, (const int32_t*)ord, (const u64*)cf, (const uint8_t*)maskb, rings, verts, HW, W, n, n_corners,
                      ring_cap);
+    }
+    WESUP_CHECK_LAUNCH();
+    return WESUP_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- simplification
+#define SP_BLOCK 1024
+#define SP_LDS_N 896                    // vertices of a ring whose state lives in LDS: 64 bytes each, 56 KiB of the 64 KiB a block may declare
+#define SP_MAX_BLOCKS 1024
+#define SP_HDR_WORDS 64                 // words 0 ok; the 8-byte total of kept vertices at word 2
+#define SP_SPAN 32768
+#define SP_NONE 0xffffffffffffffffull
+
+namespace {
+
+// one block, striding over the records: first vertices consecutive from 0 to V, every ring of at least one vertex
+__global__ __launch_bounds__(SP_BLOCK) void sp_validate_kernel(const int32_t* __restrict__ rings, int R, int V,
+                                                               int32_t* __restrict__ hdr, int32_t* __restrict__ counts) {
+    __shared__ int bad;
+    if (threadIdx.x == 0) bad = 0;
+    __syncthreads();
+    int b = 0;
+    for (int r = threadIdx.x; r < R; r += SP_BLOCK) {
+        const long fv = rings[(long)r * CT_RING + 2], n = rings[(long)r * CT_RING + 3];
+        const long prev = r ? (long)rings[(long)(r - 1) * CT_RING + 2] + rings[(long)(r - 1) * CT_RING + 3] : 0l;
+        if (n < 1 || fv < 0 || fv + n > V || fv != prev) b = 1;
+        if (r == R - 1 && fv + n != V) b = 1;
+    }
+    if (b) atomicOr(&bad, 1);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        hdr[0] = bad ? 0 : 1;
+        hdr[2] = 0;
+        hdr[3] = 0;
+        if (bad) counts[3] = 1;
+    }
+}
+
+// a ring's state, in LDS or in the workspace: the code below is the same
+struct SpState {
+    const int32_t* px;                  // x at px[stride * k], y at py[stride * k]
+    const int32_t* py;
+    int stride;
+    int32_t *lo, *hi;                   // per vertex: the ends of its piece, positions 0 .. n (n is vertex 0 again)
+    u64 *best, *tie;                    // per piece, at its lo: the largest D; (|2k - lo - hi| << 32) | k of the winner
+    int32_t* list;                      // the live vertices
+    long par;                           // best, tie and list of the odd levels lie this many elements behind those of the even ones
+    u64* dl;                            // D of the live vertex at this place of the list
+};
+
+struct SpShared {
+    u64 akey, area_all, area_k;
+    int bb_all[4], bb_k[4];
+    int nkept, nact[2];
+};
+
+__device__ __forceinline__ u64 sp_cross(int xa, int ya, int xb, int yb) {               // one term of area2: -(xa yb - xb ya)
+    return (u64)(-((long long)xa * yb - (long long)xb * ya));
+}
+
+__device__ __forceinline__ void sp_ring(const SpState S, SpShared& sh, int n, u64 tol2, u64* __restrict__ keep) {
+    const int tid = threadIdx.x;
+    const int a1 = (int)(0xffffffffu - (unsigned)sh.akey);                              // (read after the caller's barrier)
+    // pieces 0 .. a1 and a1 .. n; every other vertex is live
+    for (int k = tid; k < n; k += SP_BLOCK) {
+        const bool anchor = k == 0 || k == a1;
+        keep[k] = anchor ? 1ull : 0ull;
+        if (anchor) {
+            S.best[k] = 0;
+            S.tie[k] = SP_NONE;
+        } else {
+            S.lo[k] = k < a1 ? 0 : a1;
+            S.hi[k] = k < a1 ? a1 : n;
+            S.list[k - 1 - (k > a1 && a1 > 0)] = k;
+        }
+    }
+    if (tid == 0) {
+        sh.nact[0] = n - 1 - (a1 > 0);
+        sh.nact[1] = 0;
+        sh.nkept = 1 + (a1 > 0);
+        sh.area_k = 0;
+        const int x0 = S.px[0], y0 = S.py[0], x1 = S.px[(long)S.stride * a1], y1 = S.py[(long)S.stride * a1];
+        sh.bb_k[0] = min(x0, x1); sh.bb_k[1] = min(y0, y1); sh.bb_k[2] = max(x0, x1); sh.bb_k[3] = max(y0, y1);
+    }
+    __syncthreads();
+    int p = 0;
+    // at most n levels: a level with live vertices keeps at least one more vertex or retires them all, and ends the loop then
+    for (int level = 0; level < n; ++level, p ^= 1) {
+        const int cnt = sh.nact[p];
+        if (cnt == 0) break;
+        const int32_t* lst = S.list + p * S.par;
+        u64 *best = S.best + p * S.par, *tie = S.tie + p * S.par;
+        u64 *best_n = S.best + (p ^ 1) * S.par, *tie_n = S.tie + (p ^ 1) * S.par;
+        int32_t* lst_n = S.list + (p ^ 1) * S.par;
+        for (int i0 = 0; i0 < cnt; i0 += SP_BLOCK) {
+            const int i = i0 + tid;
+            const bool valid = i < cnt;
+            int l = -1;
+            u64 D = 0;
+            if (valid) {
+                const int k = lst[i], h = S.hi[k];
+                l = S.lo[k];
+                const int hv = h == n ? 0 : h;
+                const long long ax = S.px[(long)S.stride * l], ay = S.py[(long)S.stride * l];
+                const long long bx = S.px[(long)S.stride * hv], by = S.py[(long)S.stride * hv];
+                const long long qx = S.px[(long)S.stride * k], qy = S.py[(long)S.stride * k];
+                const long long ux = bx - ax, uy = by - ay, vx = qx - ax, vy = qy - ay;
+                const u64 L = (u64)(ux * ux + uy * uy), da = (u64)(vx * vx + vy * vy);
+                if (L == 0) D = da;
+                else {
+                    const long long t = vx * ux + vy * uy;
+                    if (t <= 0) D = da * L;
+                    else if ((u64)t >= L) D = (u64)((qx - bx) * (qx - bx) + (qy - by) * (qy - by)) * L;
+                    else {
+                        const long long c = vx * uy - vy * ux;
+                        D = (u64)(c * c);
+                    }
+                }
+                S.dl[i] = D;
+            }
+            // a wave inside one piece folds first: the early levels of a long ring would otherwise meet on one word
+            const int first = __shfl(l, 0);
+            if (__all(!valid || l == first)) {
+                for (int off = 32; off > 0; off >>= 1) {
+                    const u64 o = __shfl_xor(D, off);
+                    D = o > D ? o : D;
+                }
+                if ((tid & 63) == 0 && valid) atomicMax(&best[l], D);
+            } else if (valid) atomicMax(&best[l], D);
+        }
+        __syncthreads();
+        for (int i = tid; i < cnt; i += SP_BLOCK) {
+            const int k = lst[i], l = S.lo[k], h = S.hi[k];
+            if (S.dl[i] == best[l]) {
+                const int a = 2 * k - l - h;
+                atomicMin(&tie[l], ((u64)(unsigned)(a < 0 ? -a : a) << 32) | (u64)(unsigned)k);
+            }
+        }
+        if (tid == 0) sh.nact[p ^ 1] = 0;
+        __syncthreads();
+        for (int i0 = 0; i0 < cnt; i0 += SP_BLOCK) {
+            const int i = i0 + tid;
+            bool live = false;
+            int k = 0;
+            if (i < cnt) {
+                k = lst[i];
+                const int l = S.lo[k], h = S.hi[k];
+                const int hv = h == n ? 0 : h;
+                const int ax = S.px[(long)S.stride * l], ay = S.py[(long)S.stride * l];
+                const int bx = S.px[(long)S.stride * hv], by = S.py[(long)S.stride * hv];
+                const long long ux = (long long)bx - ax, uy = (long long)by - ay;
+                const u64 L = (u64)(ux * ux + uy * uy);
+                if (best[l] > ((tol2 * (L ? L : 1ull)) >> 8)) {
+                    const int m = (int)(unsigned)tie[l];
+                    if (k == m) {
+                        const int mx = S.px[(long)S.stride * k], my = S.py[(long)S.stride * k];
+                        keep[k] = 1ull;
+                        best_n[l] = 0; tie_n[l] = SP_NONE;
+                        best_n[k] = 0; tie_n[k] = SP_NONE;
+                        atomicAdd(&sh.area_k, sp_cross(ax, ay, mx, my) + sp_cross(mx, my, bx, by) - sp_cross(ax, ay, bx, by));
+                        atomicAdd(&sh.nkept, 1);
+                        atomicMin(&sh.bb_k[0], mx); atomicMin(&sh.bb_k[1], my);
+                        atomicMax(&sh.bb_k[2], mx); atomicMax(&sh.bb_k[3], my);
+                    } else {
+                        if (k < m) S.hi[k] = m; else S.lo[k] = m;
+                        live = true;
+                    }
+                }
+            }
+            // the survivors go to the other list: one atomic per wave, the order inside the list does not matter
+            const u64 mask = __ballot(live);
+            if (mask) {
+                const int lane = tid & 63, leader = __ffsll((long long)mask) - 1;
+                int base = 0;
+                if (lane == leader) base = atomicAdd(&sh.nact[p ^ 1], __popcll(mask));
+                base = __shfl(base, leader);
+                if (live) lst_n[base + __popcll(mask & ((1ull << lane) - 1ull))] = k;
+            }
+        }
+        __syncthreads();
+    }
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(SP_BLOCK) void sp_simplify_kernel(const int32_t* __restrict__ hdr, const int32_t* __restrict__ rings,
+                                                               const int32_t* __restrict__ verts, int R, u64 tol2,
+                                                               int32_t* __restrict__ rings_out, int32_t* __restrict__ flags,
+                                                               int32_t* __restrict__ counts, u64* __restrict__ keep,
+                                                               int32_t* __restrict__ g_lo, int32_t* __restrict__ g_hi,
+                                                               u64* __restrict__ g_best, u64* __restrict__ g_tie,
+                                                               int32_t* __restrict__ g_list, u64* __restrict__ g_dl, long V) {
+    __shared__ SpShared sh;
+    __shared__ u64 s_best[2][SP_LDS_N], s_tie[2][SP_LDS_N], s_dl[SP_LDS_N];
+    __shared__ int32_t s_x[SP_LDS_N], s_y[SP_LDS_N], s_lo[SP_LDS_N], s_hi[SP_LDS_N], s_list[2][SP_LDS_N];
+    if (hdr[0] == 0) return;
+    const int tid = threadIdx.x;
+    for (int r = blockIdx.x; r < R; r += gridDim.x) {
+        const int32_t* rec = rings + (long)r * CT_RING;
+        const long fv = rec[2];
+        const int n = rec[3];
+        const long long a2_in = (long long)(((u64)(unsigned)rec[11] << 32) | (u64)(unsigned)rec[10]);
+        const bool oversize = n > 4 && ((long)rec[7] - rec[5] >= SP_SPAN || (long)rec[8] - rec[6] >= SP_SPAN);
+        const bool work = n > 4 && !oversize;
+        const bool in_lds = work && n <= SP_LDS_N;
+        const int32_t* P = verts + 2 * fv;
+        if (tid == 0) {
+            sh.akey = 0;
+            sh.area_all = 0;
+            sh.bb_all[0] = sh.bb_all[1] = 0x7fffffff;
+            sh.bb_all[2] = sh.bb_all[3] = (int)0x80000000;
+        }
+        __syncthreads();
+        // every vertex once: the ring as traced (bounding box, area2), the far anchor
+        {
+            const int x0 = P[0], y0 = P[1];
+            u64 key = 0, area = 0;
+            int bx0 = 0x7fffffff, by0 = 0x7fffffff, bx1 = (int)0x80000000, by1 = (int)0x80000000;
+            for (int k = tid; k < n; k += SP_BLOCK) {
+                const int x = P[2 * k], y = P[2 * k + 1];
+                const int kn = k + 1 == n ? 0 : k + 1;
+                area += sp_cross(x, y, P[2 * kn], P[2 * kn + 1]);
+                bx0 = min(bx0, x); by0 = min(by0, y); bx1 = max(bx1, x); by1 = max(by1, y);
+                if (work) {
+                    const long long dx = (long long)x - x0, dy = (long long)y - y0;
+                    const u64 kk = ((u64)(dx * dx + dy * dy) << 32) | (u64)(0xffffffffu - (unsigned)k);      // < 2^31: the spans are below 2^15
+                    key = kk > key ? kk : key;
+                    if (in_lds) { s_x[k] = x; s_y[k] = y; }
+                } else keep[fv + k] = 1ull;
+            }
+            for (int off = 32; off > 0; off >>= 1) {
+                const u64 ok = __shfl_xor(key, off);
+                key = ok > key ? ok : key;
+                area += __shfl_xor(area, off);
+                bx0 = min(bx0, __shfl_xor(bx0, off)); by0 = min(by0, __shfl_xor(by0, off));
+                bx1 = max(bx1, __shfl_xor(bx1, off)); by1 = max(by1, __shfl_xor(by1, off));
+            }
+            if ((tid & 63) == 0 && (long)(tid & ~63) < n) {
+                atomicMax(&sh.akey, key);
+                atomicAdd(&sh.area_all, area);
+                atomicMin(&sh.bb_all[0], bx0); atomicMin(&sh.bb_all[1], by0);
+                atomicMax(&sh.bb_all[2], bx1); atomicMax(&sh.bb_all[3], by1);
+            }
+        }
+        __syncthreads();
+        bool as_traced = true;
+        if (work) {
+            SpState S;
+            if (in_lds) {
+                S.px = s_x; S.py = s_y; S.stride = 1;
+                S.lo = s_lo; S.hi = s_hi;
+                S.best = s_best[0]; S.tie = s_tie[0]; S.list = s_list[0]; S.par = SP_LDS_N;
+                S.dl = s_dl;
+                sp_ring(S, sh, n, tol2, keep + fv);
+            } else {
+                S.px = P; S.py = P + 1; S.stride = 2;
+                S.lo = g_lo + fv; S.hi = g_hi + fv;
+                S.best = g_best + fv; S.tie = g_tie + fv; S.list = g_list + fv; S.par = V;
+                S.dl = g_dl + fv;
+                sp_ring(S, sh, n, tol2, keep + fv);
+            }
+            const long long ak = (long long)sh.area_k;
+            as_traced = sh.nkept < 3 || ak == 0 || a2_in == 0 || (ak > 0) != (a2_in > 0);       // orientation is never lost
+            if (as_traced)
+                for (int k = tid; k < n; k += SP_BLOCK) keep[fv + k] = 1ull;
+        }
+        if (tid == 0) {
+            const int flag = oversize ? 2 : (work && as_traced) ? 1 : 0;
+            const u64 area = as_traced ? sh.area_all : sh.area_k;
+            const int* bb = as_traced ? sh.bb_all : sh.bb_k;
+            int32_t* out = rings_out + (long)r * CT_RING;
+            out[0] = rec[0]; out[1] = rec[1];
+            out[3] = as_traced ? n : sh.nkept;
+            out[4] = rec[4];
+            out[5] = bb[0]; out[6] = bb[1]; out[7] = bb[2]; out[8] = bb[3];
+            out[9] = rec[9];
+            out[10] = (int)(unsigned)area; out[11] = (int)(unsigned)(area >> 32);
+            flags[r] = flag;
+            if (flag) atomicAdd(counts + flag, 1);
+        }
+        __syncthreads();
+    }
+}
+
+// grid over max(V, R): scan[k] is the number of kept vertices in front of k
+__global__ __launch_bounds__(CT_BLOCK) void sp_emit_kernel(const int32_t* __restrict__ hdr, const int32_t* __restrict__ rings,
+                                                           const int32_t* __restrict__ verts, const u64* __restrict__ scan,
+                                                           int32_t* __restrict__ rings_out, int32_t* __restrict__ verts_out,
+                                                           int32_t* __restrict__ counts, int R, int V) {
+    if (hdr[0] == 0) return;
+    const long k = (long)blockIdx.x * CT_BLOCK + threadIdx.x;
+    const u64 total = *(const u64*)(hdr + 2);
+    if (k < V) {
+        const u64 s = scan[k], e = k + 1 < V ? scan[k + 1] : total;
+        if (e != s && s < (u64)V) {
+            verts_out[2 * s] = verts[2 * k];
+            verts_out[2 * s + 1] = verts[2 * k + 1];
+        }
+    }
+    if (k < R) rings_out[k * CT_RING + 2] = (int)scan[rings[k * CT_RING + 2]];
+    if (k == 0) counts[0] = (int)total;
+}
+
+struct SpLayout { size_t hdr, keep, bsum, lo, hi, best, tie, list, dl, total; };
+inline SpLayout sp_layout(long V) {
+    const size_t v = (size_t)V;
+    SpLayout L;
+    size_t o = 0;
+    L.hdr = o; o += align_up(SP_HDR_WORDS * 4, 256);
+    L.keep = o; o += align_up(v * 8, 256);
+    L.bsum = o; o += align_up(((v + CT_SCAN - 1) / CT_SCAN) * 8, 256);
+    L.lo = o; o += align_up(v * 4, 256);
+    L.hi = o; o += align_up(v * 4, 256);
+    L.best = o; o += align_up(2 * v * 8, 256);
+    L.tie = o; o += align_up(2 * v * 8, 256);
+    L.list = o; o += align_up(2 * v * 4, 256);
+    L.dl = o; o += align_up(v * 8, 256);
+    L.total = o;
+    return L;
+}
+inline bool sp_bad_sizes(int R, int V) { return R < 0 || V < 0 || V > (1 << 28) || R > V; }
+
+}  // namespace
+
+extern "C" size_t wesup_contour_simplify_workspace_bytes(int R, int V) {
+    if (sp_bad_sizes(R, V)) return 0;
+    return sp_layout(V).total;
+}
+
+extern "C" int wesup_contour_simplify(const int32_t* rings, int R, const int32_t* verts, int V, int tol_q4, int32_t* rings_out,
+                                      int32_t* verts_out, int32_t* flags, int32_t* counts, void* ws, size_t ws_bytes, void* stream) {
+    if (!rings || !verts || !rings_out || !verts_out || !flags || !counts || !ws || sp_bad_sizes(R, V)) return WESUP_ERR_INVALID;
+    if (tol_q4 < 0 || tol_q4 > WESUP_SIMPLIFY_TOL_MAX) return WESUP_ERR_INVALID;
+    if (((uintptr_t)ws & 15) || ((uintptr_t)rings & 7) || ((uintptr_t)rings_out & 7) || ((uintptr_t)verts & 3) ||
+        ((uintptr_t)verts_out & 3) || ((uintptr_t)flags & 3) || ((uintptr_t)counts & 3))
+        return WESUP_ERR_INVALID;
+    const SpLayout L = sp_layout(V);
+    if (ws_bytes < L.total) return WESUP_ERR_INVALID;
+    const size_t nr = (size_t)(R > 0 ? R : 1) * CT_RING * 4, nv = (size_t)(V > 0 ? V : 1) * 8, nf = (size_t)(R > 0 ? R : 1) * 4;
+    const void* ops[7] = {rings, verts, rings_out, verts_out, flags, counts, ws};
+    const size_t len[7] = {nr, nv, nr, nv, nf, WESUP_SIMPLIFY_COUNTS * 4, L.total};
+    for (int i = 0; i < 7; ++i)
+        for (int j = i + 1; j < 7; ++j)
+            if (overlap(ops[i], len[i], ops[j], len[j])) return WESUP_ERR_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    char* w = (char*)ws;
+    int32_t* hdr = (int32_t*)(w + L.hdr);
+    u64* keep = (u64*)(w + L.keep);
+    u64* bsum = (u64*)(w + L.bsum);
+    if (wesup_fill_words_(counts, 0u, (size_t)WESUP_SIMPLIFY_COUNTS, st) != WESUP_OK) return WESUP_ERR_LAUNCH;
+    WESUP_LAUNCH(sp_validate_kernel, dim3(1), dim3(SP_BLOCK), 0, st, rings, R, V, hdr, counts);
+    if (R > 0) {
+        const unsigned gs = (unsigned)((V + CT_SCAN - 1) / CT_SCAN);
+        const int big = V > R ? V : R;
+        WESUP_LAUNCH(sp_simplify_kernel, dim3(R < SP_MAX_BLOCKS ? R : SP_MAX_BLOCKS), dim3(SP_BLOCK), 0, st, (const int32_t*)hdr,
+                     rings, verts, R, (u64)tol_q4 * (u64)tol_q4, rings_out, flags, counts, keep, (int32_t*)(w + L.lo),
+                     (int32_t*)(w + L.hi), (u64*)(w + L.best), (u64*)(w + L.tie), (int32_t*)(w + L.list), (u64*)(w + L.dl), (long)V);
+        WESUP_LAUNCH(sc_block_sums, dim3(gs), dim3(CT_SCAN), 0, st, (const int32_t*)hdr, (const u64*)keep, bsum, V);
+        WESUP_LAUNCH(sc_small, dim3(1), dim3(CT_SCAN), 0, st, (const int32_t*)hdr, bsum, (int)gs, (u64*)(hdr + 2));
+        WESUP_LAUNCH(sc_apply, dim3(gs), dim3(CT_SCAN), 0, st, (const int32_t*)hdr, keep, (const u64*)bsum, V);
+        WESUP_LAUNCH(sp_emit_kernel, dim3((unsigned)((big + CT_BLOCK - 1) / CT_BLOCK)), dim3(CT_BLOCK), 0, st, (const int32_t*)hdr,
+                     rings, verts, (const u64*)keep, rings_out, verts_out, counts, R, V);
     }
     WESUP_CHECK_LAUNCH();
     return WESUP_OK;

@@ -1,6 +1,6 @@
 """Object measurements: moments, shape counts and the exact convex hull of every label of a label map.
 
-  python -m wesup_amd.measure PRED_DIR OUT.csv [--gpu] [--labels] [--classes C] [--min-area A] [--scale S] [--geojson DIR]
+  python -m wesup_amd.measure PRED_DIR OUT.csv [--gpu] [--labels] [--classes C] [--min-area A] [--scale S] [--geojson DIR [--simplify PX]]
 
 Coordinates are ``contour.py``'s: pixel (r, c) covers [c, c+1] x [r, r+1], vertices are integer pixel corners (x, y), y downwards.
 The input is an int32 label map (H, W) / (B, H, W) with labels 0 .. L; label 0 is background and its row of the table is zero; a
@@ -307,26 +307,33 @@ def _instances(mask, device):
     return lab
 
 
-def measure_directory(pred_dir, out_csv, device=None, labels=False, classes=0, min_area=0, scale=1.0, geojson=None, log=print):
+def measure_directory(pred_dir, out_csv, device=None, labels=False, classes=0, min_area=0, scale=1.0, geojson=None, log=print,
+                      simplify=None):
     """One csv row per object of every ``*.png`` / ``*.bmp`` of ``pred_dir``: binary masks (any non-zero) are labelled 8-connected
     (``ops.cc_label`` on the device), 16-bit instance maps are read with ``labels``, class-index maps of ``classes`` = C per class.
-    ``geojson``: a directory that gets ``<stem>.geojson`` with the features under ``properties.measurements``."""
+    ``geojson``: a directory that gets ``<stem>.geojson`` with the features under ``properties.measurements``; ``simplify``: its
+    outlines are simplified within that many pixels -- the measurements stay those of the traced objects."""
     from PIL import Image
     from . import contour
+    if simplify is not None and geojson is None:
+        raise ValueError('simplify: the tolerance of the outlines that geojson writes')
     pred_dir = Path(pred_dir).expanduser()
     paths = sorted(p for e in ('*.bmp', '*.png') for p in pred_dir.glob(e))
     rows = []
     for path in paths:
         a = np.asarray(Image.open(path))
         a = a[..., 0] if a.ndim == 3 else a
-        n0, polys, meas = len(rows), [], {}
+        n0, polys, meas, stats = len(rows), [], {}, {}
         for k in (range(1, int(classes)) if classes else (0,)):
             lab = a.astype(np.int32) if labels else _instances(a == k if classes else a, device)
             r, by_label = object_rows(lab, path.name, device, k, min_area, scale)
             rows += r
             if geojson is not None:
                 lab_np = lab.cpu().numpy() if not isinstance(lab, np.ndarray) else lab
-                ps = [p for p in contour.polygons(*contour.trace(lab_np, device)[:2]) if p['area_px'] >= min_area]
+                if simplify is None:
+                    ps = [p for p in contour.polygons(*contour.trace(lab_np, device)[:2]) if p['area_px'] >= min_area]
+                else:
+                    ps = contour.label_polygons(lab_np, device, min_area, simplify, stats)
                 for p in ps:
                     if classes:
                         p['class'] = k
@@ -335,7 +342,7 @@ def measure_directory(pred_dir, out_csv, device=None, labels=False, classes=0, m
                     polys.append(p)
         if geojson is not None:
             contour.write_geojson(Path(geojson).expanduser() / (path.stem + '.geojson'), polys, scale, measurements=meas)
-        log(f'{path.name}: {len(rows) - n0} objects')
+        log(f'{path.name}: {len(rows) - n0} objects' + ('' if simplify is None else '; ' + contour.simplify_log(stats, simplify)))
     write_csv(out_csv, rows)
     return rows
 
@@ -351,6 +358,7 @@ def build_parser():
     ap.add_argument('--min-area', type=int, default=0, help='drop objects of fewer pixels')
     ap.add_argument('--scale', type=float, default=1.0, help='slide pixels per mask pixel')
     ap.add_argument('--geojson', default=None, metavar='DIR', help='also write <stem>.geojson with the measurements as properties')
+    ap.add_argument('--simplify', type=float, default=None, metavar='PX', help='simplify the outlines of --geojson within this many pixels')
     return ap
 
 
@@ -358,7 +366,8 @@ def main(argv=None):
     a = build_parser().parse_args(argv)
     if a.labels and a.classes:
         raise SystemExit('--labels and --classes exclude each other')
-    measure_directory(a.pred_dir, a.out_csv, a.device if a.gpu else None, a.labels, a.classes, a.min_area, a.scale, a.geojson)
+    measure_directory(a.pred_dir, a.out_csv, a.device if a.gpu else None, a.labels, a.classes, a.min_area, a.scale, a.geojson,
+                      **({} if a.simplify is None else {'simplify': a.simplify}))
 
 
 if __name__ == '__main__':

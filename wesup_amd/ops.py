@@ -1641,6 +1641,43 @@ def contour_trace(labels):
     return rings[:sum(t[:B])], verts[:n_corners], tail[:B]
 
 
+def contour_simplify(rings, verts, tol_q4):
+    """Exact Douglas-Peucker of traced rings: rings (R, 12) and verts (V, 2) int32 as ``contour_trace`` leaves
+    them, ``tol_q4`` the tolerance in sixteenths of a pixel (0 .. 4096) -> (rings2 (R, 12), verts2 (V2, 2), flags (R,), counts
+    (4,): kept vertices, rings flagged 1, rings flagged 2, status) int32 on the device, equal to contour.simplify_host.  One
+    read-back behind the call, of ``counts``: verts2 is cut to its length from it."""
+    name = 'contour_simplify'
+    _chk(rings, torch.int32, f'{name}: rings')
+    _chk(verts, torch.int32, f'{name}: verts')
+    if rings.dim() != 2 or rings.shape[1] != CONTOUR_RING or verts.dim() != 2 or verts.shape[1] != 2 or verts.device != rings.device:
+        raise _lib.WesupHipError(f'{name}: expected rings (R, {CONTOUR_RING}) and verts (V, 2) on one device, got '
+                                 f'{tuple(rings.shape)} and {tuple(verts.shape)}')
+    tol = int(tol_q4)
+    if tol != tol_q4 or not 0 <= tol <= _lib.SIMPLIFY_TOL_MAX:
+        raise _lib.WesupHipError(f'{name}: tol_q4 {tol_q4}: an integer in 0 .. {_lib.SIMPLIFY_TOL_MAX}')
+    dev = rings.device
+    R, V = rings.shape[0], verts.shape[0]
+    if R == 0 and V != 0:
+        raise _lib.WesupHipError(f'{name}: {V} vertices without a ring')
+    if R == 0:
+        return (torch.empty(0, CONTOUR_RING, dtype=torch.int32, device=dev), torch.empty(0, 2, dtype=torch.int32, device=dev),
+                torch.empty(0, dtype=torch.int32, device=dev), torch.zeros(_lib.SIMPLIFY_COUNTS, dtype=torch.int32, device=dev))
+    nb = _lib.load().wesup_contour_simplify_workspace_bytes(R, V)
+    if not nb:
+        raise _lib.WesupHipError(f'{name}: {R} rings of {V} vertices are outside the entry\'s range (R <= V <= 2^28)')
+    rings2 = torch.empty(max(R, 1), CONTOUR_RING, dtype=torch.int32, device=dev)
+    verts2 = torch.empty(max(V, 1), 2, dtype=torch.int32, device=dev)
+    flags = torch.empty(max(R, 1), dtype=torch.int32, device=dev)
+    counts = torch.empty(_lib.SIMPLIFY_COUNTS, dtype=torch.int32, device=dev)
+    ws = workspace(nb, dev, 'simplify')
+    _lib.call('wesup_contour_simplify', _p(rings), R, _p(verts), V, tol, _p(rings2), _p(verts2), _p(flags), _p(counts), _p(ws), nb,
+              _stream())
+    c = counts.tolist()                                                      # the read-back
+    if c[3] != 0:
+        raise _lib.WesupHipError(f'{name}: status {c[3]}: the records\' vertex ranges are not consecutive from 0 to {V}')
+    return rings2[:R], verts2[:c[0]], flags[:R], counts
+
+
 # ---------------------------------------------------------------- polygon fill (csrc/raster.hip, DESIGN.md 3.23)
 def polygon_fill(verts, ring_first, feature_first_ring, feature_image, shape, values=None):
     """Polygons in CSR form, fixed point with 8 fractional bits (raster.pack) -> (labels int32, out8 uint8 or None, status (1,)

@@ -504,7 +504,7 @@ def score_directory(output_dir, gt_dir, log=print, device=None, n_classes=2):
 
 def main(data_root, checkpoint, model_type='wesup', pixel=False, patch_size=PATCH_SIZE, skip_infer=False, device=None, batch=None,
          post_threshold=None, log=print, stain_normalize=None, skip_background=None, tissue_masks=None, geojson=None,
-         measure=None):
+         measure=None, simplify=None):
     """test_dp2019_pipeline.py:114-219 without its patch files: predict every slide of ``data_root/images/*.jpg`` (unless
     ``skip_infer``), write the combined PNGs, score them against ``data_root/masks``.  Returns ``score_directory``'s result.
 
@@ -519,7 +519,9 @@ def main(data_root, checkpoint, model_type='wesup', pixel=False, patch_size=PATC
     ``geojson``: a directory that gets the outlines of every combined map as ``<stem>.geojson``: the objects of
     the binary map as it is written (after ``post_threshold``), for more than two classes the objects of every class.
     ``measure``: a directory that gets the measurements of the same objects as ``<stem>.csv``, one row per object (DESIGN.md
-    3.22)."""
+    3.22).
+    ``simplify``: the outlines of ``geojson`` are simplified within that many pixels; one log line per slide tells
+    the vertex counts, the flagged rings and the pixels that change when the simplified polygons are filled back."""
     from PIL import Image
     data_root = Path(data_root).expanduser()
     output_dir = output_dir_for(checkpoint, pixel)
@@ -536,6 +538,8 @@ def main(data_root, checkpoint, model_type='wesup', pixel=False, patch_size=PATC
     skipping = skip_background not in (None, False)
     if tissue_masks is not None and not skipping:
         raise ValueError('--tissue-masks writes the masks of --skip-background')
+    if simplify is not None and geojson is None:
+        raise ValueError('--simplify is the tolerance of the outlines that --geojson writes')
     if not skip_infer:
         log('\nMaking inference ...')
         if pixel:
@@ -573,7 +577,13 @@ def main(data_root, checkpoint, model_type='wesup', pixel=False, patch_size=PATC
             Image.fromarray(combined).save(output_dir / f'{path.stem}.png', format='PNG')
             if geojson is not None:
                 from . import contour
-                polys = (contour.classmap_polygons(combined, C, device) if C > 2 else contour.mask_polygons(combined, device))
+                if simplify is None:
+                    polys = (contour.classmap_polygons(combined, C, device) if C > 2 else contour.mask_polygons(combined, device))
+                else:
+                    stats = {}
+                    polys = (contour.classmap_polygons(combined, C, device, simplify=simplify, stats=stats) if C > 2 else
+                             contour.mask_polygons(combined, device, simplify=simplify, stats=stats))
+                    log(f'{path.stem}: ' + contour.simplify_log(stats, simplify))
                 contour.write_geojson(Path(geojson).expanduser() / f'{path.stem}.geojson', polys)
             if measure is not None:
                 from . import measure as measure_mod
@@ -607,6 +617,7 @@ def parse_args(argv=None):
     ap.add_argument('--tissue-masks', default=None, metavar='DIR', help='write the tissue mask PNGs here (with --skip-background)')
     ap.add_argument('--geojson', default=None, metavar='DIR', help='write the outlines of every combined map here as <stem>.geojson')
     ap.add_argument('--measure', default=None, metavar='DIR', help='write the measurements of the objects of every combined map here as <stem>.csv')
+    ap.add_argument('--simplify', type=float, default=None, metavar='PX', help='simplify the outlines of --geojson within this many pixels')
     from .stain import add_argument
     add_argument(ap)
     return ap.parse_args(argv)
@@ -624,6 +635,8 @@ def cli(argv=None):
         extra['geojson'] = a.geojson
     if a.measure is not None:
         extra['measure'] = a.measure
+    if a.simplify is not None:
+        extra['simplify'] = a.simplify
     return main(a.data_root, a.checkpoint, model_type=a.model, pixel=a.pixel, patch_size=a.patch_size, skip_infer=a.skip_infer,
                 device=a.device, batch=a.batch, post_threshold=a.post_threshold, **extra,
                 **({} if a.stain_normalize is None else {'stain_normalize': a.stain_normalize}))

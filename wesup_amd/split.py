@@ -1,6 +1,6 @@
 """Splitting touching objects of a predicted mask: distance seeds, label growth, cuts.
 
-  python -m wesup_amd.split PRED_DIR OUT_DIR --radius R [--gpu] [--labels] [--geojson DIR] [--measure CSV]
+  python -m wesup_amd.split PRED_DIR OUT_DIR --radius R [--gpu] [--labels] [--geojson DIR [--simplify PX]] [--measure CSV]
 
 Every object-level metric takes an object to be an 8-connected component of the mask, so two glands whose predictions touch
 count as one.  ``split_objects`` separates them: the pixels whose whole open disc of radius ``radius`` is foreground are the
@@ -145,11 +145,14 @@ def split_objects(mask, radius, device=None, return_labels=False):
     return (out, L) if return_labels else out
 
 
-def split_directory(pred_dir, out_dir, radius, device=None, labels=False, log=print, geojson=None, measure=None):
+def split_directory(pred_dir, out_dir, radius, device=None, labels=False, log=print, geojson=None, measure=None, simplify=None):
     """Split every 0/255 mask (``*.png``, ``*.bmp``) of ``pred_dir`` into ``out_dir`` (masks x 255; with ``labels`` also the
     instance map -- the 8-connected components of the result in raster order -- as ``<stem>_labels.png``, 16 bit; with
     ``geojson`` the outlines of the split instances as ``<stem>.geojson`` in that directory; with
-    ``measure`` the measurements of the split instances of all masks as that csv file)."""
+    ``measure`` the measurements of the split instances of all masks as that csv file; with ``simplify`` the
+    outlines are simplified within that many pixels, DESIGN.md 3.24, and what that changed is logged)."""
+    if simplify is not None and geojson is None:
+        raise ValueError('simplify: the tolerance of the outlines that geojson writes')
     from PIL import Image
     pred_dir, out_dir = Path(pred_dir).expanduser(), Path(out_dir).expanduser()
     out_dir.mkdir(parents=True, exist_ok=True)
@@ -169,8 +172,13 @@ def split_directory(pred_dir, out_dir, radius, device=None, labels=False, log=pr
             Image.fromarray(inst.astype(np.uint16)).save(out_dir / (path.stem + '_labels.png'))
         if geojson is not None:
             from . import contour
-            contour.write_geojson(Path(geojson).expanduser() / (path.stem + '.geojson'),
-                                  contour.polygons(*contour.trace(inst.astype(np.int32), device)[:2]))
+            if simplify is None:
+                polys = contour.polygons(*contour.trace(inst.astype(np.int32), device)[:2])
+            else:
+                stats = {}
+                polys = contour.label_polygons(inst.astype(np.int32), device, simplify=simplify, stats=stats)
+                log(f'{path.name}: ' + contour.simplify_log(stats, simplify))
+            contour.write_geojson(Path(geojson).expanduser() / (path.stem + '.geojson'), polys)
         if measure is not None:
             rows += measure_mod.object_rows(inst.astype(np.int32), path.name, device)[0]
         log(f'{path.name}: {n_before} -> {int(inst.max())} objects')
@@ -189,13 +197,15 @@ def build_parser():
     ap.add_argument('--labels', action='store_true', help='also write the instance maps as 16-bit <stem>_labels.png')
     ap.add_argument('--geojson', default=None, metavar='DIR', help='write the outlines of the split instances here as <stem>.geojson')
     ap.add_argument('--measure', default=None, metavar='CSV', help='write the measurements of the split instances, one row per object')
+    ap.add_argument('--simplify', type=float, default=None, metavar='PX', help='simplify the outlines of --geojson within this many pixels')
     return ap
 
 
 def main(argv=None):
     a = build_parser().parse_args(argv)
     _check_radius(a.radius)
-    split_directory(a.pred_dir, a.out_dir, a.radius, a.device if a.gpu else None, a.labels, geojson=a.geojson, measure=a.measure)
+    split_directory(a.pred_dir, a.out_dir, a.radius, a.device if a.gpu else None, a.labels, geojson=a.geojson, measure=a.measure,
+                    **({} if a.simplify is None else {'simplify': a.simplify}))
 
 
 if __name__ == '__main__':
