@@ -48,6 +48,26 @@ def test_slic_matches_restatement(H, W, n_seg):
     assert torch.equal(lab_gpu, lab2) and torch.equal(n_gpu, n2)       # run-to-run identical
 
 
+def test_slic_connectivity_batch_of_two_over_several_scan_blocks():
+    """The renumbering scan (csrc/scan.hpp through slic.hip's own wrappers) with B = 2 and three scan blocks of 1024 per image
+    (80 x 32 = 2560 pixels), two different images: a wrong image offset or block offset renumbers one of them wrongly.  The
+    integer pass is exact: the restated pass on the GPU's own k-means labels, image by image."""
+    from oracle import slic_oracle as so
+    from wesup_amd import ops, synth
+    H, W, n_seg = 80, 32, 20
+    imgs = np.stack([synth.synth_image(5 + b, H, W) for b in range(2)])
+    assert not np.array_equal(imgs[0], imgs[1])
+    t = torch.from_numpy(imgs).to('cuda:0')
+    km, _ = ops.slic(t, n_seg, 40.0, 10, enforce_connectivity=False)
+    lab, n = ops.slic(t, n_seg, 40.0, 10)
+    for b in range(2):
+        ref_lab, ref_n = so.enforce_connectivity(km[b].cpu().numpy().astype(np.int64), n_seg, 0.5)
+        first = np.full(ref_n, H * W); np.minimum.at(first, ref_lab.ravel(), np.arange(H * W))
+        assert (first >= 1024).any() and (first >= 2048).any(), first      # ids begin in every scan block: all offsets are used
+        assert int(n[b]) == ref_n, (b, int(n[b]), ref_n)
+        assert np.array_equal(lab[b].cpu().numpy(), ref_lab), b
+
+
 @pytest.mark.parametrize('H,W,sp_area', [(480, 480, 200), (200, 300, 150)])
 def test_slic_properties_and_quality(H, W, sp_area):
     from scipy import ndimage

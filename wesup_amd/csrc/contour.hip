@@ -23,7 +23,8 @@
 //                      next power; once 2^k covers the ring m is the leader and off the distance to it (the ring length at the
 //                      leader itself).  One 16-byte element per crack and round, read once in order and once through nxt.
 //   ct_ring_kernel     position in the ring, and the scan key of the leaders: (1 << 32) | length
-//   sc_block_sums, sc_small, sc_apply    ring ids and the rings' first crack in ring order, one 64-bit scan
+//   sc_block_sums, sc_small, sc_apply    ring ids and the rings' first crack in ring order, one 64-bit scan (the three passes of
+//                      scan.hpp here and below; ct_pfx_kernel above is its apply pass over the crack counts)
 //   ct_check2_kernel   rings against ring_cap
 //   ct_place_kernel    ring order: the crack of every place, the corner flag of every place; the leaders start their records
 //   sc_block_sums, sc_small, sc_apply    vertex indices: the scan of the corner flags in ring order
@@ -38,6 +39,7 @@
 //   sc_block_sums, sc_small, sc_apply    the scan of the keep flags: the output index of every kept vertex
 //   sp_emit_kernel     kept vertices to their places, every record's first vertex, the total
 #include "common.hpp"
+#include "scan.hpp"
 
 #define CT_SCAN 1024
 #define CT_BLOCK 256
@@ -74,24 +76,6 @@ __device__ __forceinline__ void crack_ends(int r, int c, int d, int& x0, int& y0
     y0 = r + (d >= 2);
     x1 = c + (d >= 2);
     y1 = r + (d == 1 || d == 2);
-}
-
-// exclusive scan of CT_SCAN values, one per thread
-template <typename T>
-__device__ __forceinline__ T block_scan(T v, T* sh, T* total) {
-    const int tid = threadIdx.x;
-    sh[tid] = v;
-    __syncthreads();
-    for (int off = 1; off < CT_SCAN; off <<= 1) {
-        const T t = (tid >= off) ? sh[tid - off] : (T)0;
-        __syncthreads();
-        sh[tid] += t;
-        __syncthreads();
-    }
-    const T incl = sh[tid];
-    *total = sh[CT_SCAN - 1];
-    __syncthreads();
-    return incl - v;
 }
 
 // grid (nblk, B).  maskb [B][HW]: bits 0..3 the cracks N W S E, bits 4..7 their corner flags
@@ -140,38 +124,24 @@ __global__ __launch_bounds__(CT_SCAN) void ct_mask_kernel(const int32_t* __restr
     }
 }
 
-// the 64-bit scan in three kernels; gate: a header word, every launch behind a check is a no-op unless the check passed (NULL: none)
+// the 64-bit scan in three kernels (scan.hpp); gate: a header word, every launch behind a check is a no-op unless the check passed (NULL: none)
 __global__ __launch_bounds__(CT_SCAN) void sc_block_sums(const int32_t* __restrict__ gate, const u64* __restrict__ vals,
                                                                u64* __restrict__ bsum, int n) {
-    __shared__ u64 sh[CT_SCAN];
     if (gate && *gate == 0) return;
-    const long i = (long)blockIdx.x * CT_SCAN + threadIdx.x;
-    u64 tot;
-    block_scan<u64>(i < n ? vals[i] : 0ull, sh, &tot);
+    const u64 tot = scan::scan_block_total<u64, CT_SCAN>([vals](long i) { return vals[i]; }, n);
     if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
 }
 __global__ __launch_bounds__(CT_SCAN) void sc_small(const int32_t* __restrict__ gate, u64* __restrict__ v, int n,
                                                           u64* __restrict__ total_out) {
-    __shared__ u64 sh[CT_SCAN];
     if (gate && *gate == 0) return;
-    u64 run = 0;
-    for (int i0 = 0; i0 < n; i0 += CT_SCAN) {
-        const int i = i0 + threadIdx.x;
-        u64 tot;
-        const u64 e = block_scan<u64>(i < n ? v[i] : 0ull, sh, &tot);
-        if (i < n) v[i] = run + e;
-        run += tot;
-    }
+    u64 run;
+    scan::scan_small<u64, CT_SCAN>(v, n, &run);
     if (threadIdx.x == 0) *total_out = run;
 }
 __global__ __launch_bounds__(CT_SCAN) void sc_apply(const int32_t* __restrict__ gate, u64* __restrict__ vals,
                                                           const u64* __restrict__ bsum, int n) {
-    __shared__ u64 sh[CT_SCAN];
     if (gate && *gate == 0) return;
-    const long i = (long)blockIdx.x * CT_SCAN + threadIdx.x;
-    u64 tot;
-    const u64 e = block_scan<u64>(i < n ? vals[i] : 0ull, sh, &tot);
-    if (i < n) vals[i] = bsum[blockIdx.x] + e;
+    scan::scan_apply<u64, CT_SCAN>([vals](long i) { return vals[i]; }, [vals](long i, u64 x) { vals[i] = x; }, bsum[blockIdx.x], n);
 }
 
 // hdr[0] = 1 when the map holds exactly the cracks and corners the caller sized its buffers for
@@ -187,16 +157,14 @@ __global__ void ct_check2_kernel(int32_t* __restrict__ hdr, int32_t* __restrict_
     else atomicOr(status, 1);
 }
 
-// grid (nblk, B): pfx [B][HW], the compact index of the pixel's first crack
+// grid (nblk, B): pfx [B][HW], the compact index of the pixel's first crack: the apply pass of the scan whose block sums
+// ct_mask_kernel made
 __global__ __launch_bounds__(CT_SCAN) void ct_pfx_kernel(const uint8_t* __restrict__ maskb, const u64* __restrict__ bsum,
                                                          int32_t* __restrict__ pfx, int HW, int nblk) {
-    __shared__ int sh[CT_SCAN];
-    const int b = blockIdx.y, blk = blockIdx.x;
-    const int p = blk * CT_SCAN + threadIdx.x;
-    const int v = p < HW ? __popc(maskb[(long)b * HW + p] & 15u) : 0;
-    int tot;
-    const int e = block_scan<int>(v, sh, &tot);
-    if (p < HW) pfx[(long)b * HW + p] = (int)bsum[(long)b * nblk + blk] + e;
+    const uint8_t* m = maskb + (long)blockIdx.y * HW;
+    int32_t* out = pfx + (long)blockIdx.y * HW;
+    scan::scan_apply<int, CT_SCAN>([m](long p) { return __popc(m[p] & 15u); }, [out](long p, int x) { out[p] = x; },
+                                   (int)bsum[(long)blockIdx.y * nblk + blockIdx.x], HW);
 }
 
 // grid (ceil(HW / CT_BLOCK), B)

@@ -22,19 +22,21 @@
 //   ms_local_kernel     one thread per pixel corner: the pixel's maximum of d2 (atomicMax on d2 << 32 | ~pixel: the first pixel in
 //                       raster order wins; a wave inside one label folds first), its border class, and the corner's 2 x 2 pattern
 //                       of every distinct label among its four pixels
-//   ms_offsets_kernel   candidates h + 1 and hull blocks ceil((h + 1) / CHUNK) of every label, both scanned (one block)
+//   ms_offsets_kernel   candidates h + 1 and hull blocks ceil((h + 1) / CHUNK) of every label, both scanned (one block, two block
+//                       scans of scan.hpp per round from one read of the boxes)
 //   ms_check_kernel     the candidates against n_prof: every later kernel returns at once unless they fit
 //   two fills, ms_rows_kernel   L[r] / R[r] of every (label, row) by int32 atomicMin / atomicMax from the ends of runs only
 //   ms_cand_kernel      the two candidates of every line
 //   fill, ms_hull_kernel   a block per (label, chunk of CHUNK candidates), found by binary search in the scanned block counts;
 //                       all candidates of the label stream through LDS; flags and packed coordinates in output order
-//   ms_flag_sums, ms_scan_small, ms_flag_apply   the vertex index of every flag, one scan over 2 n_prof flags
+//   ms_flag_sums, ms_scan_small, ms_flag_apply   the vertex index of every flag, one scan over 2 n_prof flags (the passes of scan.hpp)
 //   ms_check2_kernel    the vertices against vert_cap
 //   ms_emit_kernel      the vertices
 //   ms_final_kernel     a block per label: area2, the Feret pair in two passes over the vertex pairs, and the row of the table
 // Nothing is written to table or hull_verts unless both checks pass; status gets bit 0 per image for a label outside [0, L] and
 // bit 1 on every image when a capacity is short.
 #include "common.hpp"
+#include "scan.hpp"
 
 #define MS_BLOCK 256
 #define MS_PIX 8                          // consecutive pixels per thread
@@ -58,24 +60,6 @@ namespace {
 
 typedef unsigned long long u64;
 typedef long long i64;
-
-// exclusive scan of MS_SCAN values, one per thread
-template <typename T>
-__device__ __forceinline__ T block_scan(T v, T* sh, T* total) {
-    const int tid = threadIdx.x;
-    sh[tid] = v;
-    __syncthreads();
-    for (int off = 1; off < MS_SCAN; off <<= 1) {
-        const T t = (tid >= off) ? sh[tid - off] : (T)0;
-        __syncthreads();
-        sh[tid] += t;
-        __syncthreads();
-    }
-    const T incl = sh[tid];
-    *total = sh[MS_SCAN - 1];
-    __syncthreads();
-    return incl - v;
-}
 
 __device__ __forceinline__ int lab_at(const int32_t* __restrict__ img, int H, int W, int r, int c) {
     return ((unsigned)r < (unsigned)H && (unsigned)c < (unsigned)W) ? img[(long)r * W + c] : -1;      // a label l >= 1 never equals it
@@ -281,8 +265,8 @@ __global__ __launch_bounds__(MS_SCAN) void ms_offsets_kernel(const int32_t* __re
         }
         const u64 k = (c + MS_CHUNK - 1) / MS_CHUNK;
         u64 totc, totk;
-        const u64 ec = block_scan<u64>(c, sh, &totc);
-        const u64 ek = block_scan<u64>(k, sh, &totk);
+        const u64 ec = scan::block_scan<u64, MS_SCAN>(c, sh, &totc);
+        const u64 ek = scan::block_scan<u64, MS_SCAN>(k, sh, &totk);
         if (e < n_e) { offc[e] = runc + ec; offk[e] = runk + ek; }
         runc += totc;
         runk += totk;
@@ -428,37 +412,24 @@ __global__ __launch_bounds__(MS_BLOCK) void ms_hull_kernel(const int32_t* __rest
     seqxy[qr] = (y << 16) | (unsigned)(there ? xr : 0);
 }
 
-// the scan of the flags in three kernels
+// the scan of the flags in three kernels (scan.hpp)
 __global__ __launch_bounds__(MS_SCAN) void ms_flag_sums_kernel(const int32_t* __restrict__ hdr, const uint8_t* __restrict__ seqf,
                                                                int* __restrict__ bsum, long n) {
-    __shared__ int sh[MS_SCAN];
     if (hdr[0] == 0) return;
-    const long i = (long)blockIdx.x * MS_SCAN + threadIdx.x;
-    int tot;
-    block_scan<int>(i < n ? (int)seqf[i] : 0, sh, &tot);
+    const int tot = scan::scan_block_total<int, MS_SCAN>([seqf](long i) { return (int)seqf[i]; }, n);
     if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
 }
 __global__ __launch_bounds__(MS_SCAN) void ms_scan_small_kernel(int32_t* __restrict__ hdr, int* __restrict__ v, int n) {
-    __shared__ int sh[MS_SCAN];
     if (hdr[0] == 0) return;
-    int run = 0;
-    for (int i0 = 0; i0 < n; i0 += MS_SCAN) {
-        const int i = i0 + threadIdx.x;
-        int tot;
-        const int e = block_scan<int>(i < n ? v[i] : 0, sh, &tot);
-        if (i < n) v[i] = run + e;
-        run += tot;
-    }
+    int run;
+    scan::scan_small<int, MS_SCAN>(v, n, &run);
     if (threadIdx.x == 0) hdr[8] = run;
 }
 __global__ __launch_bounds__(MS_SCAN) void ms_flag_apply_kernel(const int32_t* __restrict__ hdr, const uint8_t* __restrict__ seqf,
                                                                 const int* __restrict__ bsum, int* __restrict__ seqi, long n) {
-    __shared__ int sh[MS_SCAN];
     if (hdr[0] == 0) return;
-    const long i = (long)blockIdx.x * MS_SCAN + threadIdx.x;
-    int tot;
-    const int e = block_scan<int>(i < n ? (int)seqf[i] : 0, sh, &tot);
-    if (i < n) seqi[i] = bsum[blockIdx.x] + e;
+    scan::scan_apply<int, MS_SCAN>([seqf](long i) { return (int)seqf[i]; }, [seqi](long i, int x) { seqi[i] = x; }, bsum[blockIdx.x],
+                                   n);
 }
 
 __global__ __launch_bounds__(MS_BLOCK) void ms_emit_kernel(const int32_t* __restrict__ hdr, const uint8_t* __restrict__ seqf,

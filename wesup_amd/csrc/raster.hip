@@ -13,7 +13,8 @@
 //   rs_box_kernel      a block per feature: its CSR offsets, image index and vertices are checked (a bad feature sets the status
 //                      bit and owns no tile: nothing of it is read again), its bounding box is reduced over the block, clipped to
 //                      the image and cut into tiles; the tile count goes to the scan
-//   rs_scan_blocks, rs_scan_small    the features' first tiles (64-bit, two levels) and the tile total
+//   rs_scan_blocks, rs_scan_small    the features' first tiles (64-bit, two levels: the block scan and the one-block scan of
+//                      scan.hpp; the fill adds the block's offset itself) and the tile total
 //   rs_fill_kernel     a fixed grid striding over the tiles: the tile's feature by bisection; the tile's toggle bits, 64 rows of
 //                      one 64-bit word, zeroed in LDS; the block's threads walk the feature's edges ring by ring and xor one bit
 //                      per crossed centre row; one thread per row turns the toggles into the parity prefix by six shifts; each
@@ -21,6 +22,7 @@
 //   rs_values_kernel   out8 = values[label - 1], 0 where the label is 0
 #include "common.hpp"
 #include "raster.hpp"
+#include "scan.hpp"
 
 #define RS_TILE_ROWS WESUP_RASTER_TILE_ROWS
 #define RS_TILE_COLS WESUP_RASTER_TILE_COLS
@@ -37,23 +39,6 @@ static_assert(RS_TILE_ROWS <= RS_BLOCK && RS_BLOCK % 64 == 0 && 2 * RS_TILE_ROWS
 namespace {
 
 typedef unsigned long long u64;
-
-// exclusive scan of RS_SCAN values, one per thread
-__device__ __forceinline__ u64 block_scan(u64 v, u64* sh, u64* total) {
-    const int tid = threadIdx.x;
-    sh[tid] = v;
-    __syncthreads();
-    for (int off = 1; off < RS_SCAN; off <<= 1) {
-        const u64 t = (tid >= off) ? sh[tid - off] : 0ull;
-        __syncthreads();
-        sh[tid] += t;
-        __syncthreads();
-    }
-    const u64 incl = sh[tid];
-    *total = sh[RS_SCAN - 1];
-    __syncthreads();
-    return incl - v;
-}
 
 // box [F]: {first tile column, first tile row, tile columns, image}; cnt [F]: the feature's tiles
 __global__ __launch_bounds__(RS_BLOCK) void rs_box_kernel(const int32_t* __restrict__ verts, const int32_t* __restrict__ ring_first,
@@ -128,20 +113,13 @@ __global__ __launch_bounds__(RS_SCAN) void rs_scan_blocks(u64* __restrict__ cnt,
     __shared__ u64 sh[RS_SCAN];
     const long i = (long)blockIdx.x * RS_SCAN + threadIdx.x;
     u64 tot;
-    const u64 e = block_scan(i < n ? cnt[i] : 0ull, sh, &tot);
+    const u64 e = scan::block_scan<u64, RS_SCAN>(i < n ? cnt[i] : 0ull, sh, &tot);
     if (i < n) cnt[i] = e;
     if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
 }
 __global__ __launch_bounds__(RS_SCAN) void rs_scan_small(u64* __restrict__ v, int n, u64* __restrict__ total_out) {
-    __shared__ u64 sh[RS_SCAN];
-    u64 run = 0;
-    for (int i0 = 0; i0 < n; i0 += RS_SCAN) {
-        const int i = i0 + threadIdx.x;
-        u64 tot;
-        const u64 e = block_scan(i < n ? v[i] : 0ull, sh, &tot);
-        if (i < n) v[i] = run + e;
-        run += tot;
-    }
+    u64 run;
+    scan::scan_small<u64, RS_SCAN>(v, n, &run);
     if (threadIdx.x == 0) *total_out = run;
 }
 

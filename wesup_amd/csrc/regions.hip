@@ -9,13 +9,14 @@
 //   1. rg_tile_kernel    one block per 16 x 16 tile: union-find in LDS, then parent[p] = global index of the tile-local root;
 //   2. rg_border_kernel  unions only across tile borders, in global memory, with atomicMin (as uf_union of slic.hip);
 //   3. rg_flatten_kernel parent[p] = root (and the root flags / the areas per root);
-//   4. the three-kernel scan of the root flags and the relabel: ids 1..n in raster order of the first pixel.
+//   4. the three-kernel scan of the root flags (scan.hpp) and the relabel: ids 1..n in raster order of the first pixel.
 // Parents only ever decrease, so every find / union loop terminates.  Merge, flatten and renumber are separate launches: the
 // kernel boundary makes one XCD's writes visible to the others.  Inside the merge kernel a load of parent[] may be stale; it is
 // then an OLDER parent of that pixel, i.e. still a member of the same tree with an index >= the current one, and the atomicMin
 // returns the true previous value, from which the union continues -- the loads are agent-scope atomic loads all the same (they
 // bypass the CU's L1, which no other CU's store refreshes).
 #include "common.hpp"
+#include "scan.hpp"
 
 #define RG_TILE 16
 #define RG_SCAN 1024
@@ -150,63 +151,26 @@ __global__ void rg_flatten_kernel(int* __restrict__ parent, int32_t* __restrict_
     }
 }
 
-// exclusive scan of 1024 values, one per thread
-__device__ __forceinline__ int block_scan_1024(int v, int* sh, int* total) {
-    const int tid = threadIdx.x;
-    sh[tid] = v;
-    __syncthreads();
-    for (int off = 1; off < RG_SCAN; off <<= 1) {
-        const int t = (tid >= off) ? sh[tid - off] : 0;
-        __syncthreads();
-        sh[tid] += t;
-        __syncthreads();
-    }
-    const int incl = sh[tid];
-    *total = sh[RG_SCAN - 1];
-    __syncthreads();
-    return incl - v;
-}
+// the scan of the root flags in three kernels (scan.hpp), grid (nblk, B)
 __global__ __launch_bounds__(RG_SCAN) void rg_scan_block_sums(const int32_t* __restrict__ flags, int32_t* __restrict__ bsum,
                                                               long HW, int nblk) {
-    __shared__ int sh[RG_SCAN / 64];
-    const int b = blockIdx.y, blk = blockIdx.x, tid = threadIdx.x;
-    const long p = (long)blk * RG_SCAN + tid;
-    int v = (p < HW) ? flags[(long)b * HW + p] : 0;
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    if ((tid & 63) == 0) sh[tid >> 6] = v;
-    __syncthreads();
-    if (tid == 0) {
-        int s = 0;
-        for (int i = 0; i < RG_SCAN / 64; ++i) s += sh[i];
-        bsum[(long)b * nblk + blk] = s;
-    }
+    const int32_t* f = flags + (long)blockIdx.y * HW;
+    const int s = scan::scan_block_total<int, RG_SCAN>([f](long p) { return f[p]; }, HW);
+    if (threadIdx.x == 0) bsum[(long)blockIdx.y * nblk + blockIdx.x] = s;
 }
 // in-place exclusive scan of n values per image (block b), total -> total_out[b]
 __global__ __launch_bounds__(RG_SCAN) void rg_scan_small(int32_t* __restrict__ vals, int32_t* __restrict__ total_out, int n,
                                                          int stride, int total_stride) {
-    __shared__ int sh[RG_SCAN];
-    int32_t* v = vals + (long)blockIdx.x * stride;
-    int run = 0;
-    for (int i0 = 0; i0 < n; i0 += RG_SCAN) {
-        const int i = i0 + threadIdx.x;
-        const int x = i < n ? v[i] : 0;
-        int tot;
-        const int e = block_scan_1024(x, sh, &tot);
-        if (i < n) v[i] = run + e;
-        run += tot;
-    }
+    int run;
+    scan::scan_small<int, RG_SCAN>(vals + (long)blockIdx.x * stride, n, &run);
     if (threadIdx.x == 0 && total_out) total_out[(long)blockIdx.x * total_stride] = run;
 }
 // flags -> exclusive prefix, in place
 __global__ __launch_bounds__(RG_SCAN) void rg_scan_apply(int32_t* __restrict__ flags, const int32_t* __restrict__ bsum, long HW,
                                                          int nblk) {
-    __shared__ int sh[RG_SCAN];
-    const int b = blockIdx.y, blk = blockIdx.x;
-    const long p = (long)blk * RG_SCAN + threadIdx.x;
-    const int v = (p < HW) ? flags[(long)b * HW + p] : 0;
-    int tot;
-    const int e = block_scan_1024(v, sh, &tot);
-    if (p < HW) flags[(long)b * HW + p] = bsum[(long)b * nblk + blk] + e;
+    int32_t* f = flags + (long)blockIdx.y * HW;
+    scan::scan_apply<int, RG_SCAN>([f](long p) { return f[p]; }, [f](long p, int x) { f[p] = x; },
+                                   bsum[(long)blockIdx.y * nblk + blockIdx.x], HW);
 }
 __global__ void rg_relabel_kernel(const int* __restrict__ parent, const int32_t* __restrict__ newid, int32_t* __restrict__ labels,
                                   long HW, int B) {

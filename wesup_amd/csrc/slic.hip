@@ -15,9 +15,11 @@
 //   4. connectivity: 4-connected components of the label image by lock-free union-find (root = first pixel in
 //      raster order); components smaller than min_size_factor * HW/n are absorbed by the component of the pixel
 //      left of (else above) their first pixel; surviving components are renumbered 0..K-1 in raster order of their
-//      first pixel -- exactly the contiguous 0-based ids _preprocess_superpixels needs (models/wesup.py:41).
+//      first pixel -- exactly the contiguous 0-based ids _preprocess_superpixels needs (models/wesup.py:41).  The
+//      renumbering is the three-pass scan of scan.hpp over the root flags.
 // Everything is integer-deterministic except the float distance comparison itself.
 #include "common.hpp"
+#include "scan.hpp"
 
 #define SLIC_FIX 1048576.0   // 2^20 fixed-point scale of the centre sums
 
@@ -300,48 +302,26 @@ __global__ void ccl_resolve_kernel(const int* __restrict__ parent, const int32_t
     final_root[idx] = r;
     is_root[idx] = (r == p) ? 1 : 0;
 }
-// exclusive scan of is_root over each image (three small kernels: per-block sums, scan of block sums, apply)
+// exclusive scan of is_root over each image in three kernels (scan.hpp): grid (nblk, B), (B), (nblk, B)
 #define SCAN_BLOCK 1024
 __global__ __launch_bounds__(SCAN_BLOCK) void scan_block_sums(const int32_t* __restrict__ flags, int32_t* __restrict__ bsum,
                                                               long HW, int nblk) {
-    __shared__ int sh[SCAN_BLOCK];
-    const int b = blockIdx.y, blk = blockIdx.x;
-    const long p = (long)blk * SCAN_BLOCK + threadIdx.x;
-    sh[threadIdx.x] = (p < HW) ? flags[(long)b * HW + p] : 0;
-    __syncthreads();
-    for (int off = SCAN_BLOCK / 2; off > 0; off >>= 1) {
-        if (threadIdx.x < off) sh[threadIdx.x] += sh[threadIdx.x + off];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) bsum[(long)b * nblk + blk] = sh[0];
+    const int32_t* f = flags + (long)blockIdx.y * HW;
+    const int s = scan::scan_block_total<int, SCAN_BLOCK>([f](long p) { return f[p]; }, HW);
+    if (threadIdx.x == 0) bsum[(long)blockIdx.y * nblk + blockIdx.x] = s;
 }
-__global__ void scan_of_block_sums(int32_t* __restrict__ bsum, int32_t* __restrict__ n_labels, int nblk) {
-    const int b = blockIdx.x;
-    if (threadIdx.x == 0) {
-        int run = 0;
-        for (int i = 0; i < nblk; ++i) {
-            const int v = bsum[(long)b * nblk + i];
-            bsum[(long)b * nblk + i] = run;
-            run += v;
-        }
-        n_labels[b] = run;
-    }
+__global__ __launch_bounds__(SCAN_BLOCK) void scan_of_block_sums(int32_t* __restrict__ bsum, int32_t* __restrict__ n_labels,
+                                                                 int nblk) {
+    int run;
+    scan::scan_small<int, SCAN_BLOCK>(bsum + (long)blockIdx.x * nblk, nblk, &run);
+    if (threadIdx.x == 0) n_labels[blockIdx.x] = run;
 }
 __global__ __launch_bounds__(SCAN_BLOCK) void scan_apply(const int32_t* __restrict__ flags, const int32_t* __restrict__ bsum,
                                                          int32_t* __restrict__ newid, long HW, int nblk) {
-    __shared__ int sh[SCAN_BLOCK];
-    const int b = blockIdx.y, blk = blockIdx.x, tid = threadIdx.x;
-    const long p = (long)blk * SCAN_BLOCK + tid;
-    const int v = (p < HW) ? flags[(long)b * HW + p] : 0;
-    sh[tid] = v;
-    __syncthreads();
-    for (int off = 1; off < SCAN_BLOCK; off <<= 1) {
-        const int t = (tid >= off) ? sh[tid - off] : 0;
-        __syncthreads();
-        sh[tid] += t;
-        __syncthreads();
-    }
-    if (p < HW) newid[(long)b * HW + p] = bsum[(long)b * nblk + blk] + sh[tid] - v;     // exclusive
+    const int32_t* f = flags + (long)blockIdx.y * HW;
+    int32_t* out = newid + (long)blockIdx.y * HW;
+    scan::scan_apply<int, SCAN_BLOCK>([f](long p) { return f[p]; }, [out](long p, int x) { out[p] = x; },
+                                      bsum[(long)blockIdx.y * nblk + blockIdx.x], HW);
 }
 __global__ void relabel_kernel(const int32_t* __restrict__ final_root, const int32_t* __restrict__ newid,
                                int32_t* __restrict__ labels, long HW, int B) {
@@ -441,7 +421,7 @@ extern "C" int wesup_slic(const float* img_nchw, int32_t* labels, int32_t* n_lab
     WESUP_LAUNCH(ccl_absorb_kernel, dim3(pb), dim3(256), 0, st, parent, size, target, W, HW, B, min_size);
     WESUP_LAUNCH(ccl_resolve_kernel, dim3(pb), dim3(256), 0, st, parent, target, final_root, is_root, HW, B);
     WESUP_LAUNCH(scan_block_sums, dim3(nblk, B), dim3(SCAN_BLOCK), 0, st, is_root, bsum, HW, nblk);
-    WESUP_LAUNCH(scan_of_block_sums, dim3(B), dim3(64), 0, st, bsum, n_labels, nblk);
+    WESUP_LAUNCH(scan_of_block_sums, dim3(B), dim3(SCAN_BLOCK), 0, st, bsum, n_labels, nblk);
     WESUP_LAUNCH(scan_apply, dim3(nblk, B), dim3(SCAN_BLOCK), 0, st, is_root, bsum, newid, HW, nblk);
     WESUP_LAUNCH(relabel_kernel, dim3(pb), dim3(256), 0, st, final_root, newid, labels, HW, B);
     WESUP_CHECK_LAUNCH();

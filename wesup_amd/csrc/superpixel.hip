@@ -7,6 +7,7 @@
 // load instruction of a wave is 1 KiB contiguous, there are no atomics, and the summation order is fixed
 // (ascending pixel index), so results are bitwise reproducible.
 #include "common.hpp"
+#include "scan.hpp"
 
 #define SP_CHUNK 2048            // pixels per counting-sort chunk
 #define SP_MAX_K 16384           // LDS histogram capacity (ids per image)
@@ -25,26 +26,10 @@
 //      all loads of a thread in flight at once; (b) one block per image does what needs all ids: the reference ordering, labels,
 //      row starts, segment table -- O(Kmax / 1024) per thread, from the sums;
 //   3. sp_place_kernel, one wave per chunk: places the pixels (stable: ascending pixel index inside a row).
-// No hand-off between blocks inside a launch, no library-side state: any B, any number of streams.
+// No hand-off between blocks inside a launch, no library-side state: any B, any number of streams.  The per-image scans of
+// (2b) and of sp_segments_kernel are scan::block_scan (scan.hpp), one value per thread of a 1024-thread block.
 #define SP_SCAN_COLS 64
 #define SP_SCAN_SEGS 16
-
-// block-wide exclusive scan of one int per thread (1024 threads); returns the exclusive prefix, total in *total
-__device__ int block_excl_scan(int v, int* total, int* sh /*[1024]*/) {
-    const int tid = threadIdx.x;
-    sh[tid] = v;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {
-        const int t = (tid >= off) ? sh[tid - off] : 0;
-        __syncthreads();
-        sh[tid] += t;
-        __syncthreads();
-    }
-    const int incl = sh[tid];
-    *total = sh[1023];
-    __syncthreads();
-    return incl - v;
-}
 
 struct SpPre {
     const int32_t* labels;
@@ -164,7 +149,7 @@ __device__ void sp_order_image(const SpPre& p, int b, int* sh /*[1024]*/) {
     if (tid == 0) p.status[b] = stat | (sh[0] ? 2 : 0);
     __syncthreads();
     int total_l;
-    const int pre_l = block_excl_scan(nlab, &total_l, sh);
+    const int pre_l = scan::block_scan<int, 1024>(nlab, sh, &total_l);
     // second pass: assign rows
     int rl = pre_l, ru = total_l + (min(i0, n) - pre_l);
     int asum = 0;
@@ -202,7 +187,7 @@ __device__ void sp_order_image(const SpPre& p, int b, int* sh /*[1024]*/) {
     int32_t* rs = p.row_start + (long)b * (Kmax + 1);
     for (int r = i0; r < i1; ++r) asum += p.area_new[(long)b * Kmax + r];
     int tot;
-    int pre = block_excl_scan(asum, &tot, sh);
+    int pre = scan::block_scan<int, 1024>(asum, sh, &tot);
     for (int r = i0; r < i1; ++r) {
         rs[r] = pre;
         pre += p.area_new[(long)b * Kmax + r];
@@ -214,7 +199,7 @@ __device__ void sp_order_image(const SpPre& p, int b, int* sh /*[1024]*/) {
         int c = 0;
         for (int r = i0; r < i1; ++r) c += max(1, (rs[r + 1] - rs[r] + SP_SEG - 1) / SP_SEG);
         int total;
-        int ps = block_excl_scan(c, &total, sh);
+        int ps = scan::block_scan<int, 1024>(c, sh, &total);
         for (int r = i0; r < i1; ++r) {
             const int k = max(1, (rs[r + 1] - rs[r] + SP_SEG - 1) / SP_SEG);
             p.seg_start[(long)b * (Kmax + 1) + r] = ps;
@@ -447,7 +432,7 @@ __global__ __launch_bounds__(1024) void sp_segments_kernel(const int32_t* __rest
     int cnt = 0;
     for (int r = i0; r < i1; ++r) cnt += max(1, (rs[r + 1] - rs[r] + SP_SEG - 1) / SP_SEG);
     int total;
-    int pre = block_excl_scan(cnt, &total, sh);
+    int pre = scan::block_scan<int, 1024>(cnt, sh, &total);
     for (int r = i0; r < i1; ++r) {
         const int n = max(1, (rs[r + 1] - rs[r] + SP_SEG - 1) / SP_SEG);
         seg_start[(long)b * (Kmax + 1) + r] = pre;
