@@ -315,6 +315,9 @@ int wesup_gemm_tn(const float* A, int lda, const float* B, int ldb, float* C, in
                   int M, int N, int K, int relu_b, void* ws, size_t ws_bytes, void* stream);
 /* nbatch products of one shape in one launch: C_b = A_b^T . B_b, element strides between batch entries */
 size_t wesup_gemm_tn_batched_workspace_bytes(int nbatch, int M, int N, int K);
+/* length of the K ranges whose sums that entry adds in ascending order (>= K: one range); equal ranges, i.e. not the
+ * weighted split of a single product of 128 x 128 tiles */
+int wesup_gemm_tn_batched_k_per_split(int nbatch, int M, int N, int K);
 int wesup_gemm_tn_batched(const float* A, int lda, long strideA, const float* B, int ldb, long strideB,
                           float* C, int ldc, long strideC, int nbatch, int M, int N, int K, int relu_b,
                           void* ws, size_t ws_bytes, void* stream);
@@ -390,6 +393,20 @@ int wesup_sp_pool_upsample_fwd(const float* s, const int32_t* pix_sorted, const 
  * (on Wm^T resp. Wm); used for the deep layers, where Wm is small (models/wesup.py:254-261 + :283-285 and autograd) */
 int wesup_sp_interp_matrix(const int32_t* pix_sorted, const int32_t* row_start, float* Wm,
                            int B, int H, int W, int h, int w, int Kmax, void* stream);
+/* The two products of Wm, each by the route its size asks for.  Operands: Wm [B][Kmax][hw] and its transpose WmT [B][hw][Kmax],
+ * s / ds [B][hw][C] contiguous, and the C channels at channel `off` of the superpixel-side rows sp / gsp [B][Kmax][ld]
+ * (C, ld, off multiples of 4, off + C <= ld, hw <= 8192).
+ *   fwd:  sp[b][r][off..off+C) = sum_q Wm[b][r][q] s[b][q][.]        bwd:  ds[b][q][.] = sum_r Wm[b][r][q] gsp[b][r][off..off+C)
+ * Below the size rule (wesup_sp_pool_mat_route(Kmax, hw) == 0: Kmax * hw under 65 536 entries, or under what
+ * WESUP_POOL_MAT_SPARSE_MIN says -- 0: never sparse, 1: always) they issue exactly wesup_gemm_tn_batched on WmT resp. Wm, with its
+ * conditions (Kmax, hw multiples of 4) and its workspace (wesup_gemm_tn_batched_workspace_bytes(B, Kmax, C, hw) resp.
+ * (B, hw, C, Kmax)).  Above it one kernel walks the non-zeros of each row (column) in ascending index, adding in the order of the dense product's own additions (its K ranges): a fixed-order sum,
+ * no atomics, bitwise reproducible, no workspace (ws may be NULL); an all-zero row (column) gives exact zeros. */
+int wesup_sp_pool_mat_route(int Kmax, int hw);
+int wesup_sp_pool_mat_fwd(const float* Wm, const float* WmT, const float* s, float* sp, int ld, int off,
+                          int B, int Kmax, int hw, int C, void* ws, size_t ws_bytes, void* stream);
+int wesup_sp_pool_mat_bwd(const float* Wm, const float* WmT, const float* gsp, int ld, int off, float* ds,
+                          int B, int Kmax, int hw, int C, void* ws, size_t ws_bytes, void* stream);
 /* dfm[b][p][c] = g[b][new_row[p]][c] / area[new_row[p]] */
 int wesup_sp_pool_bwd(const float* g, const int32_t* new_row, const int32_t* area_new, float* dfm,
                       int B, int HW, int ldf, int C, int Kmax, void* stream);

@@ -75,6 +75,7 @@ _SIGS = {
     'wesup_gemm_tn_workspace_bytes': (c_size_t, 'iii'),
     'wesup_gemm_tn': (c_int, 'pipipipiiiipzp'),
     'wesup_gemm_tn_batched_workspace_bytes': (c_size_t, 'iiii'),
+    'wesup_gemm_tn_batched_k_per_split': (c_int, 'iiii'),
     'wesup_gemm_tn_batched': (c_int, 'pilpilpiliiiiipzp'),
     'wesup_colsum_workspace_bytes': (c_size_t, 'ii'),
     'wesup_colsum': (c_int, 'pipiipzp'),
@@ -93,6 +94,9 @@ _SIGS = {
     'wesup_sp_pool_bwd': (c_int, 'ppppiiiiip'),
     'wesup_sp_pool_upsample_fwd': (c_int, 'ppppppiiiiiiiiiipzp'),
     'wesup_sp_interp_matrix': (c_int, 'pppiiiiiip'),
+    'wesup_sp_pool_mat_route': (c_int, 'ii'),
+    'wesup_sp_pool_mat_fwd': (c_int, 'pppp' + 'ii' + 'iiii' + 'pzp'),
+    'wesup_sp_pool_mat_bwd': (c_int, 'ppp' + 'ii' + 'p' + 'iiii' + 'pzp'),
     'wesup_paint_fwd': (c_int, 'pppiiiiip'),
     'wesup_slic_num_centers': (c_int, 'iii'),
     'wesup_slic_workspace_bytes': (c_size_t, 'iiii'),

@@ -1259,6 +1259,12 @@ extern "C" size_t wesup_gemm_tn_batched_workspace_bytes(int nbatch, int M, int N
     const TnPlan pl = plan_tn(M, N, K, 1, nbatch);
     return (size_t)nbatch * pl.S * tn_slab_stride(M, pl.Nslab) * sizeof(float);
 }
+// the length of the K ranges of that plan (K or more: one range): the order of wesup_gemm_tn_batched's additions, for a caller
+// that adds the same products itself (superpixel.hip: the products of Wm by its non-zeros)
+extern "C" int wesup_gemm_tn_batched_k_per_split(int nbatch, int M, int N, int K) {
+    if (nbatch <= 0 || M <= 0 || N <= 0 || K <= 0) return 0;
+    return plan_tn(M, N, K, 1, nbatch).k_per_split;
+}
 extern "C" int wesup_gemm_tn_batched(const float* A, int lda, long strideA, const float* B, int ldb, long strideB, float* C,
                                      int ldc, long strideC, int nbatch, int M, int N, int K, int relu_b, void* ws,
                                      size_t ws_bytes, void* stream) {

@@ -8,6 +8,7 @@
 // (ascending pixel index), so results are bitwise reproducible.
 #include "common.hpp"
 #include "scan.hpp"
+#include "pool_mat_route.hpp"
 
 #define SP_CHUNK 2048            // pixels per counting-sort chunk
 #define SP_MAX_K 16384           // LDS histogram capacity (ids per image)
@@ -809,6 +810,264 @@ extern "C" int wesup_sp_interp_matrix(const int32_t* pix_sorted, const int32_t* 
     const float sh = H > 1 ? (float)(h - 1) / (float)(H - 1) : 0.f, sw = W > 1 ? (float)(w - 1) / (float)(W - 1) : 0.f;
     WESUP_LAUNCH(sp_interp_matrix_kernel, dim3(Kmax, B), dim3(256), (size_t)h * w * sizeof(unsigned long long),
                        (hipStream_t)stream, pix_sorted, row_start, Wm, H, W, h, w, Kmax, make_fastdiv(W), sh, sw);
+    WESUP_CHECK_LAUNCH();
+    return WESUP_OK;
+}
+
+// ------------------------------------------------------------------ applying Wm by its non-zeros
+// A row of Wm has a non-zero weight only at the cells its superpixel's pixels interpolate from (a few dozen of 3600 at
+// 480 x 480 with 576 superpixels), a column only at the 2 - 6 superpixels that touch the cell: the dense GEMMs of Wm . s and
+// Wm^T . g multiply by an exact zero more than 99 times out of 100.  Above the size rule of pool_mat_route.hpp the two entries
+// below run one kernel each that reads the matrix once, compacts a row's (column's) non-zeros into LDS in ascending index --
+// per-wave ballots, the wave offsets added in wave order: no atomics -- and sums w * operand row over that list in list order
+// (fmaf, in the order of the dense product's own additions): a fixed-order sum, the same bits from run to run and for every grid.  Below the rule
+// they issue exactly what wesup_gemm_tn_batched issues.
+#define PM_CHUNK 2048            // forward: cells of a row per list chunk, 8 per thread of the 256-thread block
+#define PM_ROWS 512              // backward: rows of a column per list chunk, 8 per lane of the wave
+#define PM_PER 8
+
+// The order of the additions is the dense product's own, so that a step computes the same bits on either route:
+// wesup_gemm_tn_batched cuts K (the cells of a row, the rows of a column) into ranges of k_per_split, adds the products of a
+// range one after the other into one accumulator that starts at zero (the MFMA's K loop, one fused multiply-add per k; a zero
+// weight leaves the accumulator as it is), and adds the ranges' sums in ascending order (tn_reduce_kernel; one range: the
+// accumulator is the result).  Here acc is the chain of the range that ends at kend and tot the sum of the finished ranges.
+#define PM_FMA4(acc_, a, wt) acc_.x = fmaf(wt, a.x, acc_.x); acc_.y = fmaf(wt, a.y, acc_.y); acc_.z = fmaf(wt, a.z, acc_.z); acc_.w = fmaf(wt, a.w, acc_.w)
+__device__ __forceinline__ float4 pm_sum(const float4 x, const float4 y) {
+    return make_float4(x.x + y.x, x.y + y.y, x.z + y.z, x.w + y.w);
+}
+// index k opens a later range: close the ranges before it (an empty range adds a zero)
+__device__ __forceinline__ void pm_edge(float4& acc, float4& tot, int& kend, int kps, int k) {
+    while (k >= kend) {
+        tot = pm_sum(tot, acc);
+        acc = make_float4(0.f, 0.f, 0.f, 0.f);
+        kend += kps;
+    }
+}
+
+// the entries j in [0, n) of the list, in ascending j: acc = fmaf(lw[j], src[lq[j] * ld ..+4), acc) within a K range, 8 (then 4)
+// 16-byte loads in flight
+__device__ __forceinline__ void pm_walk(float4& acc, float4& tot, int& kend, int kps, const float* __restrict__ src, long ld,
+                                        const int* lq, const float* lw, int n) {
+    int j = 0;
+    for (; j + 8 <= n; j += 8) {
+        float4 a[8];
+        float wt[8];
+        int qi[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) { qi[u] = lq[j + u]; a[u] = ld4(src + qi[u] * ld); wt[u] = lw[j + u]; }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) { pm_edge(acc, tot, kend, kps, qi[u]); PM_FMA4(acc, a[u], wt[u]); }
+    }
+    if (j + 4 <= n) {
+        float4 a[4];
+        float wt[4];
+        int qi[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) { qi[u] = lq[j + u]; a[u] = ld4(src + qi[u] * ld); wt[u] = lw[j + u]; }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) { pm_edge(acc, tot, kend, kps, qi[u]); PM_FMA4(acc, a[u], wt[u]); }
+        j += 4;
+    }
+    {                                       // the last <= 3 entries: their loads issued together as well
+        float4 a[3];
+        float wt[3];
+        int qi[3];
+#pragma unroll
+        for (int u = 0; u < 3; ++u)
+            if (j + u < n) { qi[u] = lq[j + u]; a[u] = ld4(src + qi[u] * ld); wt[u] = lw[j + u]; }
+#pragma unroll
+        for (int u = 0; u < 3; ++u)
+            if (j + u < n) { pm_edge(acc, tot, kend, kps, qi[u]); PM_FMA4(acc, a[u], wt[u]); }
+    }
+}
+
+// out[b][r][0..C) = sum_q Wm[b][r][q] * s[b][q][0..C): one block per (r, b), one thread per channel quad (C in slabs of 1024).
+__global__ __launch_bounds__(256) void sp_pool_mat_fwd_kernel(const float* __restrict__ Wm, const float* __restrict__ s,
+                                                              float* __restrict__ out, int Kmax, int hw, int C4, int ldo,
+                                                              int kps) {
+    __shared__ int lq[PM_CHUNK];
+    __shared__ float lw[PM_CHUNK];
+    __shared__ int wcnt[4 * PM_PER];         // non-zeros of (pass i, wave), in list order
+    __shared__ int woff[4 * PM_PER + 1];     // their exclusive prefix, and the total
+    const int r = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float* row = Wm + ((long)b * Kmax + r) * hw;
+    const float* sb = s + (long)b * hw * (4l * C4);
+    float* o = out + ((long)b * Kmax + r) * ldo;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    for (int c0 = 0; c0 < C4; c0 += 256) {
+        const int c4 = c0 + tid;
+        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f), tot = acc;
+        int kend = kps;
+        for (int base = 0; base < hw; base += PM_CHUNK) {
+            float v[PM_PER];
+#pragma unroll
+            for (int i = 0; i < PM_PER; ++i) {
+                const int q = base + i * 256 + tid;
+                v[i] = q < hw ? row[q] : 0.f;
+            }
+#pragma unroll
+            for (int i = 0; i < PM_PER; ++i) {
+                const unsigned long long m = __ballot(v[i] != 0.f);
+                if (lane == 0) wcnt[i * 4 + wave] = __popcll(m);
+            }
+            __syncthreads();
+            if (wave == 0) {                 // exclusive prefix of the 32 counts, by the whole first wave
+                const int c = lane < 4 * PM_PER ? wcnt[lane] : 0;
+                int x = c;
+#pragma unroll
+                for (int d = 1; d < 64; d <<= 1) {
+                    const int y = __shfl_up(x, d);
+                    if (lane >= d) x += y;
+                }
+                if (lane < 4 * PM_PER) woff[lane] = x - c;
+                if (lane == 4 * PM_PER - 1) woff[4 * PM_PER] = x;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int i = 0; i < PM_PER; ++i) {
+                const bool nz = v[i] != 0.f;
+                const unsigned long long m = __ballot(nz);
+                if (nz) {
+                    const int k = woff[i * 4 + wave] + __popcll(m & below);
+                    lq[k] = base + i * 256 + tid;
+                    lw[k] = v[i];
+                }
+            }
+            __syncthreads();
+            if (c4 < C4) pm_walk(acc, tot, kend, kps, sb + 4 * c4, 4l * C4, lq, lw, woff[4 * PM_PER]);
+            __syncthreads();                 // the next chunk (or slab) rewrites the list
+        }
+        if (c4 < C4) st4(o + 4 * c4, pm_sum(tot, acc));
+    }
+}
+
+// ds[b][q][0..C) = sum_r WmT[b][q][r] * g[b][r][0..C): one wave per (q, b), four cells per block, a lane holds the channel
+// quads lane, lane + 64, lane + 128, lane + 192 of a 1024-channel slab.
+__global__ __launch_bounds__(256) void sp_pool_mat_bwd_kernel(const float* __restrict__ WmT, const float* __restrict__ g,
+                                                              float* __restrict__ ds, int Kmax, int hw, int C4, int ldg,
+                                                              int kps) {
+    __shared__ int lr[4][PM_ROWS];
+    __shared__ float lw[4][PM_ROWS];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.y;
+    const int q = blockIdx.x * 4 + wave;
+    const bool live = q < hw;                // (a wave past the last cell walks the last cell again and stores nothing)
+    const int qc = live ? q : hw - 1;
+    const float* col = WmT + ((long)b * hw + qc) * Kmax;
+    const float* gb = g + (long)b * Kmax * ldg;
+    float* o = ds + ((long)b * hw + qc) * (4l * C4);
+    const unsigned long long below = (1ull << lane) - 1ull;
+    for (int c0 = 0; c0 < C4; c0 += 256) {
+        float4 acc[4], tot[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) acc[k] = tot[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+        int kend = kps;
+        for (int base = 0; base < Kmax; base += PM_ROWS) {
+            float v[PM_PER];
+#pragma unroll
+            for (int i = 0; i < PM_PER; ++i) {
+                const int r = base + i * 64 + lane;
+                v[i] = r < Kmax ? col[r] : 0.f;
+            }
+            int n = 0;
+#pragma unroll
+            for (int i = 0; i < PM_PER; ++i) {
+                const bool nz = v[i] != 0.f;
+                const unsigned long long m = __ballot(nz);
+                if (nz) {
+                    const int k = n + __popcll(m & below);
+                    lr[wave][k] = base + i * 64 + lane;
+                    lw[wave][k] = v[i];
+                }
+                n += __popcll(m);
+            }
+            __syncthreads();
+            // two list entries x the slab's quads per round: up to 8 loads of a lane in flight.  nk is the same for the whole
+            // wave; a lane past the last quad of the last 64 reads quad 0 again and stores nothing.
+            const int nk = min(4, (C4 - c0 + 63) >> 6);
+            const float* gk[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int c4 = c0 + k * 64 + lane;
+                gk[k] = gb + 4 * (c4 < C4 ? c4 : 0);
+            }
+            const int* rl = lr[wave];
+            const float* wl = lw[wave];
+            // (the range edge is the same for the four quads: one test per list entry)
+#define PM_EDGE4(r_)                                                                        \
+    while ((r_) >= kend) {                                                                  \
+        _Pragma("unroll") for (int k = 0; k < 4; ++k) {                                     \
+            tot[k] = pm_sum(tot[k], acc[k]);                                                \
+            acc[k] = make_float4(0.f, 0.f, 0.f, 0.f);                                       \
+        }                                                                                   \
+        kend += kps;                                                                        \
+    }
+            int j = 0;
+            for (; j + 2 <= n; j += 2) {
+                const int i0 = rl[j], i1 = rl[j + 1];
+                const long r0 = (long)i0 * ldg, r1 = (long)i1 * ldg;
+                const float w0 = wl[j], w1 = wl[j + 1];
+                float4 a0[4], a1[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (k < nk) { a0[k] = ld4(gk[k] + r0); a1[k] = ld4(gk[k] + r1); }
+                PM_EDGE4(i0)
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (k < nk) { PM_FMA4(acc[k], a0[k], w0); }
+                PM_EDGE4(i1)
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (k < nk) { PM_FMA4(acc[k], a1[k], w1); }
+            }
+            if (j < n) {
+                const int i0 = rl[j];
+                const long r0 = (long)i0 * ldg;
+                const float w0 = wl[j];
+                float4 a0[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (k < nk) a0[k] = ld4(gk[k] + r0);
+                PM_EDGE4(i0)
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (k < nk) { PM_FMA4(acc[k], a0[k], w0); }
+            }
+#undef PM_EDGE4
+            __syncthreads();
+        }
+        if (live) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int c4 = c0 + k * 64 + lane;
+                if (c4 < C4) st4(o + 4 * c4, pm_sum(tot[k], acc[k]));
+            }
+        }
+    }
+}
+
+
+extern "C" int wesup_sp_pool_mat_route(int Kmax, int hw) { return pool_mat_sparse(Kmax, hw) ? 1 : 0; }
+
+extern "C" int wesup_sp_pool_mat_fwd(const float* Wm, const float* WmT, const float* s, float* sp, int ld, int off, int B,
+                                     int Kmax, int hw, int C, void* ws, size_t ws_bytes, void* stream) {
+    if (!pool_mat_operands_ok(Wm, WmT, s, sp, ld, off, B, Kmax, hw, C)) return WESUP_ERR_INVALID;
+    if (!pool_mat_sparse(Kmax, hw))          // sp slice = (WmT)^T . s: today's launches, plan and workspace
+        return wesup_gemm_tn_batched(WmT, Kmax, (long)hw * Kmax, s, C, (long)hw * C, sp + off, ld, (long)Kmax * ld, B, Kmax, C,
+                                     hw, 0, ws, ws_bytes, stream);
+    WESUP_LAUNCH(sp_pool_mat_fwd_kernel, dim3(Kmax, B), dim3(256), 0, (hipStream_t)stream, Wm, s, sp + off, Kmax, hw, C / 4, ld,
+                 wesup_gemm_tn_batched_k_per_split(B, Kmax, C, hw));
+    WESUP_CHECK_LAUNCH();
+    return WESUP_OK;
+}
+
+extern "C" int wesup_sp_pool_mat_bwd(const float* Wm, const float* WmT, const float* gsp, int ld, int off, float* ds, int B,
+                                     int Kmax, int hw, int C, void* ws, size_t ws_bytes, void* stream) {
+    if (!pool_mat_operands_ok(Wm, WmT, ds, gsp, ld, off, B, Kmax, hw, C)) return WESUP_ERR_INVALID;
+    if (!pool_mat_sparse(Kmax, hw))          // ds = (Wm)^T . gsp slice
+        return wesup_gemm_tn_batched(Wm, hw, (long)Kmax * hw, gsp + off, ld, (long)Kmax * ld, ds, C, (long)hw * C, B, hw, C,
+                                     Kmax, 0, ws, ws_bytes, stream);
+    WESUP_LAUNCH(sp_pool_mat_bwd_kernel, dim3(ceil_div(hw, 4), B), dim3(256), 0, (hipStream_t)stream, WmT, gsp + off, ds, Kmax,
+                 hw, C / 4, ld, wesup_gemm_tn_batched_k_per_split(B, hw, C, Kmax));
     WESUP_CHECK_LAUNCH();
     return WESUP_OK;
 }

@@ -559,9 +559,9 @@ class WesupEngine:
             elif grp is not None:
                 if l == grp.layers[-1]:        # all side outputs of this resolution are in: sp_in slice = Wm . s
                     tok = T.begin('sp_pool_mat_fwd')
-                    ops.gemm_tn_batched(grp.WmT, grp.s.view(B, grp.h * grp.w, grp.C), b.sp_in[:, :, grp.off:grp.off + grp.C],
-                                        ws_tag='side')
-                    T.end(tok, 2.0 * B * Kmax * grp.h * grp.w * grp.C)
+                    ops.sp_pool_mat_fwd(grp.Wm, grp.WmT, grp.s.view(B, grp.h * grp.w, grp.C), b.sp_in, grp.off, ws_tag='side')
+                    # (by Wm's non-zeros above the size rule: their count is not known on the host, so no work figure)
+                    T.end(tok, 0.0 if ops.sp_pool_mat_sparse(Kmax, grp.h * grp.w) else 2.0 * B * Kmax * grp.h * grp.w * grp.C)
             elif self.fuse_pool_fwd:
                 tok = T.begin('sp_pool_up_fwd')
                 ops.sp_pool_upsample_fwd(s_l, meta, b.sp_in, off)
@@ -911,9 +911,8 @@ class WesupEngine:
                     grp = b.groups[Ls[l].group]
                     if l == grp.layers[-1]:      # ds of every layer of this resolution at once: ds = Wm^T . gsp slice
                         tok = T.begin('upsample_mat_bwd')
-                        ops.gemm_tn_batched(grp.Wm, b.gsp[:, :, grp.off:grp.off + grp.C],
-                                            grp.ds.view(B, grp.h * grp.w, grp.C), ws_tag='side')
-                        T.end(tok, 2.0 * B * Kmax * grp.h * grp.w * grp.C)
+                        ops.sp_pool_mat_bwd(grp.Wm, grp.WmT, b.gsp, grp.off, grp.ds.view(B, grp.h * grp.w, grp.C), ws_tag='side')
+                        T.end(tok, 0.0 if ops.sp_pool_mat_sparse(Kmax, grp.h * grp.w) else 2.0 * B * Kmax * grp.h * grp.w * grp.C)
                     tok = None
                     ds2d = b.ds[l].view(P, co // 2)
                 elif ds_ready[l] is not None:

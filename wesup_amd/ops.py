@@ -1049,6 +1049,44 @@ def sp_interp_matrix(meta, h, w, out=None):
     return out
 
 
+def sp_pool_mat_sparse(Kmax, hw):
+    """True where the products of a (Kmax, hw) interpolation-pooling matrix walk its non-zeros, False where they are the dense
+    batched GEMMs (the size rule of csrc/pool_mat_route.hpp; WESUP_POOL_MAT_SPARSE_MIN moves it, read at every call)."""
+    return bool(_lib.load().wesup_sp_pool_mat_route(Kmax, hw))
+
+
+def _pool_mat_args(Wm, WmT, x, sp, off):
+    B, Kmax, hw = Wm.shape
+    C = x.shape[2]
+    for t, n in ((Wm, 'Wm'), (WmT, 'WmT'), (x, 's / ds'), (sp, 'sp')):
+        _chk(t, name=n)
+    assert WmT.shape == (B, hw, Kmax) and x.shape == (B, hw, C) and sp.dim() == 3 and sp.shape[:2] == (B, Kmax)
+    return B, Kmax, hw, C, sp.shape[2]
+
+
+def sp_pool_mat_fwd(Wm, WmT, s, sp, off, ws_tag='default'):
+    """sp[:, :, off:off + C] = Wm . s per image: Wm (B,Kmax,hw), WmT its transpose (B,hw,Kmax), s (B,hw,C), sp (B,Kmax,ld).
+    Dense (gemm_tn_batched on WmT, bit for bit) below the size rule, by Wm's non-zeros in ascending cell order above it."""
+    B, Kmax, hw, C, ld = _pool_mat_args(Wm, WmT, s, sp, off)
+    ws, nbytes = None, 0
+    if not sp_pool_mat_sparse(Kmax, hw):
+        nbytes = _lib.load().wesup_gemm_tn_batched_workspace_bytes(B, Kmax, C, hw)
+        ws = workspace(nbytes, Wm.device, ws_tag)
+    _lib.call('wesup_sp_pool_mat_fwd', _p(Wm), _p(WmT), _p(s), _p(sp), ld, off, B, Kmax, hw, C, _p(ws), nbytes, _stream())
+    return sp
+
+
+def sp_pool_mat_bwd(Wm, WmT, gsp, off, ds, ws_tag='default'):
+    """ds = Wm^T . gsp[:, :, off:off + C] per image: gsp (B,Kmax,ld), ds (B,hw,C).  The two routes of sp_pool_mat_fwd."""
+    B, Kmax, hw, C, ld = _pool_mat_args(Wm, WmT, ds, gsp, off)
+    ws, nbytes = None, 0
+    if not sp_pool_mat_sparse(Kmax, hw):
+        nbytes = _lib.load().wesup_gemm_tn_batched_workspace_bytes(B, hw, C, Kmax)
+        ws = workspace(nbytes, Wm.device, ws_tag)
+    _lib.call('wesup_sp_pool_mat_bwd', _p(Wm), _p(WmT), _p(gsp), ld, off, _p(ds), B, Kmax, hw, C, _p(ws), nbytes, _stream())
+    return ds
+
+
 def sp_pool_bwd(g, meta, out=None):
     _chk(g, name='g')
     B, Kmax, C = g.shape
